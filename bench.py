@@ -2,17 +2,25 @@
 """bench.py -- utterances/sec of one full AVSR train step (fwd + BPTT + clip + Adam) on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--workload c4|c2|c3|c5] [--no-graph] [--video-frontend resnet_cnn|features]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds everything else the line can carry (below): the
+per-kernel event pass with its roofline and live HBM-traffic counters, the greedy / beam decode rates, the other video input form,
+the c2 / c3 / c5 lines, the CPU baseline and, with N > 1, the strong-scaling section.  `--dump-outputs DIR` writes what the last timed
+step computed (loss, global norm, parameters and moving statistics in TF layout) as DIR/<name>.npy; the inputs are seeded, so two
+builds run with the same arguments can be compared array for array.
 
 The headline feeds north_star's synthetic input: T_v = 75 x 36 x 36 x 3 lip crops through the CNN front-end (video.resnet_cnn) for
-every workload with a video stream; the same step on pre-computed 128-d lip features is reported next to it as `without_lip_cnn`.
+every workload with a video stream; with `--full`, the same step on pre-computed 128-d lip features is reported next to it as
+`without_lip_cnn`.
 
 N > 1 is launched by the driver with torch.distributed.run (one rank per GPU, RCCL): utterances are
-sharded across ranks (weak scaling: B utterances PER GPU; a `strong_scaling` object reports the same job at the workload's
-global B), the collectives on the data path are the gradient all-reduce, a 4-float all-reduce of the loss normalisers and the
+sharded across ranks (weak scaling: B utterances PER GPU; with `--full`, a `strong_scaling` object reports the same job at the
+workload's global B), the collectives on the data path are the gradient all-reduce, a 4-float all-reduce of the loss normalisers and the
 two sync-batch-norm reductions of the feature inputs.
 
 Prints ONE JSON line (rank 0).  `value` = utterances processed by all ranks / max-over-ranks wall time,
-inputs resident in HBM.  `roofline` = the dominant kernel of the step (by summed time, measured here with
+inputs resident in HBM.  With `--full`: `roofline` = the dominant kernel of the step (by summed time, measured here with
 HIP events around every launch in a separate eager pass); `cpu_baseline` = the CPU oracle restatement
 (torch-CPU fp32, "port") on a bounded sample of the same workload -- a reported baseline, not a target.
 The reference publishes no number for this metric, so `vs_baseline` is null.
@@ -238,6 +246,27 @@ def measure_traffic(args):
                  "of `bench.py --steps 2 --warmup 1 --no-graph` on the same workload, averages per dispatch")
 
 
+DUMP_BUDGET = 60 << 20          # array bytes of --dump-outputs: 64 MB in all, with room for the .npy headers
+
+
+def dump_outputs(model, out_dir):
+    """What the last timed step computed, as its caller receives it: the loss and global gradient norm train_step returns and the
+    parameters + batch-norm moving statistics it leaves in the model (TF layout, export_tf_weights), one float32 DIR/<name>.npy
+    each ('/' in a variable name becomes '.').  Every workload's arrays fit the budget (12-17 MB); were they to exceed it, each
+    array is cut to a fixed, seeded sample of its elements."""
+    arrays = {"loss": model.loss, "global_norm": model.gnorm}
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    for name, a in model.export_tf_weights("params").items():
+        arrays["param." + name.replace("/", ".")] = np.asarray(a, dtype=np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if total > DUMP_BUDGET:
+            keep = max(1, a.size * DUMP_BUDGET // total)
+            a = a.reshape(-1)[np.sort(np.random.default_rng(7).choice(a.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def collective_selftest(dist, world, rank, backend):
     """Pre-flight for the first contact with N > 1 real devices: before anything is timed, every collective shape the step uses is
     run on buffers with a known answer and checked EXACTLY (small integers: fp32 / fp64 sums are exact) -- the 13 MB fp32 gradient
@@ -297,9 +326,14 @@ def main():
     ap.add_argument("--section", default=None, choices=[None, "aux_frontend", "cpu_baseline", "cpu_baseline_noonednn", "cpu_baseline_sample"], help="internal: run one auxiliary section in a child process and print its JSON")
     ap.add_argument("--strong", action="store_true", help="N > 1: global batch fixed at the workload's B (B/N utterances per GPU) instead of B per GPU")
     ap.add_argument("--no-profile", action="store_true")
-    ap.add_argument("--brief", action="store_true", help="timed steps + the per-kernel event pass only (no counters, decode rates, other input form, CPU baseline)")
-    ap.add_argument("--no-other-workloads", action="store_true", help="skip the c2 / c3 / c5 lines appended to the default c4 run")
+    ap.add_argument("--brief", action="store_true", help="with --full: timed steps + the per-kernel event pass only (no counters, decode rates, other input form, CPU baseline)")
+    ap.add_argument("--no-other-workloads", action="store_true", help="skip the c2 / c3 / c5 lines --full appends to the default c4 run")
+    ap.add_argument("--full", action="store_true", help="also measure the auxiliary figures (per-kernel events + roofline, decode rates, other input form, "
+                                                        "other workloads, CPU baseline, strong scaling); a plain run times the headline step only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy (float32)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # stdout carries exactly ONE line (the JSON): libraries that print banners to fd 1 (RCCL does, through C stdio that is only
     # flushed at exit) are sent to stderr for the whole run; the JSON goes to the saved descriptor at the end
@@ -411,6 +445,8 @@ def main():
         per_rank = [[float(v) for v in a.cpu()] for a in allr]
     loss = float(model.loss.item())
     trace("timed steps done")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(model, args.dump_outputs)
     persist_err = bool(ops.rnn_persistent_error())      # sticky flag of the persistent encoder kernels (a bounded device-side wait expired)
 
     out = {
@@ -442,7 +478,7 @@ def main():
     }
 
     force_strong = force_dist and os.environ.get("AVSR_BENCH_FORCE_STRONG") == "1"      # test hook: this section with one rank
-    if (world > 1 or force_strong) and not args.strong and dist is not None:
+    if args.full and (world > 1 or force_strong) and not args.strong and dist is not None:
         # the same job with the GLOBAL batch fixed at the workload's B (strong scaling): B / N utterances per GPU.  The headline above is
         # weak scaling (B per GPU); both figures are labelled, neither is an efficiency.
         Bs = max(1, wl["B"] // (world if world > 1 else 8))
@@ -471,7 +507,7 @@ def main():
         except Exception as e:      # an auxiliary figure must not take the headline line down
             out["strong_scaling"] = {"value": None, "error": repr(e)}
 
-    if rank == 0 and not args.no_profile:
+    if args.full and rank == 0 and not args.no_profile:
         # per-kernel timing: one eager step with a HIP-event pair around every engine launch
         # The host enqueues slower than these kernels run, so a busy-wait kernel first holds the stream for ~0.4 s:
         # the whole step is queued behind it and then executes back-to-back, and each event pair brackets
@@ -646,7 +682,7 @@ def main():
 
         out["roofline"] = roof(dom)
         out["roofline_other"] = [roof(k) for k in kinds if k != dom and k != "step_dense"]
-    if rank == 0 and world == 1 and not args.no_profile and not args.brief:
+    if args.full and rank == 0 and world == 1 and not args.no_profile and not args.brief:
         # SURVEY 8(d) also asks for the greedy-decode rate: eval graph (no dropout, BN moving statistics), GreedyEmbeddingHelper,
         # T_dec steps per utterance (random weights never emit EOS, so every utterance runs all LDEC steps)
         trace("profile section done")
@@ -675,7 +711,7 @@ def main():
                                          "beam_width": 10, "steps": LDEC}
         except Exception as e:
             out["beam_search_decode"] = {"value": None, "error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_profile and not args.brief and cfg.video_units is not None:
+    if args.full and rank == 0 and world == 1 and not args.no_profile and not args.brief and cfg.video_units is not None:
         # The same workload with the OTHER video input: the headline feeds lip crops through the CNN front-end (north_star's
         # synthetic shape); `without_lip_cnn` is the step on pre-computed 128-d lip features, i.e. the replaced subsystems alone.
         # Runs in a child process: an auxiliary figure must not be able to take the headline line down with it.
@@ -698,14 +734,14 @@ def main():
                 {"value": None, "error": "child exit %d: %s" % (p.returncode, p.stderr.strip().splitlines()[-1][:200] if p.stderr.strip() else "")}
         except Exception as e:
             out[aux_key] = {"value": None, "error": repr(e)}
-    if rank == 0 and world == 1 and not args.brief and not args.no_profile and not args.no_other_workloads and args.workload == "c4" and not args.batch:
+    if args.full and rank == 0 and world == 1 and not args.brief and not args.no_profile and not args.no_other_workloads and args.workload == "c4" and not args.batch:
         # The other BASELINE configs, driver-timed in the same command: the bench line of each (child process, --brief: the timed steps
         # and the per-kernel event pass, nothing else), reduced to its step time, loss and dominant kernel.
         import subprocess
         out["other_workloads"] = {}
         for w in ("c2", "c3", "c5"):
             try:
-                cmd = [sys.executable, os.path.abspath(__file__), "--workload", w, "--steps", "10", "--warmup", "3", "--brief"] + \
+                cmd = [sys.executable, os.path.abspath(__file__), "--workload", w, "--steps", "10", "--warmup", "3", "--full", "--brief"] + \
                       (["--no-graph"] if args.no_graph else []) + (["--no-dropout"] if args.no_dropout else [])
                 p = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
                 lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -723,7 +759,7 @@ def main():
                     "kernel_time_events_ms": {k: v["total_ms"] for k, v in (r.get("kernel_time_events") or {}).items()}}
             except Exception as e:
                 out["other_workloads"][w] = {"value": None, "error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.brief:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.brief:
         # child processes: the CPU oracle is test infrastructure and must not be able to take the headline line down with it; thread
         # count and oneDNN are process-wide, so every leg is its own child.  Main leg = the SAME workload as the timed GPU step (whole
         # batch, same video input); oneDNN on, and once more without it if that child dies (an earlier image's oneDNN convolution

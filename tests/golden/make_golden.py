@@ -11,6 +11,8 @@
    avsr/visualise/00025.html, i.e. `BeamSearchDecoderOutput.scores / predicted_ids / parent_ids` of one utterance as TensorFlow's own
    BeamSearchDecoder produced them (written by avsr/avsr.py:472-487 through avsr/visualise/beam_search.py:create_html), flattened
    to one list per decode step.  The only TensorFlow OUTPUT in the reference tree; it pins the beam bookkeeping (tests/test_beam_trace.py).
+   It is derived from reference_beam_tree_00025.json, the page's tree data and transcript as they stand (extracted when the reference
+   checkout is present, kept otherwise), so the flattening re-runs from the committed files alone.
 """
 import importlib.util
 import json
@@ -21,6 +23,7 @@ import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
+TREE = "reference_beam_tree_00025.json"
 sys.path.insert(0, ROOT)
 
 CASES = {
@@ -111,12 +114,24 @@ def reference_cer():
 def reference_beam_trace():
     import re
     path = "/root/reference/avsr/visualise/00025.html"
-    if not os.path.exists(path):
-        print("reference not present; keeping the committed reference_beam_trace_00025.json")
-        return
-    html = open(path).read()
-    tree = json.loads(re.search(r"var treeData = (\{.*\});\s*\n", html).group(1))
-    transcript = re.search(r'const transcript = "(.*)";', html).group(1)
+    if os.path.exists(path):
+        html = open(path).read()
+        tree = json.loads(re.search(r"var treeData = (\{.*\});\s*\n", html).group(1))
+        transcript = re.search(r'const transcript = "(.*)";', html).group(1)
+        with open(os.path.join(HERE, TREE), "w") as f:
+            json.dump({"source": "georgesterpu/avsr-tf1 avsr/visualise/00025.html: the page's `treeData` and `transcript`, verbatim",
+                       "transcript": transcript, "treeData": tree}, f)
+            f.write("\n")
+    else:
+        print("reference not present; keeping the committed %s" % TREE)
+    beam_trace_from_tree(os.path.join(HERE, TREE))
+
+
+def beam_trace_from_tree(tree_path):
+    """reference_beam_tree_00025.json -> reference_beam_trace_00025.json (in HERE): the search tree flattened to one list per decode step."""
+    with open(tree_path) as f:
+        blob = json.load(f)
+    tree, transcript = blob["treeData"], blob["transcript"]
     levels = {}
 
     def walk(node, parent):                        # node id = [decode step (1-based), beam]; the root is START

@@ -35,8 +35,8 @@ def test_bench_json_contract_and_forced_collectives():
     assert st["ok"] and st["backend"] == "rccl" and st["ranks"] == 1 and forced["rccl_ranks"] == 1 and st["allreduce_13MB_f32_us"] > 0
     assert plain["collective_selftest"] is None and plain["rccl_ranks"] is None
     assert plain["data"].startswith("synthetic, device-resident")
-    # the strong-scaling section `--gpus N > 1` adds (global batch fixed: here 64 / 8 utterances on the one rank)
-    strong = _bench({"AVSR_BENCH_FORCE_DIST": "1", "AVSR_BENCH_FORCE_STRONG": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29535"})
+    # the strong-scaling section `--gpus N > 1 --full` adds (global batch fixed: here 64 / 8 utterances on the one rank)
+    strong = _bench({"AVSR_BENCH_FORCE_DIST": "1", "AVSR_BENCH_FORCE_STRONG": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29535"}, "--full")
     assert strong["strong_scaling"]["value"] > 0 and strong["strong_scaling"]["utterances_per_gpu"] == 8 and strong["scaling"] == "weak"
     assert not strong["strong_scaling"]["persistent_wait_expired"]
     eager = _bench({"AVSR_BENCH_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29534", "AVSR_DP_GRAPH": "0"})
@@ -44,6 +44,36 @@ def test_bench_json_contract_and_forced_collectives():
     assert abs(eager["final_loss"] - plain["final_loss"]) < 1e-4 * max(1.0, abs(plain["final_loss"]))
     assert abs(forced["final_loss"] - plain["final_loss"]) < 1e-4 * max(1.0, abs(plain["final_loss"]))
 
+
+
+def test_plain_run_times_the_steps_only_and_dumps_the_last_steps_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and carries none of the auxiliary sections; --dump-outputs writes the last
+    timed step's loss, global norm and parameters as float32 .npy files (at most 64 MB), the same arrays in two runs."""
+    import numpy as np
+    runs = []
+    for run in range(2):
+        d = tmp_path / ("run%d" % run)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "8",
+                            "--dump-outputs", str(d)], cwd=ROOT, env=dict(os.environ), capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines = [l for l in p.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, p.stdout[-2000:]
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["value"] > 0 and not out["persistent_wait_expired"]
+        for k in ("metric", "unit", "higher_is_better", "dtype"):
+            assert k in out, k
+        for k in ("roofline", "kernel_time_events", "greedy_decode", "beam_search_decode", "without_lip_cnn", "other_workloads", "cpu_baseline",
+                  "strong_scaling"):
+            assert k not in out, k
+        arrays = {f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))}
+        assert sum((d / f).stat().st_size for f in os.listdir(d)) <= 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert abs(float(arrays["loss"][0]) - out["final_loss"]) < 1e-4 and np.isfinite(arrays["global_norm"]).all()
+        assert sum(n.startswith("param.") for n in arrays) > 20 and "param.dec.embedding" in arrays
+        runs.append(arrays)
+    assert sorted(runs[0]) == sorted(runs[1])
+    for n in runs[0]:
+        assert np.array_equal(runs[0][n], runs[1][n]), n
 
 def _ranks_over_gloo(world, batch, steps):
     import socket
@@ -53,7 +83,7 @@ def _ranks_over_gloo(world, batch, steps):
     env = dict(os.environ, AVSR_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", str(steps), "--warmup", "2",
-           "--batch", str(batch), "--video-frontend", "features", "--no-cpu-baseline", "--no-profile"]
+           "--batch", str(batch), "--video-frontend", "features", "--full", "--no-cpu-baseline", "--no-profile"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip().startswith("{")]

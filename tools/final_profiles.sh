@@ -5,8 +5,8 @@
 cd "$(dirname "$0")/.." || exit 1
 R=${1:-r06}; V=${2:-v1}; O=gpurun_out; export TMPDIR=/tmp
 mkdir -p $O/ck
-python bench.py > $O/${R}_bench_default_${V}.json 2> $O/${R}_bench_default_${V}.err
-for w in c2 c3 c5; do timeout 400 python bench.py --workload $w --no-cpu-baseline --steps 10 > $O/${R}_bench_${w}_${V}.json 2>/dev/null; done
+python bench.py --full > $O/${R}_bench_default_${V}.json 2> $O/${R}_bench_default_${V}.err
+for w in c2 c3 c5; do timeout 400 python bench.py --full --workload $w --no-cpu-baseline --steps 10 > $O/${R}_bench_${w}_${V}.json 2>/dev/null; done
 python - <<PY
 import json
 for w in ("default", "c2", "c3", "c5"):
