@@ -219,16 +219,17 @@ class LipCNN:
         self.dcol = torch.empty(max_col, device=dev)              # d col of the layer being differentiated (transient)
         # Weight-gradient slabs: every MFMA convolution gets its own region, so that the twelve final reductions of a backward pass can
         # run as ONE launch at its end (ops.slab_defer_begin / _end) instead of one 5 us launch behind every convolution.
-        self.wg_off, off = {}, 0
+        self.wg_region, off = {}, 0                                 # name -> (first float, floats)
         for op in self.ops:
             if op[0] == "conv" and op[1] in self.mfma:
                 _, name, _src, _dst, k, _s, cin, cout = op
-                self.wg_off[name] = off
                 # the kernel's own rule (conv_bwd_weight_impl): slabs above 2048 floats come from at most 256 workgroups (one per CU:
                 # there the partial slabs, not the staging, are the traffic), smaller ones from up to four workgroups per CU
                 # (a launch covers the whole kernel or a group of its taps: whichever of the two caps needs more floats)
                 slab = max(k * k * cin * cout + cout, 12 * cin * 16 + 16)
-                off += max(256 * slab, 1024 * min(slab, 2048))
+                size = max(256 * slab, 1024 * min(slab, 2048))
+                self.wg_region[name] = (off, size)
+                off += size
         # ONE buffer per model, shared by the LipCNN of every workspace shape (the region sizes do not depend on N; the slabs are live
         # only inside one backward pass, and passes -- eager or replayed graphs -- are serialised on the engine's stream): a buffer
         # per shape was ~180 MB x (8 cached + 8 pinned) shapes
@@ -462,11 +463,13 @@ class LipCNN:
                         x, bn = self._src(src)
                         d = ops.conv_desc(*self.mfma[name], bn=bn)
                         fold = self.fold_src.pop(dst, None)
+                        wo, wn = self.wg_region[name]
+                        ws = self.wg_scratch[wo:wo + wn]                # the kernel clamps its grid to this layer's own region
                         if fold is not None:
-                            ops.conv_bwd_weight_bn(d, x, fold[0], fold[1], fold[2], gk.t[gk.off:], gb.t[gb.off:], self.wg_scratch[self.wg_off[name]:],
+                            ops.conv_bwd_weight_bn(d, x, fold[0], fold[1], fold[2], gk.t[gk.off:], gb.t[gb.off:], ws,
                                                    dx_out=fold[3] if src != "in" else None)
                         else:
-                            ops.conv_bwd_weight(d, x, self.gmaps[dst], gk.t[gk.off:], gb.t[gb.off:], self.wg_scratch[self.wg_off[name]:])
+                            ops.conv_bwd_weight(d, x, self.gmaps[dst], gk.t[gk.off:], gb.t[gb.off:], ws)
                         fused_bn = self.bnb_conv.get(name)
                         if src != "in" and fused_bn is not None and src in self.lazy:
                             g, beta = target(src)

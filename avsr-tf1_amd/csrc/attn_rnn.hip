@@ -194,7 +194,7 @@ __global__ __launch_bounds__(256) void logits_sample_kernel(const float* x, long
 // -- score as a sortable 32-bit key, accumulated log-probability -- in REGISTERS, and the top K are K rounds of
 // {wave arg-max of a 64-bit (score key, ~index) word, four wave winners through LDS}: larger score first, LOWER index on ties
 // (= tf.nn.top_k's order; -inf scores stay selectable, in index order).
-// History, measured at c4 (B * K = 640 rows, V = 31; tools/beam_gemm_dissect.sh): round 2 one thread selecting serially 165 us;
+// History, measured at c4 (B * K = 640 rows, V = 31; profiles/r04_beam_gemm_dissect.txt): round 2 one thread selecting serially 165 us;
 // round 3 one wave, candidates in LDS, parents' flags loaded inside every round 22 us; rank by counting (every candidate against
 // every other, broadcast LDS reads) 28 us -- 310 x 310 comparisons are more instructions than ten reductions.
 // NCT > 0: the output layer runs here too (seq2seq.py:339 the decoder's Dense(vocab) under BeamSearchDecoder): the utterance's K rows of
@@ -289,10 +289,6 @@ __global__ __launch_bounds__(256) void beam_step_kernel(float* logits, long logi
     }
   }
   __syncthreads();
-#if defined(BS_STOP) && BS_STOP <= 1
-  if (tid == 0) n_unfinished[0] = (int)lg_s[0];
-  return;
-#endif
   for (int k = wave; k < K; k += 4) {                 // max and exp-sum of beam k: wave reductions over its V logits
     float mx = -INFINITY;
     for (int v = lane; v < V; v += 64) mx = fmaxf(mx, lg_s[k * V + v]);
@@ -308,10 +304,6 @@ __global__ __launch_bounds__(256) void beam_step_kernel(float* logits, long logi
   if (tid < K) lse_s[tid] = mx_s[tid] + logf(sum_s[tid]);
   for (int j = tid - 64; j >= 0 && j < 2 * K; j += 192) pen[j] = powf((5.0f + (float)(len_s[j >> 1] + (j & 1))) / 6.0f, w);
   __syncthreads();
-#if defined(BS_STOP) && BS_STOP <= 2
-  if (tid == 0) n_unfinished[0] = (int)lse_s[0];
-  return;
-#endif
   // ---- this thread's candidates i = tid + 256 c: key (0 = none / taken) and accumulated log-probability, in registers ----
   constexpr int NC = 4;                               // K * V <= 1024
   unsigned key[NC];
@@ -331,10 +323,6 @@ __global__ __launch_bounds__(256) void beam_step_kernel(float* logits, long logi
       tot[c] = t;
     }
   }
-#if defined(BS_STOP) && BS_STOP <= 3
-  if (tid == 0) n_unfinished[0] = (int)key[0];
-  return;
-#endif
   int alive = 0;
   for (int j = 0; j < K; ++j) {
     // this thread's best remaining candidate as one 64-bit word: (score key, ~index) -- larger is better, lower index wins ties

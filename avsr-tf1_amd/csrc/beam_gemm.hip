@@ -19,7 +19,6 @@
 #include "prof.h"
 #include "attn.h"
 #include "step.h"
-#include <cstdlib>
 
 namespace avsr {
 
@@ -48,7 +47,7 @@ struct BGLaunch { int nprob, ntiles; BGProb p[BG_MAX_PROB]; };
 #define BG_P (BG_K + 4)    // LDS row pitch in floats (16-byte aligned rows, 4 banks apart)
 
 // Code-generation notes (each visible in the ISA, each cost a whole serialised memory round trip per stage until fixed;
-// tools/beam_gemm_dissect.sh):  (1) the problem descriptor is read through CONSTANT indices into the by-value kernel argument (PF below):
+// profiles/r04_beam_gemm_dissect.txt):  (1) the problem descriptor is read through CONSTANT indices into the by-value kernel argument (PF below):
 // `L.p[pi]` with a run-time pi makes the compiler copy the argument into scratch memory and turn every field access into a scratch load;
 // (2) no local array is indexed by the stage's source -- such an array lives in scratch too; (3) no arithmetic on a loaded operand
 // before it is committed to LDS, else the compiler waits for the load right behind its issue.
@@ -97,13 +96,9 @@ __global__ __launch_bounds__(512) void beam_gemm_kernel(const BGLaunch L) {
 
   f32x4 ra0, ra1, ra2, ra3, rb0, rb1, rb2, rb3;
   // operand fetch of stage ST into ra0 / ra1 / rb0 / rb1
-#ifdef BG_NO_LOAD      // dissection build (tools/beam_gemm_dissect.sh): everything but the operand fetch
-#define BG_LOAD1(ra, rb, rs, in, ao, wo, kl, kw) ra = f32x4{(float)(kl), 1.f, 2.f, (float)(ao)}; rb = f32x4{(float)(kw), 1.f, 2.f, (float)(wo)};
-#else
 #define BG_LOAD1(ra, rb, rs, in, ao, wo, kl, kw)                                                                  \
     ra = ldb4(rs, ((in) && (ao) != P_OOB) ? (ao) + (kl) * 4 : P_OOB);                                             \
     rb = ldb4(wrs, ((in) && (wo) != P_OOB) ? (wo) + (kw) : P_OOB);
-#endif
 #define BG_FETCH(ST) {                                                                                             \
     const int st_ = (ST);                                                                                          \
     const int s_ = __builtin_amdgcn_readfirstlane(st_ >= sb2 ? 2 : (st_ >= sb1 ? 1 : 0));                          \
@@ -179,13 +174,7 @@ __global__ __launch_bounds__(512) void beam_gemm_kernel(const BGLaunch L) {
 #pragma unroll
     for (int j = 0; j < 8; ++j)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-#ifdef BG_NO_MFMA      // dissection build: everything but the matrix instructions
-        acc[(4 * j + e) & 15] += a4[j][e] * b4[j][e];
-#else
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[j][e], b4[j][e], acc, 0, 0, 0);
-#endif
-      }
+      for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[j][e], b4[j][e], acc, 0, 0, 0);
     if (st + 1 < nstage) {
       if (buf) BG_COMMIT(0) else BG_COMMIT(1)                 // the stage fetched while the previous one was multiplied
       if (st + 2 < nstage) BG_FETCH(st + 2)
@@ -299,12 +288,9 @@ __global__ __launch_bounds__(256) void beam_ctx_merge_kernel(const BCLaunch L) {
 }
 
 // ---- host side (called from avsr_attn_rnn_fwd, mode 3) --------------------------------------------------------------------------
-int g_beam_dense = -1;        // -1: read AVSR_BEAM_DENSE once (default on)
+int g_beam_dense = 1;         // avsr_attn_rnn_set_beam_kernel
 
-bool beam_dense_on() {
-  if (g_beam_dense < 0) { const char* e = getenv("AVSR_BEAM_DENSE"); g_beam_dense = e ? (atoi(e) != 0) : 1; }
-  return g_beam_dense != 0;
-}
+bool beam_dense_on() { return g_beam_dense != 0; }
 
 // the LSTM cell step of all B rows.  Returns AVSR_ERR_UNSUPPORTED where the tiled kernel does not apply (the caller then runs step_kernel).
 int beam_cell_launch(const avsr_attn_rnn& d, int l, hipStream_t s) {

@@ -53,6 +53,8 @@ __device__ __forceinline__ void stage_rows(const float* __restrict__ src, float*
 }
 
 #define CG_MAXTAP 16
+// workgroups of one forward / data-gradient launch: each writes one partial row of the statistics buffers, which hold 512 (avsr_hip.h)
+#define CONV_MAX_PARTS 512
 // One (wide) tap of the product's depth: source offset (da, db) from the row's base position; w[sp] = index of the kernel tap this
 // source pixel meets for sub-position sp of the row, or -1 (zero weights).
 struct CGTap { int da, db; short w[4]; };
@@ -83,7 +85,6 @@ struct CGArgs {
   int nsp, SB, OSA, OSB, lin;
   signed char sp_dh[4], sp_dw[4];
   int ntap, wmode, F;
-  int dbg;                                // CONV_DEBUG builds only: bit 0 no stores, bit 1 no LDS operand reads, bit 2 no MFMAs
   float beta;
   unsigned m_opf, m_ob, m_rq, m_per, m_sw;   // division magics: positions per frame, OB, pieces per source row / per frame (Cs % 4 == 0),
                                           // or channels / floats per frame / SW (otherwise)
@@ -107,7 +108,6 @@ struct WGArgs {
   int t0, nt, kw;                         // taps t0 .. t0+nt-1 of a kw x kw kernel: rows (t - t0, ci) of this launch's slab
   int slab, want_bias;                    // floats per workgroup partial: nt*Ci*Co (+ Co column sums of dy = the bias gradient)
   const float* bn_sc; const float* bn_sh; // BN-ReLU applied to x while staging (see CGArgs)
-  int dbg;                                // CONV_DEBUG builds: bit 3 = per-wave cycle stamps behind the partial slabs
   // FOLD (round 5): dy is not stored -- it is the batch-norm backward's output gamma*invstd*(dz - mean(dz) - xhat*mean(dz*xhat)) =
   // k1[c]*dz + k2[c]*y + k3[c] of the convolution's OWN output y (avsr_bn_bwd_finalize's coefficient vectors fk [3*fC]), evaluated while
   // the operand is fetched: `dy` points at dz, fy at y (same layout).  For a convolution whose only gradient consumer is this kernel

@@ -32,9 +32,6 @@ namespace avsr {
 template <int MAXCH, bool CH4, int EP>
 __global__ __launch_bounds__(256, 2) void conv_gen_kernel(const CGArgs A) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
-#ifdef CONV_DEBUG
-  const long t_k0 = __builtin_readcyclecounter();
-#endif
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int i = lane & 15, q = lane >> 4;
   const int Cs = A.Cs, CsL = A.CsL, CsP = A.CsP, Cd = A.Cd, C4 = CsL >> 2;
@@ -59,9 +56,6 @@ __global__ __launch_bounds__(256, 2) void conv_gen_kernel(const CGArgs A) {
   // zero the LDS once: halos (and the padded 4th channel of a 3-channel source) stay zero, frames overwrite the interior
   for (int idx = tid; idx < A.F * fstride; idx += 256) lds[idx] = 0.f;
   if (tid < CG_MAXTAP * 4) taptab[tid] = tapword;
-#ifdef CONV_DEBUG
-  const long t_s1 = __builtin_readcyclecounter();
-#endif
   // tile tables (rows beyond the staged frames read the window of row 0 and are never written out)
   for (int m = tid; m < rows_pad; m += 256) {
     int ro = 0, dt = 4;
@@ -78,9 +72,6 @@ __global__ __launch_bounds__(256, 2) void conv_gen_kernel(const CGArgs A) {
   }
 
   __syncthreads();                                      // (tap table visible)
-#ifdef CONV_DEBUG
-  const long t_s2 = __builtin_readcyclecounter();
-#endif
   // weight fragments of this wave's column tile (A operand: row i of the fragment = column nt*16 + i of the product) + per-chunk LDS
   // offsets of this lane's k-quad
   const __amdgpu_buffer_rsrc_t w_rs = make_rsrc(A.w);
@@ -110,9 +101,6 @@ __global__ __launch_bounds__(256, 2) void conv_gen_kernel(const CGArgs A) {
       wreg[c] = wv;
     }
   }
-#ifdef CONV_DEBUG
-  const long t_s3 = __builtin_readcyclecounter();
-#endif
   // result columns of this lane: cD0 .. cD0 + 3 = four consecutive channels of sub-position spD
   const int cD0 = nt * 16 + q * 4;
   const bool colok = cD0 < NC;
@@ -223,23 +211,12 @@ __global__ __launch_bounds__(256, 2) void conv_gen_kernel(const CGArgs A) {
     }
   };
   int n0 = n_begin;
-#ifdef CONV_DEBUG
-  long t_pro = 0, t_b1 = 0, t_commit = 0, t_b2 = 0, t_comp = 0, t_mark = __builtin_readcyclecounter();
-  const long t_start = t_mark;
-#define CG_STAMP(acc) { const long t_now = __builtin_readcyclecounter(); acc += t_now - t_mark; t_mark = t_now; }
-#else
-#define CG_STAMP(acc)
-#endif
   if (n0 < n_end) fetch(n0);
-  CG_STAMP(t_pro)
   for (; n0 < n_end; n0 += n_step) {
     const int fcur = min(FP, n_end - n0);
     __syncthreads();                                    // previous pass has finished reading the LDS (first pass: tables written)
-    CG_STAMP(t_b1)
     commit(n0);
-    CG_STAMP(t_commit)
     __syncthreads();
-    CG_STAMP(t_b2)
     if (n0 + n_step < n_end) fetch(n0 + n_step);      // in flight during the MFMAs below
     // ---- implicit GEMM over the staged frames ----
     const int Mtot = fcur * opf, mtiles = (Mtot + 15) >> 4;
@@ -273,9 +250,6 @@ __global__ __launch_bounds__(256, 2) void conv_gen_kernel(const CGArgs A) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = fmaf(ev[r], esc4[r], esh4[r]) > 0.f ? v[r] : 0.f;
       }
-#ifdef CONV_DEBUG
-      if (!(A.dbg & 1))
-#endif
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_, v), dst_rs, dbo, 0, 0);
       // statistics are accumulated unconditionally (a few operations); only their final write is conditional
       const f32x4 vs = ok ? v : zero4;
@@ -350,9 +324,6 @@ __global__ __launch_bounds__(256, 2) void conv_gen_kernel(const CGArgs A) {
       auto work = [&](const int k) {
         if (k == 0) { rb_nn = rowtab[t2 * 16 + i]; dt_nxt = dsttab[t1 * 16 + i]; }
         else if (k < W_DEST) {                          // the NEXT tile's operands (this tile's arrived during the previous one)
-#ifdef CONV_DEBUG
-          if (!(A.dbg & 2))
-#endif
           nxt[k - W_RD] = ld4(lds + rb_nxt + koff[k - W_RD]);
         } else if (k == W_DEST) {
           dbo = dest(mt, dt_cur, ok);
@@ -381,9 +352,6 @@ __global__ __launch_bounds__(256, 2) void conv_gen_kernel(const CGArgs A) {
             for (int r = 0; r < 4; ++r) v[r] = fmaf(pev[r], esc4[r], esh4[r]) > 0.f ? v[r] : 0.f;
           }
         } else if (k == W_EPI + 6) {
-#ifdef CONV_DEBUG
-          if (!(A.dbg & 1))
-#endif
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_, v), dst_rs, pdbo, 0, 0);
         } else if (k == W_EPI + 7) { vs = poki != 0 ? v : zero4; ssum += vs; }
         else if (k == W_EPI + 8) ssq += ((EP & 1) && bnb) ? vs * pev : vs * vs;
@@ -391,14 +359,8 @@ __global__ __launch_bounds__(256, 2) void conv_gen_kernel(const CGArgs A) {
 #pragma unroll
       for (int k = 0; k < NM; ++k) {
         const int c = k >> 2, e = k & 3;
-#ifdef CONV_DEBUG
-        if (!(A.dbg & 4)) {
-#endif
         if (e & 1) acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[c][e], cur[c][e], acc1, 0, 0, 0);
         else acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[c][e], cur[c][e], acc0, 0, 0, 0);
-#ifdef CONV_DEBUG
-        }
-#endif
         if (k < NWORK) work(k);
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -417,17 +379,7 @@ __global__ __launch_bounds__(256, 2) void conv_gen_kernel(const CGArgs A) {
     } else {
       for (int mt = mslot; mt < mtiles; mt += mstep) tile(bufa, bufb, mt);
     }
-    CG_STAMP(t_comp)
   }
-#ifdef CONV_DEBUG
-  if ((A.dbg & 8) && A.stats && lane == 0) {           // per-wave cycle counts behind the statistics partials (probe allocates them)
-    float* o = A.stats + (long)gridDim.x * 2 * Cd + ((long)blockIdx.x * 4 + wave) * 8;
-    o[0] = (float)t_pro; o[1] = (float)t_b1; o[2] = (float)t_commit; o[3] = (float)t_b2; o[4] = (float)t_comp;
-    o[5] = (float)(__builtin_readcyclecounter() - t_start);
-    o[6] = (float)(t_start - t_k0);                      // set-up: LDS zeroing, tile tables, weight fragments
-    if (A.dbg & 16) { o[0] = (float)(t_s1 - t_k0); o[1] = (float)(t_s2 - t_s1); o[2] = (float)(t_s3 - t_s2); o[3] = (float)(t_start - t_s3); }   // set-up split
-  }
-#endif
   if (A.stats) {
     // per-channel partials of this workgroup: sum over the 16 positions of a lane group first (lanes q*16 .. q*16+15 hold the same
     // four channels), then over the (wave, q, r) slots that carry the channel
@@ -612,23 +564,12 @@ __global__ __launch_bounds__(256, 2) void conv_q4_kernel(const CGArgs A) {
     }
   };
   int n0 = n_begin;
-#ifdef CONV_DEBUG
-  long t_pro = 0, t_b1 = 0, t_commit = 0, t_b2 = 0, t_comp = 0, t_mark = __builtin_readcyclecounter();
-  const long t_start = t_mark;
-#define CG_STAMP(acc) { const long t_now = __builtin_readcyclecounter(); acc += t_now - t_mark; t_mark = t_now; }
-#else
-#define CG_STAMP(acc)
-#endif
   if (n0 < n_end) fetch(n0);
-  CG_STAMP(t_pro)
   for (; n0 < n_end; n0 += n_step) {
     const int fcur = min(FP, n_end - n0);
     __syncthreads();                                    // previous pass has finished reading the LDS (first pass: tables written)
-    CG_STAMP(t_b1)
     commit(n0);
-    CG_STAMP(t_commit)
     __syncthreads();
-    CG_STAMP(t_b2)
     if (n0 + n_step < n_end) fetch(n0 + n_step);      // in flight during the MFMAs below
     // ---- the staged frames' positions, 64 per wave tile ----
     const int Mtot = fcur * opf, mtiles = (Mtot + 63) >> 6;
@@ -700,18 +641,10 @@ __global__ __launch_bounds__(256, 2) void conv_q4_kernel(const CGArgs A) {
       ssq0 += ((EP & 1) && bnb) ? s0 * ev0 : s0 * s0;
       ssq1 += ((EP & 1) && bnb) ? s1 * ev1 : s1 * s1;
     }
-    CG_STAMP(t_comp)
   }
 #undef Q4C_LD
 #undef Q4C_MFMA
 #undef Q4C_E
-#ifdef CONV_DEBUG
-  if ((A.dbg & 8) && A.stats && lane == 0) {           // per-wave cycle counts behind the statistics partials (tools/conv_dissect.py)
-    float* o = A.stats + (long)gridDim.x * 2 * Cd + ((long)blockIdx.x * 4 + wave) * 8;
-    o[0] = (float)t_pro; o[1] = (float)t_b1; o[2] = (float)t_commit; o[3] = (float)t_b2; o[4] = (float)t_comp;
-    o[5] = (float)(__builtin_readcyclecounter() - t_start);
-  }
-#endif
   if (A.stats) {
     // per-channel partials of this workgroup: every lane holds all 8 channels of its positions
     __syncthreads();
@@ -727,7 +660,6 @@ __global__ __launch_bounds__(256, 2) void conv_q4_kernel(const CGArgs A) {
 }
 
 int g_conv_mfma = 1;
-static const int g_conv_pad = [] { const char* e = getenv("AVSR_CONV_PAD"); return e ? atoi(e) : 1; }();   // A/B switch of the padded LDS pixel stride
 
 }  // namespace avsr
 
@@ -735,10 +667,8 @@ using namespace avsr;
 
 extern "C" int avsr_conv_set_mfma(int32_t on) { g_conv_mfma = on ? 1 : 0; return AVSR_OK; }
 
-static int g_conv_q4 = -1;
 static bool cg_q4_ok(const CGArgs& A, int ntaps) {
-  if (g_conv_q4 < 0) { const char* e = getenv("AVSR_CONV_Q4"); g_conv_q4 = e ? (atoi(e) != 0) : 1; }
-  return g_conv_q4 && A.Cd == 8 && A.S == 1 && A.OS == 1 && !A.oh0 && !A.ow0 && A.DH == A.OA && A.DW == A.OB && ntaps == 9 &&
+  return A.Cd == 8 && A.S == 1 && A.OS == 1 && !A.oh0 && !A.ow0 && A.DH == A.OA && A.DW == A.OB && ntaps == 9 &&
          (A.Cs == 8 || A.Cs == 3) && A.SW + 1 < 256;
 }
 // the kernel derives a tap's column from its index: db = t % 3 - 1 (forward) or 1 - t % 3 (flipped, A.wmode)
@@ -771,23 +701,18 @@ static int cg_launch_q4(CGArgs& A, hipStream_t s, int kind, double flops, bool d
   int bestF = 0;
   for (int F = (Fcap < 16 ? Fcap : 16); F >= 1; --F) {
     if (lds_bytes(F) > 64 * 1024 || (long)F * frame_b / 4 >= (1 << 14) * 4 || (long)F * opf >= (1 << 24)) continue;
-    const long units = (A.N + F - 1) / F, grid = units < 512 ? units : 512;
+    const long units = (A.N + F - 1) / F, grid = units < CONV_MAX_PARTS ? units : CONV_MAX_PARTS;
     const long cnt = (A.N + grid - 1) / grid, np = (cnt + F - 1) / F, fp = (cnt + np - 1) / np;
     const long tiles = (fp * opf + 63) / 64, per_wave = (tiles + 3) / 4;
     const double cost = (double)np * (double)(per_wave * 8 + 4);
     if (best < 0.0 || cost < 0.97 * best) { best = cost; bestF = F; }
   }
   if (!bestF) return AVSR_ERR_UNSUPPORTED;
-#ifdef CONV_DEBUG
-  { const char* e = getenv("AVSR_CONV_DBG"); A.dbg = e ? atoi(e) : 0; }
-#endif
   A.F = bestF;
   size_t lds = lds_bytes(A.F);
   if (lds < 256) lds = 256;
   int grid = (A.N + A.F - 1) / A.F;
-  static int cap = 0;
-  if (!cap) { const char* e = getenv("AVSR_CONV_Q4_CAP"); cap = e ? atoi(e) : 512; }     // statistics buffers hold 512 partial rows (avsr_hip.h)
-  if (grid > cap) grid = cap;
+  if (grid > CONV_MAX_PARTS) grid = CONV_MAX_PARTS;
   if (dry) return grid;
   ProfScope ps(kind, s, flops);
   const bool emap = A.res != nullptr || A.bnb_x != nullptr;
@@ -811,9 +736,6 @@ static int cg_launch(CGArgs& A, hipStream_t s, int kind, double flops, bool dry 
     A.nsp = 1; A.SB = A.S; A.OSA = A.OS; A.OSB = A.OS;
     A.lin = (A.OS == 1 && A.oh0 == 0 && A.ow0 == 0 && A.DH == A.OA && A.DW == A.OB) ? 1 : 0;
   }
-#ifdef CONV_DEBUG
-  { const char* e = getenv("AVSR_CONV_DBG"); A.dbg = e ? atoi(e) : 0; }
-#endif
   if (cg_q4_ok(A, A.ntap) && A.nsp == 1 && A.lin && cg_q4_taps_ok(A)) return cg_launch_q4(A, s, kind, flops, dry);
   const int KQ = A.ntap * (A.CsL / 4), nch = (KQ + 3) / 4;
   const int NT = (A.nsp * A.Cd + 15) / 16;
@@ -843,7 +765,7 @@ static int cg_launch(CGArgs& A, hipStream_t s, int kind, double flops, bool dry 
   // 8 (16) slots -- 4 (8) lanes per slot, and SQ_LDS_BANK_CONFLICT counted 68-84 % of the LDS-active cycles of the 16- / 32- / 64-channel
   // launches (profiles/r06_c4_lds_pmc_v1.txt).  A stride of 2 (mod 4) slots per position spreads every group over all 16 slots.
   A.CsP = A.CsL;
-  if (A.Cs % 4 == 0 && g_conv_pad) {
+  if (A.Cs % 4 == 0) {
     for (int p = 0; p < 4; ++p)
       if ((A.SB * (A.CsL / 4 + p)) % 4 == 2) { A.CsP = A.CsL + 4 * p; break; }
   }
@@ -869,17 +791,17 @@ static int cg_launch(CGArgs& A, hipStream_t s, int kind, double flops, bool dry 
     }
     return bestF;
   };
-  A.F = pick(64 * 1024, 512);                            // two 256-thread workgroups per CU
+  A.F = pick(64 * 1024, CONV_MAX_PARTS);                 // two 256-thread workgroups per CU
   if (!A.F && A.CsP != A.CsL) {                          // the padded frame does not fit (36 x 36 maps): unpadded
     A.CsP = A.CsL;
     frame_b = sizeof(float) * (size_t)(A.SH + 2) * (A.SW + 2) * A.CsP;
-    A.F = pick(64 * 1024, 512);
+    A.F = pick(64 * 1024, CONV_MAX_PARTS);
   }
   if (!A.F) return AVSR_ERR_UNSUPPORTED;
   size_t lds = lds_bytes(A.F);
   if (lds < sizeof(float) * 4 * 4 * 2 * 4) lds = sizeof(float) * 4 * 4 * 2 * 4;      // the statistics reduction's staging area
   int grid = (A.N + A.F - 1) / A.F;
-  if (grid > 512) grid = 512;
+  if (grid > CONV_MAX_PARTS) grid = CONV_MAX_PARTS;
   if (dry) return grid;
   ProfScope ps(kind, s, flops);
   const bool emap = A.res != nullptr || A.bnb_x != nullptr;

@@ -2,7 +2,6 @@
 // (rows = (tap, cin), columns = cout, depth = positions) with the frame staged in LDS and dy streamed; per-workgroup partial slabs, reduced
 // by the column-sum launches of elementwise.hip (deferred to the end of the CNN's backward pass: avsr_slab_defer_*).
 #include "conv_mfma.h"
-#include <cstdlib>
 
 namespace avsr {
 
@@ -142,27 +141,11 @@ __global__ __launch_bounds__(256, WG_WPC(MT * NTC)) void conv_wgrad_kernel(const
   const int cpf = (opf + 15) >> 4;                       // chunks per frame
   const unsigned m_cpf = fmagic_dev(cpf);
   int n0 = n_begin;
-  // dissection builds (tools/wgrad_ablate.sh: -DWG_ABLATE=mask, compile-time so that the rest of the code is generated as shipped):
-  // 1 no dy loads, 2 no LDS operand reads, 4 no MFMAs, 16 no frame staging.  Results: profiles/r05_wgrad_ablation.txt
-#ifdef WG_ABLATE
-#define WG_ABL(b) (((WG_ABLATE) & (b)) != 0)
-#else
-#define WG_ABL(b) false
-#endif
-#ifdef CONV_DEBUG
-  long w_b1 = 0, w_commit = 0, w_b2 = 0, w_comp = 0, w_mark = __builtin_readcyclecounter();
-  const long w_start = w_mark;
-#define WG_STAMP(acc) { const long t_now = __builtin_readcyclecounter(); acc += t_now - w_mark; w_mark = t_now; }
-#else
-#define WG_STAMP(acc)
-#endif
   if (n0 < n_end) fetch(n0);
   for (; n0 < n_end; n0 += n_step) {
     const int fcur = min(FP, n_end - n0);
     __syncthreads();
-    WG_STAMP(w_b1)
-    if (!WG_ABL(16)) commit(n0);
-    WG_STAMP(w_commit)
+    commit(n0);
     const int kch = fcur * cpf;
     const unsigned dyo = (unsigned)((long)n0 * opf * Co * 4);     // [fcur][opf][Co]
     float bn[NTC][4], byn[FOLD ? NTC : 1][4];
@@ -175,16 +158,15 @@ __global__ __launch_bounds__(256, WG_WPC(MT * NTC)) void conv_wgrad_kernel(const
 #pragma unroll
         for (int nt = 0; nt < NTC; ++nt) {
           const int off = (r0 + e < opf && nt * 16 + i < Co) ? (int)(o + (unsigned)((e * Co + nt * 16) * 4)) : P_OOB;
-          b[nt][e] = ldb1(dy_rs, WG_ABL(1) ? P_OOB : off);
-          if (FOLD) byn[nt][e] = ldb1(fy_rs, WG_ABL(1) ? P_OOB : off);
+          b[nt][e] = ldb1(dy_rs, off);
+          if (FOLD) byn[nt][e] = ldb1(fy_rs, off);
         }
     };
     constexpr int KC0 = RS ? 0 : -1, KCS = RS ? 1 : 4;                // first chunk / chunk step of a wave
     const int kc0 = KC0 < 0 ? wave : KC0;
     if (kc0 < kch) load_b(kc0, bn);
     __syncthreads();
-    WG_STAMP(w_b2)
-    if (n0 + n_step < n_end && !WG_ABL(16)) fetch(n0 + n_step);      // next pass's frames: in flight during the MFMAs
+    if (n0 + n_step < n_end) fetch(n0 + n_step);      // next pass's frames: in flight during the MFMAs
     for (int kc = kc0; kc < kch; kc += KCS) {
       float av[MT][4], bv[NTC][4];
       const int f = fdiv(kc, m_cpf), r0 = (kc - f * cpf) * 16 + q * 4;
@@ -210,7 +192,7 @@ __global__ __launch_bounds__(256, WG_WPC(MT * NTC)) void conv_wgrad_kernel(const
         // positions beyond the frame read a clamped (finite) LDS address: their dy operand is zero (out-of-range buffer load), so the
         // product vanishes without a select per operand
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) av[mt][e] = WG_ABL(2) ? (float)roff[mt] : xb[roff[mt]];
+        for (int mt = 0; mt < MT; ++mt) av[mt][e] = xb[roff[mt]];
         if (++wo == A.Wo) { wo = 0; ++ho; }
         if (ho >= A.Ho) { ho = A.Ho - 1; }                 // (only reached by out-of-range positions: masked above)
       }
@@ -221,20 +203,10 @@ __global__ __launch_bounds__(256, WG_WPC(MT * NTC)) void conv_wgrad_kernel(const
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
-          for (int nt = 0; nt < NTC; ++nt) {
-            if (WG_ABL(4)) acc[mt][nt][0] += av[mt][e] * bv[nt][e];
-            else acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt][e], bv[nt][e], acc[mt][nt], 0, 0, 0);
-          }
+          for (int nt = 0; nt < NTC; ++nt) acc[mt][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mt][e], bv[nt][e], acc[mt][nt], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
-    WG_STAMP(w_comp)
   }
-#ifdef CONV_DEBUG
-  if ((A.dbg & 8) && lane == 0) {
-    float* o = A.part + (long)gridDim.x * A.slab + ((long)blockIdx.x * 4 + wave) * 8;
-    o[0] = (float)w_b1; o[1] = (float)w_commit; o[2] = (float)w_b2; o[3] = (float)w_comp; o[4] = (float)(__builtin_readcyclecounter() - w_start);
-  }
-#endif
   // cross-wave reduction (waves hold different depth slices of the same tiles), tile by tile through a 4 KB staging area, then
   // one partial per workgroup
   float* red = lds;                                     // [4][16][16]
@@ -344,13 +316,10 @@ int avsr_conv3x3_bwd_weight_mfma(const float* x, const float* dy, float* dw, int
 
 // Workgroups per CU and LDS pixel padding of a weight-gradient launch whose passes hold ONE frame: up to WG_WPC(tiles) workgroups where
 // the frames fit the CU's 160 KB side by side -- with + 1 float of padding instead of + 2 where that is what makes the next one fit
-// (36x36x8: 3 x 52 KB; the odd pixel stride costs 4-byte staging stores and measured nothing on the operand reads).  AVSR_WG_WPC caps it.
+// (36x36x8: 3 x 52 KB; the odd pixel stride costs 4-byte staging stores and measured nothing on the operand reads).
 static int wg_occupancy(int tiles, int H, int W, int CiL, int* pad) {
-  static int cap_env = -1;
-  if (cap_env < 0) { const char* e = getenv("AVSR_WG_WPC"); cap_env = e ? atoi(e) : 4; }
   *pad = WG_PAD;
-  int cap = WG_WPC(tiles);
-  if (cap > cap_env) cap = cap_env;
+  const int cap = WG_WPC(tiles);
   auto frame = [&](int p) { return sizeof(float) * (size_t)(H + 2) * (W + 2) * (CiL + p); };
   if (2 * frame(WG_PAD) <= 64 * 1024) return 2;                       // several frames per pass: as before
   for (int w = cap; w > 2; --w) {
@@ -430,15 +399,12 @@ int conv_bwd_weight_impl(const avsr_conv_desc* c, const float* x, const float* d
   // channel), the depth index a PAIR of horizontally adjacent output pixels; the rows run over the union of the two pixels' windows
   // (3 x 4 taps, source step 2 along W): C[(ti, tj', ci)][(pp, co)] is the gradient of tap (ti, tj' - pp) where that is a tap at all.
   // 6 row tiles per pair instead of 2 x 5 per two positions; the reduction kernel above adds the two parities' valid entries.
-  if (Co == 8 && c->stride == 1 && k == 3 && (Wo & 1) == 0 && Wo == W && Ho == H && !getenv("AVSR_WGRAD_NOPAIR")) {
+  if (Co == 8 && c->stride == 1 && k == 3 && (Wo & 1) == 0 && Wo == W && Ho == H) {
     WGArgs A = {};
     A.x = x; A.dy = dy; A.part = scratch; A.N = N; A.H = H; A.W = W; A.Ci = Ci; A.CiL = (Ci + 3) & ~3; A.Ho = Ho; A.Wo = Wo / 2; A.Co = 16;
     A.S = 1; A.SW = 2; A.pt = c->pad_t; A.pl = c->pad_l; A.kw = 4; A.bn_sc = c->bn_scale; A.bn_sh = c->bn_shift;
     A.t0 = 0; A.nt = 12; A.want_bias = dbias ? 1 : 0;
     A.fy = fold_y; A.fk = fold_k; A.fC = 8; A.fdx = fold_dx;
-#ifdef CONV_DEBUG
-    { const char* e = getenv("AVSR_CONV_DBG"); A.dbg = e ? atoi(e) : 0; }
-#endif
     A.slab = 12 * Ci * 16 + (A.want_bias ? 16 : 0);
     const int MT = (12 * A.CiL + 15) / 16;
     bool ok = (Ci % 4 == 0) ? MT <= 6 : (MT <= 3 && !c->bn_scale);
@@ -534,10 +500,8 @@ int conv_bwd_weight_impl(const avsr_conv_desc* c, const float* x, const float* d
   hipStream_t s = S_(stream);
   bool bias_done = dbias == nullptr;
   // deep layers (64 destination channels, more (tap, channel) rows than one wave's accumulators hold): the row-split form, one launch
-  static int rs_on = -1;
-  if (rs_on < 0) { const char* e = getenv("AVSR_WGRAD_RS"); rs_on = e ? (atoi(e) != 0) : 1; }
   const int Mall = k * k * A.CiL;
-  const bool rs = rs_on && NTC == 4 && Ci % 4 == 0 && G < k * k && Mall <= 4 * 9 * 16;   // (32-column layers fit one launch already: no gain measured)
+  const bool rs = NTC == 4 && Ci % 4 == 0 && G < k * k && Mall <= 4 * 9 * 16;   // (32-column layers fit one launch already: no gain measured)
   if (rs) G = k * k;
   if (fold) {
     // one launch only (a second tap group would evaluate -- and write -- the gradient again), and only the forms instantiated below

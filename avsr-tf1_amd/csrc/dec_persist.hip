@@ -800,8 +800,6 @@ static const void* dp_kernel(int variant, int mode, bool v64 = false) {
 #undef DPK64
 }
 
-static int g_dec_rows16 = -1;                   // -1: read AVSR_DEC_ROWS16 once (default on)
-
 // Fills L for the descriptor; returns AVSR_ERR_UNSUPPORTED when the fused kernel does not cover it.
 int dp_plan(const avsr_attn_rnn& d, DPLaunch& L, int* variant, size_t* lds_bytes) {
   if (!g_dec_fused || !g_sync || !d.fused_ws) return AVSR_ERR_UNSUPPORTED;
@@ -824,9 +822,8 @@ int dp_plan(const avsr_attn_rnn& d, DPLaunch& L, int* variant, size_t* lds_bytes
   L.B = B; L.L = d.L; L.H = H; L.E = E; L.V = d.V; L.n_mech = d.n_mech; L.mode = d.mode; L.oa = d.output_attention;
   L.go_id = d.go_id; L.eos_id = d.eos_id; L.A = A; L.KW = KW; L.UW = UW; L.AW = AW; L.NWA = (A + AW - 1) / AW; L.uwsh = uwsh; L.awsh = awsh;
   // 16-row groups (full MFMA row tiles, half as many groups): the attentive layer with ONE memory whose halves fit a workgroup
-  if (g_dec_rows16 < 0) { const char* e = getenv("AVSR_DEC_ROWS16"); g_dec_rows16 = (e && e[0] == '0') ? 0 : 1; }
   L.R = DP_R;
-  if (g_dec_rows16 && d.mode == 0 && d.n_mech == 1 && (d.mech[0].T + 1) / 2 <= 64 && UW * 16 <= DP_NT && AW * 16 <= DP_NT) L.R = 16;
+  if (d.mode == 0 && d.n_mech == 1 && (d.mech[0].T + 1) / 2 <= 64 && UW * 16 <= DP_NT && AW * 16 <= DP_NT) L.R = 16;
   const int wpr = DP_NW / L.R;
   L.drop = (d.seed && d.mode != 1 && (d.keep_in < 1.f || d.keep_state < 1.f || d.keep_out < 1.f)) ? 1 : 0;
   L.wt = d.wt; L.bias = d.bias; L.gates = d.gates; L.cs = d.cs; L.cell_out = d.cell_out; L.att = d.att; L.attd = d.attd;
@@ -870,6 +867,12 @@ int dp_plan(const avsr_attn_rnn& d, DPLaunch& L, int* variant, size_t* lds_bytes
   return AVSR_OK;
 }
 
+// sync words of one fused forward launch: header, per-XCD slot claims, flags
+static constexpr long DP_SYNC_WORDS = P_HDR + 8 + 8 * 4 * 32;
+
+// the run-time conditions the fused forward declines on besides the plan (dp_plan)
+static bool dp_fwd_enabled() { return g_dec_fused != 0 && g_dec_fused != 3 && g_sync && DP_SYNC_WORDS <= g_sync_ints; }
+
 }  // namespace avsr
 
 int64_t avsr_dec_persist_bwd_ws_floats(int32_t B, int32_t n_mech);
@@ -898,9 +901,7 @@ extern "C" int avsr_attn_rnn_fused_eligible(const avsr_attn_rnn* d) {
 // the SAME run-time conditions avsr_dec_persist_fwd declines on, on top of the plan: a caller that sizes its host checks by the answer
 // (greedy decode runs all steps as ONE call when it is 1) must not be told "fused" and then get one launch per step and phase
 extern "C" int avsr_attn_rnn_fused_fwd_active(const avsr_attn_rnn* d) {
-  using namespace avsr;
-  if (g_dec_fused == 3 || g_dec_fused == 0 || !g_sync) return 0;
-  if ((long)(P_HDR + 8 + 8 * 4 * 32) > g_sync_ints) return 0;
+  if (!avsr::dp_fwd_enabled()) return 0;
   return avsr_attn_rnn_fused_eligible(d);
 }
 
@@ -910,14 +911,13 @@ int avsr_dec_persist_fwd(const avsr_attn_rnn* dp, int32_t l_begin, int32_t l_end
   using namespace avsr;
   static thread_local DPLaunch L;
   int variant = 0; size_t lds = 0;
-  if (g_dec_fused == 3) return AVSR_ERR_UNSUPPORTED;
+  if (!dp_fwd_enabled()) return AVSR_ERR_UNSUPPORTED;
   const int rc = dp_plan(*dp, L, &variant, &lds);
   if (rc) return rc;
   if (l_begin >= l_end) return AVSR_OK;
   hipStream_t s = (hipStream_t)stream;
   int32_t* sync = g_sync;
-  const long words = P_HDR + 8 + 8 * 4 * 32;
-  if (words > g_sync_ints) return AVSR_ERR_UNSUPPORTED;
+  const long words = DP_SYNC_WORDS;
   static bool attr_set = false;
   if (!attr_set) {
     for (int v = 0; v < 5; ++v)

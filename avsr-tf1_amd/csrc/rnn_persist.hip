@@ -20,8 +20,6 @@
 #include "avsr_hip.h"
 #include "prof.h"
 #include "persist.h"
-#include <cstring>
-#include <cstdlib>
 
 #define P_MAX_TASKS 8
 #define P_MAXC 8
@@ -438,9 +436,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     for (int spins = 0; spins < (1 << 21); ++spins) {
       const int v = poll_ptr ? __hip_atomic_load(poll_ptr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0x7fffffff;
       if (__all(v >= need)) return;
-#ifdef POLL_SLEEP
-      __builtin_amdgcn_s_sleep(POLL_SLEEP);
-#endif
       if ((spins & 1023) == 1023 && __hip_atomic_load(L.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
     }
     if (lane == 0) __hip_atomic_store(L.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -650,7 +645,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 }
 
 int32_t* g_sync = nullptr;
-int g_persist_mode = 3;      // bit 0: agent-scope forward, bit 1: XCD-local forward + fused BPTT, bit 2: split BPTT (opt-in)
+int g_persist_mode = 3;      // bit 0: agent-scope forward, bit 1: XCD-local forward + persistent BPTT, bit 2: K-split BPTT off
 
 int64_t g_sync_ints = 0;
 
@@ -706,13 +701,7 @@ static int build_tasks(const avsr_rnn_stack* st, int n, bool local, int32_t* syn
       tk.B = S.B; tk.T = S.T; tk.H = H; tk.in = in; tk.hoisted = Ly.hoisted; tk.reverse = S.reverse;
       g_fwd_flops += 2.0 * S.B * S.T * ((Ly.hoisted ? 0 : in) + H) * 4.0 * H;
       tk.uw = (local && Ly.hoisted && H % 16 == 0) ? 16 : 8;
-      {
-        // wave priority of the task's workgroups: the cells with an input product set the pace (default 2, recurrent-only layer 0: 0);
-        // AVSR_RNN_PRIO="p0,p1,..." (by task index) overrides for experiments
-        tk.prio = Ly.hoisted ? 0 : 2;
-        static const char* pe = getenv("AVSR_RNN_PRIO");
-        if (pe) { const char* q = pe; for (int k = 0; k < L.ntask - 1 && q; ++k) { q = strchr(q, ','); if (q) ++q; } if (q && *q >= '0' && *q <= '3') tk.prio = *q - '0'; }
-      }
+      tk.prio = Ly.hoisted ? 0 : 2;     // wave priority: the cells with an input product set the pace (recurrent-only layer 0: 0)
       tk.nct = H / tk.uw; tk.nrt = nrt; tk.wg_begin = wg; tk.part = parts ? i : 0;
       if (tk.nct > 32) return AVSR_ERR_UNSUPPORTED;
       wg += local ? tk.nct : nrt * tk.nct;
@@ -755,14 +744,12 @@ int avsr_rnn_fwd_persistent(const avsr_rnn_stack* st, int32_t n, void* stream, i
   static thread_local PLaunch L;
   hipStream_t s = (hipStream_t)stream;
   int wg = 0; long words = 0;
-  static const int parts_first = getenv("AVSR_RNN_PARTS") ? atoi(getenv("AVSR_RNN_PARTS")) == 2 : 0;   // experiment: two stacks side by side even when they fit together
-  if ((g_persist_mode & 2) && !(parts_first && n == 2 && st[0].B <= 64) && build_tasks(st, n, true, sync, sync_ints, L, &wg, &words) == AVSR_OK) {
+  if ((g_persist_mode & 2) && build_tasks(st, n, true, sync, sync_ints, L, &wg, &words) == AVSR_OK) {
     if (dry) return AVSR_OK;
     // 8 XCDs x R rows per launch (R = 8 up to 64 utterances, 16 above); a larger batch runs as consecutive launches over slices
     // (rows are independent)
     const int B = st[0].B;
-    static const int rows16 = getenv("AVSR_RNN_ROWS16") ? atoi(getenv("AVSR_RNN_ROWS16")) : 1;
-    const int R = (B > 64 && rows16) ? 16 : 8;
+    const int R = B > 64 ? 16 : 8;
     for (int b0 = 0; b0 < B; b0 += 8 * R) {
       const int rows = B - b0 < 8 * R ? B - b0 : 8 * R;
       L.b0 = b0; L.ngroups = (rows + R - 1) / R;
@@ -770,8 +757,7 @@ int avsr_rnn_fwd_persistent(const avsr_rnn_stack* st, int32_t n, void* stream, i
       {
         ProfScope ps(PROF_RNN_PERSIST_FWD, s, g_fwd_flops * rows / B);
         // 8-row groups at H = 256 everywhere: recurrent product on the 4x4x1 MFMA with A-block broadcast (no padding rows)
-        static const int q4_on = getenv("AVSR_RNN_Q4") ? atoi(getenv("AVSR_RNN_Q4")) : 1;
-        bool q4 = q4_on && R == 8;
+        bool q4 = R == 8;
         for (int i = 0; i < L.ntask && q4; ++i) q4 = L.task[i].H == 256 && (L.task[i].hoisted ? L.task[i].uw == 16 : (L.task[i].uw == 8 && L.task[i].in == 256));
         if (R == 16) hipLaunchKernelGGL(rnn_persist_fwd_xcd_kernel<16>, dim3(8 * wg), dim3(256), 0, s, L);
         else if (q4) hipLaunchKernelGGL((rnn_persist_fwd_xcd_kernel<8, true>), dim3(8 * wg), dim3(256), 0, s, L);
@@ -783,8 +769,7 @@ int avsr_rnn_fwd_persistent(const avsr_rnn_stack* st, int32_t n, void* stream, i
   }
   // two stacks that do not fit one XCD together (the directions of a bidirectional encoder), <= 64 utterances: one launch, each
   // stack on four XCDs in 16-row groups -- the directions run side by side instead of one after the other
-  static const int parts_on = getenv("AVSR_RNN_PARTS") ? atoi(getenv("AVSR_RNN_PARTS")) : 1;
-  if ((g_persist_mode & 2) && parts_on && build_tasks(st, n, true, sync, sync_ints, L, &wg, &words, true) == AVSR_OK) {
+  if ((g_persist_mode & 2) && build_tasks(st, n, true, sync, sync_ints, L, &wg, &words, true) == AVSR_OK) {
     if (dry) return AVSR_OK;
     const int B = st[0].B;
     L.b0 = 0; L.ngroups = (B + 15) / 16;

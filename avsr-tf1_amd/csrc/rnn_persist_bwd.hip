@@ -161,9 +161,6 @@ __global__ __launch_bounds__(512) void rnn_persist_bwd_kernel(const BLaunch L) {
     for (int spins = 0; spins < (1 << 21); ++spins) {
       const int v = p ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0x7fffffff;
       if (__all(v >= need)) return;
-#ifdef POLL_SLEEP
-      __builtin_amdgcn_s_sleep(POLL_SLEEP);
-#endif
       if ((spins & 1023) == 1023 && __hip_atomic_load(L.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
     }
     if (lane == 0) __hip_atomic_store(L.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -332,14 +329,11 @@ __device__ __forceinline__ float ldb1_sc1(__amdgpu_buffer_rsrc_t r, int byte_off
   return __builtin_bit_cast(float, (unsigned)__builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, 16));
 }
 
-// NW: waves per workgroup.  8 = 512 threads owning 16 units (two workgroups per CU).  16 (round 5) = 1024 threads owning 32 units, one
-// workgroup per CU: a cell then has HALF as many producers -- half the partial-slab bytes through the XCD's L2 per step and half the
-// partial loads per consumer -- with the same matrix work and registers per wave (one 16-column tile of the partial d h with K = 128
-// instead of two with K = 64).  tools/handoff_probe.hip: the bare exchange of this kernel's pattern costs 1.73 us per step with 16
-// producers of 512 threads and 1.22 us with 8 of 1024.
-template <int NW>
-__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(4, 4))) void rnn_persist_bwdk_kernel(const BLaunch L) {
-  constexpr int UW = 2 * NW, UWSH = NW == 8 ? 4 : 5;       // units per workgroup
+// 8 waves per workgroup: 512 threads owning 16 units (two workgroups per CU).  (A 1024-thread form owning 32 units measured slower in
+// round 5: profiles/r05_experiments.txt.)
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 4))) void rnn_persist_bwdk_kernel(const BLaunch L) {
+  constexpr int NW = 8;                                     // waves per workgroup
+  constexpr int UW = 2 * NW, UWSH = 4;                      // units per workgroup
   constexpr int TPW = 16 / NW;                              // 16-column tiles of the partial d h per wave (H <= 256)
   constexpr int KC = UW / 4;                                // 16-deep chunks of the workgroup's own gate columns
   __shared__ __attribute__((aligned(16))) float red[NW][16][16];
@@ -659,29 +653,20 @@ static_assert(sizeof(BLaunch) <= 4000, "launch descriptor must fit the kernel-ar
 #include <cstdlib>
 // AVSR_PERSIST_DEBUG=1 prints which precondition sent a call back to the per-step launches
 #define UNSUP(code) do { if (getenv("AVSR_PERSIST_DEBUG")) fprintf(stderr, "[avsr] persistent BPTT not used: reason %d (rnn_persist_bwd.hip)\n", code); return AVSR_ERR_UNSUPPORTED; } while (0)
-static int bwd_persistent(const avsr_rnn_stack* st, int32_t n, void* stream, int dry, bool ksplit, bool wide);
+static int bwd_persistent(const avsr_rnn_stack* st, int32_t n, void* stream, int dry, bool ksplit);
 
 int avsr_rnn_bwd_persistent(const avsr_rnn_stack* st, int32_t n, void* stream, int dry) {
-  // the K-split kernel first: 16-unit workgroups of 512 threads; configurations it declines take the kernel above.  AVSR_RNN_BWD_WIDE=1
-  // selects the 32-unit / 1024-thread form where every layer allows and the tasks fit: built in round 5 on the strength of
-  // tools/handoff_probe.hip (the bare exchange 1.73 -> 1.22 us per step), same results (232 parity tests), and measured SLOWER in the
-  // real kernel -- c4 4.28 -> 4.77 us per sequential step, c2 4.52 -> 4.67, c5 4.62 -> 4.79 (profiles/r05_experiments.txt): with one
-  // 16-wave workgroup per CU every in-step barrier waits for sixteen waves and nothing else runs on the CU meanwhile.  Off by default.
-  static const int ksplit = getenv("AVSR_RNN_BWD_KSPLIT") ? atoi(getenv("AVSR_RNN_BWD_KSPLIT")) : 1;
-  static const int wide = getenv("AVSR_RNN_BWD_WIDE") ? atoi(getenv("AVSR_RNN_BWD_WIDE")) : 0;
-  if (ksplit && wide) {
-    const int rc = bwd_persistent(st, n, stream, dry, true, true);
+  // the K-split kernel first (16-unit workgroups of 512 threads) unless mode bit 2 turns it off; configurations it declines take the
+  // unit-partitioned kernel above
+  if (!(avsr::g_persist_mode & 4)) {
+    const int rc = bwd_persistent(st, n, stream, dry, true);
     if (rc != AVSR_ERR_UNSUPPORTED) return rc;
   }
-  if (ksplit) {
-    const int rc = bwd_persistent(st, n, stream, dry, true, false);
-    if (rc != AVSR_ERR_UNSUPPORTED) return rc;
-  }
-  return bwd_persistent(st, n, stream, dry, false, false);
+  return bwd_persistent(st, n, stream, dry, false);
 }
 
-static int bwd_persistent(const avsr_rnn_stack* st, int32_t n, void* stream, int dry, bool ksplit, bool wide) {
-  const int UWH = wide ? 32 : 16;                    // units per workgroup of the K-split kernel
+static int bwd_persistent(const avsr_rnn_stack* st, int32_t n, void* stream, int dry, bool ksplit) {
+  const int UWH = 16;                                // units per workgroup of the K-split kernel
   using namespace avsr;
   int32_t* sync = g_sync; const int64_t sync_ints = g_sync_ints;
   if (!sync || !(g_persist_mode & 2)) return AVSR_ERR_UNSUPPORTED;
@@ -714,7 +699,6 @@ static int bwd_persistent(const avsr_rnn_stack* st, int32_t n, void* stream, int
       if (top) { tk.dh_final = S.dh_final; tk.dc_final = S.dc_final; }
       tk.B = S.B; tk.T = S.T; tk.H = H; tk.reverse = S.reverse;
       flops += 2.0 * S.B * S.T * (4.0 * H + (top ? 0.0 : 4.0 * S.layer[l + 1].units)) * H;
-      if (wide && H % 32) UNSUP(14);
       tk.ntile = (!ksplit && top && H % 32 == 0) ? 2 : 1;
       tk.nct = ksplit ? H / UWH : H / (16 * tk.ntile);
       if (tk.nct > 32) UNSUP(8);
@@ -761,11 +745,10 @@ static int bwd_persistent(const avsr_rnn_stack* st, int32_t n, void* stream, int
   // (K-split kernel: 512-thread workgroups held to 128 VGPRs, two per CU)
   int ecost[B_MAX_TASKS];
   for (int i = 0; i < L.ntask; ++i) ecost[i] = L.task[i].kind == 1 ? 1 : 3;
-  static const int solo_on = getenv("AVSR_RNN_BWD_SOLO") ? atoi(getenv("AVSR_RNN_BWD_SOLO")) : 1;
   int total_cost = 0;
   for (int i = 0; i < L.ntask; ++i) total_cost += cost[i];
-  const int cap = ksplit ? (wide ? 32 : 64) : 28;                         // workgroup slots of an XCD (1024 threads: one per CU)
-  const bool solo = ksplit && solo_on && B > 64 && total_cost <= cap;     // one XCD per 16-row group, 128 rows per launch
+  const int cap = ksplit ? 64 : 28;                                       // workgroup slots of an XCD
+  const bool solo = ksplit && B > 64 && total_cost <= cap;                // one XCD per 16-row group, 128 rows per launch
   if (solo) { for (int i = 0; i < L.ntask; ++i) half[i] = 0; ngroups = 8; }
   else if (!assign_halves(cost, upper, L.ntask, cap, half, ksplit ? ecost : nullptr)) UNSUP(9);
   long words = P_HDR + 8;
@@ -802,8 +785,7 @@ static int bwd_persistent(const avsr_rnn_stack* st, int32_t n, void* stream, int
     if (avsr::dev_zero(sync + P_HDR, sizeof(int32_t) * (words - P_HDR), s) != hipSuccess) return AVSR_ERR_HIP;
     {
       ProfScope ps(PROF_RNN_PERSIST_BWD, s, flops * rows / B);
-      if (ksplit && wide) hipLaunchKernelGGL(rnn_persist_bwdk_kernel<16>, dim3(8 * wpx), dim3(1024), 0, s, L);
-      else if (ksplit) hipLaunchKernelGGL(rnn_persist_bwdk_kernel<8>, dim3(8 * wpx), dim3(512), 0, s, L);
+      if (ksplit) hipLaunchKernelGGL(rnn_persist_bwdk_kernel, dim3(8 * wpx), dim3(512), 0, s, L);
       else hipLaunchKernelGGL(rnn_persist_bwd_kernel, dim3(8 * wpx), dim3(512), 0, s, L);
     }
     AVSR_CHECK_LAUNCH();

@@ -79,15 +79,9 @@ __device__ __forceinline__ void mm16_partial(const StepTask& tk, int row0, int c
         for (int j = 0; j < UN; ++j) {
           const int k = (c + j) << 4;
           const bool in = (c + j < c1) && (k + (q << 2) < S.K);
-#ifdef PROBE_NO_LOAD
-          wv[j] = zero4 + (float)lane;
-#pragma unroll
-          for (int r = 0; r < RM; ++r) av[r][j] = zero4 + (float)k;
-#else
           wv[j] = (in && wcol_ok) ? ld4(wp + k) : zero4;
 #pragma unroll
           for (int r = 0; r < RM; ++r) av[r][j] = (in && aok[r]) ? ld4(ap[r] + k) : zero4;
-#endif
         }
 #pragma unroll
         for (int j = 0; j < UN; ++j) {
@@ -192,10 +186,6 @@ __global__ __launch_bounds__(TN * KP * 64) void step_kernel(const StepLaunch L) 
   if ((int)blockIdx.x * TN * 16 >= tk.N || (int)blockIdx.y * TM * 16 >= tk.B) return;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nt = wave % TN, kp = wave / TN;
-#ifdef PROBE_EMPTY
-  if (tk.B < 0) tk.p5[tid] = 1.f;
-  return;
-#endif
   const int t = tk.t;
 
   // ---- epilogue operands are fetched BEFORE the matmul so their latency hides behind it ------------
@@ -292,10 +282,6 @@ __global__ __launch_bounds__(TN * KP * 64) void step_kernel(const StepLaunch L) 
 #pragma unroll
     for (int r = 0; r < 4; ++r) red[kp][m * TN + nt][(lane >> 4) * 4 + r][lane & 15] = acc[m][r];
   __syncthreads();
-#ifdef PROBE_NO_EPI
-  if (tid < 256 && row0 + (tid >> 4) < tk.B) tk.p5[(long)(row0 + (tid >> 4)) * 16 + (tid & 15)] = red[0][0][tid >> 4][tid & 15] + red[KP - 1][NTILE - 1][tid >> 4][tid & 15];
-  return;
-#endif
   if constexpr (MODE >= EP_GRU_GATES) {
     // ===================== GRU (rnn_cell_impl.GRUCell, cells.py:25-29) =====================
     //   [r,u] = sigmoid([x,h] Wg + bg);  c~ = tanh([x, r*h] Wc + bc);  h' = u*h + (1-u)*c~

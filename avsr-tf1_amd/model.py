@@ -42,8 +42,8 @@ class Seq2SeqModel(EncoderMixin, DecoderMixin):
         self.cfg = cfg = cfg.engine()
         self.gru = cfg.cell_type == "gru"
         # one-launch persistent encoder forward (csrc/rnn_persist.hip); process-wide engine switch
-        # bits: 1 agent-scope forward | 2 XCD-local forward + fused BPTT | 4 split BPTT (measured slower on c4: 3.0 vs 2.7 ms,
-        # kept selectable); 0 = per-step launches only
+        # bits: 1 agent-scope forward | 2 XCD-local forward + persistent BPTT | 4 K-split BPTT off (7: the unit-partitioned BPTT);
+        # 0 = per-step launches only
         pm = int(os.environ.get("AVSR_PERSISTENT_RNN", "3"))
         self.persistent_rnn = pm != 0
         ops.rnn_set_persistent(self.persistent_rnn, device=device, mode=pm or 3)

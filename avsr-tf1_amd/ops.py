@@ -429,15 +429,15 @@ _persist_scratch = None
 
 def rnn_set_persistent(on, device="cuda", ints=1 << 20, mode=3, scratch_floats=64 << 20):
     """Enable / disable the one-launch persistent execution of avsr_rnn_fwd / avsr_rnn_bwd (see include/avsr_hip.h).
-    mode: bit 0 agent-scope forward, bit 1 XCD-local forward + fused BPTT, bit 2 split BPTT (uses a float scratch)."""
+    mode: bit 0 agent-scope forward, bit 1 XCD-local forward + persistent BPTT, bit 2 K-split BPTT off (unit-partitioned BPTT only)."""
     global _persist_sync, _persist_scratch
     check(_L().avsr_rnn_set_persistent_mode(int(mode)), "avsr_rnn_set_persistent_mode")
     if on:
         if _persist_sync is None:
             _persist_sync = torch.zeros(ints, dtype=torch.int32, device=device)
-        if (mode & 6) and _persist_scratch is None:
-            # mode 2: the K-split BPTT kernel's partial-gradient slabs (2 x H/16 x B x H floats per cell) and its helpers' dx records
-            # ([B, T, H] per layer edge); mode 4: the split BPTT's dx operands
+        if (mode & 6) == 2 and _persist_scratch is None:
+            # the K-split BPTT kernel's partial-gradient slabs (2 x H/16 x B x H floats per cell) and its helpers' dx records
+            # ([B, T, H] per layer edge)
             _persist_scratch = torch.zeros(scratch_floats, dtype=torch.float32, device=device)
         if _persist_scratch is not None:
             check(_L().avsr_rnn_set_persistent_scratch(_persist_scratch.data_ptr(), _persist_scratch.numel()), "avsr_rnn_set_persistent_scratch")

@@ -174,12 +174,12 @@ int avsr_rnn_bwd(const avsr_rnn_stack* stacks, int32_t n_stacks, void* stream);
  * units %% 8, in+units > 512, > 512 workgroups) silently use the per-step launches.  Same results either way. */
 int avsr_rnn_set_persistent(int32_t* sync, int64_t ints);
 /* Which persistent kernels may be used: bit 0 = agent-scope (any placement, 16-row tiles), bit 1 = XCD-local
- * (8-row groups bound to the XCD their workgroups actually run on; tried first) and the fused persistent BPTT,
- * bit 2 = split persistent BPTT (needs avsr_rnn_set_persistent_scratch; opt-in), bit 3 = pair-layout forward (16-row groups
- * on XCD pairs; opt-in).  Default 3: the two opt-in forms measured slower on the benchmark shape. */
+ * (8-row groups bound to the XCD their workgroups actually run on; tried first) and the persistent BPTT,
+ * bit 2 = K-split BPTT off (only the unit-partitioned persistent BPTT runs).  Default 3. */
 int avsr_rnn_set_persistent_mode(int mode);
-/* Float device scratch for the split persistent BPTT (bit 2 of the mode): one [B,T,units] operand per encoder cell that has a
- * layer above it.  NULL / too small: that form is skipped (the fused form or the per-step launches run instead). */
+/* Float device scratch for the K-split persistent BPTT (bit 1 of the mode without bit 2): its partial-gradient slabs and one
+ * [B,T,units] operand per encoder cell that has a layer above it.  NULL / too small: that form is skipped (the unit-partitioned
+ * BPTT or the per-step launches run instead). */
 int avsr_rnn_set_persistent_scratch(float* scratch, int64_t floats);
 
 /* ---------------------------------------------------------------------------------------------
@@ -368,10 +368,9 @@ int avsr_attn_rnn_fused_fwd_active(const avsr_attn_rnn* d);
  * under the same conditions.  Process-wide switch: 0 per-step launches, 1 (default) fused forward and backward, 2 forward only,
  * 3 backward only; the path also needs avsr_rnn_set_persistent's sync scratch. */
 int avsr_attn_rnn_set_fused(int32_t on);
-/* Beam search (mode 3): which kernels run the B * K-row steps.  1 (default; AVSR_ATTN_BEAM / AVSR_BEAM_DENSE in the environment set
- * the initial values) = all beam-shaped kernels: the per-step attention as one workgroup per (utterance, chunk) serving all K
- * hypotheses over the shared memories, scores and contexts on the matrix pipe with the hypotheses as one MFMA row tile
- * (attn_fwd_beam_mfma_kernel), and the LSTM cell / attention layers as 64 x 64-tiled products with row-gathered operands
+/* Beam search (mode 3): which kernels run the B * K-row steps.  1 (default) = all beam-shaped kernels: the per-step attention
+ * as one workgroup per (utterance, chunk) serving all K hypotheses over the shared memories, scores and contexts on the matrix
+ * pipe with the hypotheses as one MFMA row tile (attn_fwd_beam_mfma_kernel), and the LSTM cell / attention layers as 64 x 64-tiled products with row-gathered operands
  * (csrc/beam_gemm.hip); 2 = the scalar K-hypotheses attention kernel (attn_fwd_beam_kernel) only, dense steps through the small-tile step kernel;
  * 0 = the general kernels everywhere.  0 and 2 give bit-identical scores, statistics and contexts; 1 differs from them by the
  * summation order of the dense products (tests/test_gpu_beam.py checks all three against the oracle). */

@@ -25,7 +25,6 @@ one "c2 --batch 256" --workload c2 --batch 256
 one "c3 --batch 256" --workload c3 --batch 256
 AVSR_PERSISTENT_RNN=0 one "c4 AVSR_PERSISTENT_RNN=0"
 AVSR_CNN_FOLD=0 one "c4 AVSR_CNN_FOLD=0"
-AVSR_RNN_BWD_WIDE=1 one "c4 AVSR_RNN_BWD_WIDE=1"
 two "2 ranks default"
 two "2 ranks --strong" --strong
 two "2 ranks --no-graph" --no-graph

@@ -21,7 +21,7 @@ case = "c4_bimodal_cnn" if rng.integers(2) else "c3_video_cnn_bi"
 B, Tv = int(rng.integers(2, 5)), int(rng.integers(3, 7))
 drop = bool(rng.integers(2))
 print(seed, case, hw, filters, dense, B, Tv, drop)
-for env in ({}, {"AVSR_CNN_FOLD": "0"}, {"AVSR_WG_WPC": "2"}):
+for env in ({}, {"AVSR_CNN_FOLD": "0"}):
     os.environ.update(env)
     O, ocfg, mcfg, W, batch = make(case, B=B, Ta=4 * Tv, Tv=Tv, L=5, video_hw=hw, cnn_filters=filters, cnn_dense_units=dense, video_feat=dense, use_dropout=drop)
     ref = O.train_step(W, None, ocfg, batch)

@@ -1,5 +1,5 @@
 // Standalone timing probe for the step kernel (development tool, not part of the product):
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -I avsr-tf1_amd/csrc [-DPROBE_...] tools/step_probe.hip -o /tmp/probe
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -I include -I avsr-tf1_amd/csrc tools/step_probe.hip -o /tmp/probe
 // Builds C4-like forward / backward launches (B=64, H=256, 3 wavefront tasks) and reports us per launch.
 #include <cstdio>
 #include <vector>
