@@ -6,12 +6,14 @@ try_restore_latest_checkpoint)` / `evaluate(checkpoint_path, epoch)` behaviour a
 (own .npz format: TF-layout weights + Adam slots + step; epoch parsed from the file name on resume, :233-249),
 `predictions/<name>/predicted_epoch_<N>.mlf`.  TensorFlow graphs/sessions/summaries do not exist here.
 
-`video_processing='resnet_cnn'` runs the lip crops through the HIP lip-CNN front-end (cnn.py; avsr/video.py:143-195).
+`video_processing='resnet_cnn'` runs the lip crops through the HIP lip-CNN front-end (cnn.py; avsr/video.py:143-195);
+`video_processing='3dconv_cnn'` through the spatio-temporal front-end (cnn3d.py, csrc/conv3d.hip; avsr/video.py:198-222), whose final
+conv3d is built with strides (1, 1, 1) where the reference passes (1, 1).
 Built besides the defaults: `input_dense_layers`, `instance_normalisation`, `residual_encoder`, `highway_encoder`, `encoder_weight_sharing`, multi-layer
 decoders (equal widths), `enable_attention=False`, `loss_fun` / `label_smoothing`, `lr_decay=('cosine_restarts', N)`, the Nadam /
 AdamW / Momentum optimisers, `write_attention_alignment` (greedy decoding), one-hot decoder inputs (`embedding_size <= 0`).  Feature / unit /
 embedding sizes may be anything (the engine pads to multiples of 4 inside, config.py `engine()`; checkpoints keep the reference's shapes).
-Not built (raise explicitly): `precision='float16'`, the `2dconv_cnn` / `3dconv_cnn` front-ends, `'wav'` audio
+Not built (raise explicitly): `precision='float16'`, the `2dconv_cnn` front-end, `sync_cnn_bn` data parallelism with `3dconv_cnn`, `'wav'` audio
 (non-functional in the reference too), the monotonic attention variants and the non-default cell types.
 """
 import glob
@@ -108,9 +110,9 @@ class AVSR(object):
                 print('learning rate policy not implemented, falling back to constant learning rate')
         if loss_fun not in (None, 'focal_loss', 'mc_loss'):
             raise ValueError('Unknown loss function {}'.format(loss_fun))                           # seq2seq.py:163
-        if video_processing is not None and video_processing not in ('features', 'resnet_cnn'):
+        if video_processing is not None and video_processing not in ('features', 'resnet_cnn', '3dconv_cnn'):
             if 'cnn' in video_processing:
-                raise NotImplementedError("video_processing=%r: only the default `resnet_cnn` front-end is built" % video_processing)
+                raise NotImplementedError("video_processing=%r: the `resnet_cnn` and `3dconv_cnn` front-ends are built" % video_processing)
             raise Exception('unknown visual content')                                             # avsr/avsr.py:713
         if audio_processing is not None and audio_processing != 'features':
             raise NotImplementedError("audio_processing=%r (the reference's 'wav' path is non-functional as well)" % audio_processing)
@@ -128,13 +130,13 @@ class AVSR(object):
             rec = self._records['train'][idx] or self._records['evaluate'][idx]
             if proc is not None:
                 shape, _ = _get_input_shape_from_record(rec)
-                if key == 'video' and proc == 'resnet_cnn':
+                if key == 'video' and proc in ('resnet_cnn', '3dconv_cnn'):
                     if len(shape) != 3:
-                        raise ValueError("video_processing='resnet_cnn' needs raw [width, height, channels] frames in the video record")
+                        raise ValueError("video_processing=%r needs raw [width, height, channels] frames in the video record" % proc)
                     video_hw, feats[key] = tuple(shape), cnn_dense_units
                     continue
                 if len(shape) != 1:
-                    raise ValueError("raw video records need video_processing='resnet_cnn'")
+                    raise ValueError("raw video records need video_processing='resnet_cnn' or '3dconv_cnn'")
                 feats[key] = shape[0]
         self._cfg = ModelConfig(
             architecture=architecture, encoder_type=encoder_type, cell_type=cell_type,

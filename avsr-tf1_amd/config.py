@@ -53,7 +53,7 @@ class ModelConfig:
     decoder_dropout: Tuple[float, float, float] = (0.9, 0.9, 0.9)
     sampling_probability: float = 0.0
     # visual front-end (avsr/avsr.py:24, :33-34): "features" = records already hold cnn_dense_units-d vectors,
-    # "resnet_cnn" = lip crops [B, T, H, W, C] through video.resnet_cnn (cnn.py)
+    # "resnet_cnn" = lip crops [B, T, H, W, C] through video.resnet_cnn (cnn.py), "3dconv_cnn" = through video.conv3d_cnn (cnn3d.py)
     video_processing: str = "features"
     cnn_filters: Tuple[int, ...] = (8, 16, 32, 64)
     cnn_dense_units: int = 128
@@ -187,9 +187,13 @@ class ModelConfig:
             if self.encoder_weight_sharing and self.wrapped(st):
                 if len(u) > 2 and (len(set(u[1:])) != 1 or u[0] != u[1]):
                     raise ValueError("encoder_weight_sharing needs equal layer sizes: layers >= 2 reuse layer 1's kernel")
-        if self.video_processing not in ("features", "resnet_cnn"):
-            raise Exception("unknown visual content")                                   # avsr/avsr.py:713 (2dconv_cnn / 3dconv_cnn: not built)
-        if self.video_units is not None and self.video_processing == "resnet_cnn":
+        if self.video_processing not in ("features", "resnet_cnn", "3dconv_cnn"):
+            raise Exception("unknown visual content")                                   # avsr/avsr.py:713 (2dconv_cnn: not built)
+        if self.video_units is not None and self.video_processing == "3dconv_cnn":
+            c = self.video_hw[2]
+            if max(self.cnn_filters) > 128 or c > 128 or (c > 3 and c % 4):
+                raise ValueError("3dconv_cnn: cnn_filters up to 128, frames of 1-3 or 4n <= 128 channels (avsr_conv3d_supported)")
+        if self.video_units is not None and self.video_processing in ("resnet_cnn", "3dconv_cnn"):
             if self.video_feat != self.cnn_dense_units:
                 raise ValueError("video_feat must equal cnn_dense_units when the CNN front-end produces the video features")
             if any(c % 4 for c in self.cnn_filters) or self.cnn_dense_units % 4 or len(self.cnn_filters) < 1:

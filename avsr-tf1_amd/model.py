@@ -87,7 +87,7 @@ class Seq2SeqModel(EncoderMixin, DecoderMixin):
         self.S = {n: Ref(self.stats, o, self.inv[n][0]) for n, o in self._stat_off.items()}
         self.l2_segments = [(self._train_off[n], int(np.prod(self.inv[n][0]))) for n in self._train_off if PR.is_l2(n)]
         self.cnn_l2_segments = [(self._train_off[n], int(np.prod(self.inv[n][0]))) for n in self._train_off if PR.is_cnn_l2(n)]
-        self.use_cnn = cfg.video_units is not None and cfg.video_processing == "resnet_cnn"
+        self.use_cnn = cfg.video_units is not None and cfg.video_processing in ("resnet_cnn", "3dconv_cnn")
         self.dense_l2_segments = [(self._train_off[n], int(np.prod(self.inv[n][0]))) for n in self._train_off if PR.is_dense_l2(n)]
         self.bn_sync = None                       # set by bn_sync_enable() under data parallelism
         self.n_dense = len(cfg.input_dense_layers) if cfg.input_dense_layers[0] > 0 else 0
@@ -160,7 +160,16 @@ class Seq2SeqModel(EncoderMixin, DecoderMixin):
                 o = self._train_off[name]
                 buf[o:o + e.numel()].copy_(e)
 
-    def export_tf_weights(self, which="params") -> Dict[str, np.ndarray]:
+    def export_tf_weights(self, which="params", tf_names=False) -> Dict[str, np.ndarray]:
+        """{name: array} in TF layout.  tf_names=True: keyed by the reference graph's variable names where the engine's differ
+        (params.tf_variable_names: the 3dconv_cnn layers' conv3d_N / batch_normalization_N)."""
+        out = self._export_tf_weights(which)
+        if tf_names:
+            ren = PR.tf_variable_names(self.cfg_tf)
+            out = OrderedDict((ren.get(k, k), v) for k, v in out.items())
+        return out
+
+    def _export_tf_weights(self, which="params") -> Dict[str, np.ndarray]:
         src = {"params": self.params, "grads": self.grads, "adam_m": self.adam_m, "adam_v": self.adam_v}[which]
         host = src.detach().cpu().numpy()
         out = OrderedDict()
@@ -211,8 +220,12 @@ class Seq2SeqModel(EncoderMixin, DecoderMixin):
             if cfg.instance_normalisation:
                 E["xi"], E["in_mean"], E["in_invstd"], E["in_dg"], E["in_db"] = z(B * T, F), z(B, F), z(B, F), z(B, F), z(B, F)
             if s == "video" and self.use_cnn:
-                from .cnn import LipCNN
-                E["cnn"] = LipCNN(self, B * T)                       # lip crops -> F = cnn_dense_units features
+                if cfg.video_processing == "3dconv_cnn":
+                    from .cnn3d import LipCNN3D
+                    E["cnn"] = LipCNN3D(self, B, T, grads=not greedy)   # the padded batch as one [B, T, H, W, C] map
+                else:
+                    from .cnn import LipCNN
+                    E["cnn"] = LipCNN(self, B * T)                   # lip crops -> F = cnn_dense_units features
                 E["dfeat"] = z(B * T, F)
             if cfg.use_dropout:
                 E["xd"] = {d: z(B * T, F0) for d in cfg.directions()}    # layer-0 input after each direction's input mask

@@ -618,6 +618,50 @@ def slab_defer_begin():
     check(_L().avsr_slab_defer_begin(), "avsr_slab_defer_begin")
 
 
+def conv3d_desc(B, T, H, W, Ci, Co, k, stride, pads, Ho, Wo, tf=None, relu=1):
+    """avsr_conv3d_desc; k = (kt, kh, kw), pads = (front, top, left); tf = (scale, shift) device vectors of the loader transform."""
+    from ._lib import Conv3dDesc
+    d = Conv3dDesc(B, T, H, W, Ci, Co, k[0], k[1], k[2], stride, pads[0], pads[1], pads[2], Ho, Wo, int(relu), None, None)
+    if tf is not None:
+        d.scale, d.shift = fptr(tf[0]), fptr(tf[1])
+    return d
+
+
+def conv3d_supported(d):
+    return bool(_L().avsr_conv3d_supported(C.byref(d)))
+
+
+def conv3d_wgrad_scratch_floats(d):
+    n = int(_L().avsr_conv3d_wgrad_scratch_floats(C.byref(d)))
+    if n < 0:
+        raise _lib.AvsrError("avsr_conv3d_wgrad_scratch_floats: unsupported geometry")
+    return n
+
+
+def conv3d_fwd(d, x, w, y, res=None, res_tf=None, stats=None):
+    """Returns the number of statistic partial rows written (0 without stats)."""
+    n = C.c_int32(0)
+    check(_L().avsr_conv3d_fwd(C.byref(d), fptr(x), fptr(w), fptr(res), fptr(res_tf[0]) if res_tf else None, fptr(res_tf[1]) if res_tf else None,
+                               fptr(y), fptr(stats), C.byref(n), _s()), "avsr_conv3d_fwd")
+    return int(n.value)
+
+
+def conv3d_bwd_data(d, dy, w, dx, beta=0.0):
+    check(_L().avsr_conv3d_bwd_data(C.byref(d), fptr(dy), fptr(w), fptr(dx), float(beta), _s()), "avsr_conv3d_bwd_data")
+
+
+def conv3d_bwd_weight(d, x, dy, dw, scratch, beta=1.0):
+    check(_L().avsr_conv3d_bwd_weight(C.byref(d), fptr(x), fptr(dy), fptr(dw), float(beta), fptr(scratch), scratch.numel(), _s()),
+          "avsr_conv3d_bwd_weight")
+
+
+def conv3d_bn_finalize(part, nparts, Cn, count, eps, momentum, mean, invstd, mov_mean, mov_var, gamma=None, beta=None, scale=None, shift=None):
+    """avsr_bn_finalize with the biased moving variance of the non-fused (rank-5) batch norm."""
+    check(_L().avsr_conv3d_bn_finalize(fptr(part), int(nparts), int(Cn), int(count), float(eps), float(momentum), fptr(mean), fptr(invstd),
+                                       fptr(mov_mean), fptr(mov_var), fptr(gamma), fptr(beta), fptr(scale), fptr(shift), _s()),
+          "avsr_conv3d_bn_finalize")
+
+
 def slab_defer_end():
     check(_L().avsr_slab_defer_end(_s()), "avsr_slab_defer_end")
 

@@ -86,6 +86,8 @@ class DataParallelTrainer:
         if sync_cnn_bn is None:
             sync_cnn_bn = os.environ.get("AVSR_DP_SYNC_CNN_BN") == "1"
         self.sync_cnn_bn = bool(sync_cnn_bn and self.collective and getattr(model, "use_cnn", False))
+        if self.sync_cnn_bn and model.cfg.video_processing == "3dconv_cnn":
+            raise NotImplementedError("sync_cnn_bn=True is not built for video_processing='3dconv_cnn': its batch norms run per rank")
         if self.sync_cnn_bn:
             model.cnn_bn_sync = lambda t: dist.all_reduce(t)
             self.use_graph = False

@@ -108,8 +108,11 @@ def _layout(cfg: ModelConfig):
         if stream == "video" and cfg.regress_aus:
             inv["video/au/kernel"] = ([depth("video"), [2]], "plain", "glorot")
             inv["video/au/bias"] = ([[2]], "plain", "zeros")
-    if cfg.video_units is not None and cfg.video_processing == "resnet_cnn":
-        from .cnn import param_shapes
+    if cfg.video_units is not None and cfg.video_processing in ("resnet_cnn", "3dconv_cnn"):
+        if cfg.video_processing == "3dconv_cnn":                 # no biases; [kt, kh, kw, cin, cout] kernels (cnn3d.tf_names: TF's names)
+            from .cnn3d import param_shapes
+        else:
+            from .cnn import param_shapes
         init_of = {"conv_kernel": "conv_vs", "bias": "zeros", "gamma": "ones", "beta": "zeros", "moving_mean": "zeros", "moving_variance": "ones"}
         for name, shape, role in param_shapes(cfg.video_hw, cfg.cnn_filters, cfg.cnn_dense_units):
             inv["video/cnn/" + name] = ([[n] for n in shape], "plain", init_of[role])
@@ -200,8 +203,17 @@ def _attention(inv, prefix, att_type, depth, units):
     inv[prefix + "/layer_kernel"] = ([[units] + depth, [units]], "plain", "glorot")
 
 
+def tf_variable_names(cfg: ModelConfig):
+    """{engine name: TF variable name} where the two differ: the 3dconv_cnn front-end's layers, which the reference leaves to TF's
+    auto-generated names (conv3d, conv3d_1, ..., batch_normalization, batch_normalization_1, ...; cnn3d.tf_names)."""
+    if cfg.video_units is None or cfg.video_processing != "3dconv_cnn":
+        return {}
+    from .cnn3d import tf_names
+    return {"video/cnn/" + k: "video/cnn/" + v for k, v in tf_names(cfg.video_hw, cfg.cnn_filters, cfg.cnn_dense_units).items()}
+
+
 def is_cnn_l2(name):
-    """conv2d kernel_regularizer l2(0.001) of the lip CNN (video.py:26; summed at seq2seq.py:180-184)."""
+    """conv2d / conv3d kernel_regularizer l2(0.001) of the lip CNN (video.py:26, :43; summed at seq2seq.py:180-184)."""
     return name.startswith("video/cnn/") and name.endswith("/kernel")
 
 
@@ -230,8 +242,8 @@ def initialise(cfg: ModelConfig, seed=0):
                 x[bad] = rng.standard_normal(int(bad.sum()))
                 bad = np.abs(x) > 2.0
             a = x * std
-        elif init == "conv_vs":                 # variance_scaling(scale=2.0, fan_in) on [kh, kw, cin, cout] (video.py:24)
-            std = math.sqrt(2.0 / (shape[0] * shape[1] * shape[2])) / 0.87962566103423978
+        elif init == "conv_vs":                 # variance_scaling(scale=2.0, fan_in) on [kh, kw, cin, cout] / [kt, kh, kw, cin, cout] (video.py:24, :41)
+            std = math.sqrt(2.0 / int(np.prod(shape[:-1]))) / 0.87962566103423978
             x = rng.standard_normal(shape)
             bad = np.abs(x) > 2.0
             while bad.any():

@@ -565,6 +565,37 @@ int avsr_conv3x3_bwd_data_s2(const float* dy, const float* w, float* dx, int32_t
 int avsr_conv3x3_bwd_weight(const float* x, const float* dy, float* dw, int32_t N, int32_t H, int32_t W, int32_t Ci, int32_t Co,
                             int32_t stride, int32_t pad_t, int32_t pad_l, int32_t Ho, int32_t Wo, float beta, float* scratch,
                             int64_t scratch_floats, void* stream);
+/* ---- spatio-temporal lip front-end (avsr/video.py:34-46 conv3d_wrapper, :92-105 residual_block_3d, :198-222 conv3d_cnn) ----
+ * tf.layers.conv3d(use_bias=False) over NDHWC maps x [B, T, H, W, Ci] -> y [B, T, Ho, Wo, Co] with kernel w [kt, kh, kw, Ci, Co] (TF
+ * layout, = the [kt*kh*kw*Ci, Co] GEMM operand), spatial stride 1 / 2, temporal stride 1; pad_f / pad_t / pad_l = zero frames / rows /
+ * columns before the map (TF SAME: the odd one goes after).  Implicit GEMMs on v_mfma_f32_16x16x4_f32 (csrc/conv3d.hip).
+ *   scale / shift (may be NULL): the kernels read the source of the forward and of the weight gradient as max(x*scale[c] + shift[c], 0)
+ *     (relu = 1: the consumer-side batch_norm_relu of video.py:4-14; the normalised map is never written) or x*scale + shift (relu = 0:
+ *     layer 0's `inputs * 2 - 1`); the zero padding comes after the transform.
+ *   avsr_conv3d_fwd: y = conv(x) (+ res, itself read as max(res*res_scale + res_shift, 0) when res_scale != NULL); stats != NULL
+ *     (>= 512*2*Co floats): per-workgroup partial sums / sums of squares of y [*nparts][2*Co] for the batch norm that consumes y.
+ *   avsr_conv3d_bwd_data: dx = beta*dx + conv_transpose(dy) (every dx element is written).
+ *   avsr_conv3d_bwd_weight: dw = beta*dw + sum x (x) dy; scratch >= avsr_conv3d_wgrad_scratch_floats(c) floats (deterministic split).
+ *   avsr_conv3d_bn_finalize: avsr_bn_finalize for the NON-fused batch norm of a rank-5 map (TF 1.13 keeps fused=True for rank 4 only):
+ *     the moving variance takes the biased batch variance.
+ * Covered: kt, kh, kw <= 3, Ci in {1..3, 4n <= 128}, Co = 4n <= 128 (avsr_conv3d_supported); otherwise AVSR_ERR_UNSUPPORTED (-3). */
+typedef struct avsr_conv3d_desc {
+  int32_t B, T, H, W, Ci, Co;
+  int32_t kt, kh, kw, stride;
+  int32_t pad_f, pad_t, pad_l, Ho, Wo, relu;
+  const float* scale;
+  const float* shift;
+} avsr_conv3d_desc;
+int avsr_conv3d_supported(const avsr_conv3d_desc* c);
+int64_t avsr_conv3d_wgrad_scratch_floats(const avsr_conv3d_desc* c);
+int avsr_conv3d_fwd(const avsr_conv3d_desc* c, const float* x, const float* w, const float* res, const float* res_scale, const float* res_shift,
+                    float* y, float* stats, int32_t* nparts, void* stream);
+int avsr_conv3d_bwd_data(const avsr_conv3d_desc* c, const float* dy, const float* w, float* dx, float beta, void* stream);
+int avsr_conv3d_bwd_weight(const avsr_conv3d_desc* c, const float* x, const float* dy, float* dw, float beta, float* scratch,
+                           int64_t scratch_floats, void* stream);
+int avsr_conv3d_bn_finalize(const float* part, int32_t nparts, int32_t C, int64_t count, float eps, float momentum, float* mean,
+                            float* invstd, float* mov_mean, float* mov_var, const float* gamma, const float* beta, float* scale,
+                            float* shift, void* stream);
 /* y = max(x, 0);  dx = dy * [y > 0];  out = a + b (tf.nn.relu / residual tf.add of video.py) */
 int avsr_relu(const float* x, float* y, int64_t n, void* stream);
 int avsr_relu_bwd(const float* y, const float* dy, float* dx, int64_t n, void* stream);
