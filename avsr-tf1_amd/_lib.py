@@ -116,6 +116,12 @@ class Conv3dDesc(C.Structure):
                                          "relu")] + [("scale", C.c_void_p), ("shift", C.c_void_p)]
 
 
+class LogmelArgs(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("B", "N", "T_out", "F", "frame_length", "frame_step", "fft_length", "num_mel_bins", "window", "stride",
+                                         "mel_nnz", "pad_")] + \
+               [(n, C.c_void_p) for n in ("wav", "wav_len", "hann", "twiddle", "mel_lo", "mel_cnt", "mel_ptr", "mel_w", "out", "out_len")]
+
+
 class ColsumJob(C.Structure):
     _fields_ = [("a", Mat), ("b", Mat), ("out", C.c_void_p), ("rows", C.c_int32), ("F", C.c_int32), ("alpha", C.c_float), ("beta", C.c_float)]
 
@@ -125,13 +131,13 @@ class TransposeJob(C.Structure):
 
 
 _STRUCTS = {"avsr_dec_layer": DecLayer, "avsr_mat": Mat, "avsr_gemm_desc": GemmDesc, "avsr_rnn_layer": RnnLayer, "avsr_rnn_stack": RnnStack,
-            "avsr_conv_desc": ConvDesc, "avsr_conv3d_desc": Conv3dDesc, "avsr_attn_mech": AttnMech, "avsr_attn_rnn": AttnRnn, "avsr_transpose_job": TransposeJob,
+            "avsr_conv_desc": ConvDesc, "avsr_conv3d_desc": Conv3dDesc, "avsr_logmel_args": LogmelArgs, "avsr_attn_mech": AttnMech, "avsr_attn_rnn": AttnRnn, "avsr_transpose_job": TransposeJob,
             "avsr_colsum_job": ColsumJob}
 
 EXPORTS = ["avsr_abi_version", "avsr_sizeof", "avsr_gemm", "avsr_gemm_batch", "avsr_rnn_fwd", "avsr_rnn_bwd", "avsr_rnn_set_persistent", "avsr_rnn_set_persistent_mode", "avsr_rnn_set_persistent_scratch", "avsr_attn_rnn_fwd",
            "avsr_attn_rnn_fused_ws_floats", "avsr_attn_rnn_fused_eligible", "avsr_attn_rnn_fused_fwd_active", "avsr_attn_rnn_set_fused", "avsr_attn_rnn_set_beam_kernel", "avsr_conv_set_mfma", "avsr_conv_supported", "avsr_conv_fwd", "avsr_conv_bwd_data", "avsr_conv_bwd_weight", "avsr_bn_finalize", "avsr_batchnorm_apply", "avsr_conv_bwd_data_bn", "avsr_conv_bwd_data_bn_supported", "avsr_conv_bwd_weight_bn", "avsr_conv_bwd_weight_bn_supported", "avsr_bn_bwd_finalize", "avsr_bn_bwd_apply", "avsr_bn_bwd_stage1", "avsr_bn_eval_affine", "avsr_bn_partials_f64", "avsr_bn_finalize_f64", "avsr_bn_bwd_finalize_f64",
            "avsr_conv3d_supported", "avsr_conv3d_wgrad_scratch_floats", "avsr_conv3d_fwd", "avsr_conv3d_bwd_data", "avsr_conv3d_bwd_weight",
-           "avsr_conv3d_bn_finalize",
+           "avsr_conv3d_bn_finalize", "avsr_logmel_supported", "avsr_logmel_fwd",
            "avsr_attn_rnn_bwd", "avsr_beam_gather_tree", "avsr_beam_search_step", "avsr_attn_alpha_rows", "avsr_bahdanau_dkeys", "avsr_transpose", "avsr_slab_defer_begin", "avsr_slab_defer_end", "avsr_colsum",
            "avsr_batchnorm_fwd", "avsr_batchnorm_fwd_ex", "avsr_batchnorm_bwd", "avsr_batchnorm_xhat", "avsr_im2col", "avsr_col2im",
            "avsr_relu", "avsr_relu_bwd", "avsr_add", "avsr_selu", "avsr_selu_bwd", "avsr_conv3x3_supported", "avsr_conv3x3", "avsr_conv3x3_bwd_data_s2",
@@ -202,6 +208,8 @@ def load():
         "avsr_conv3d_bwd_data": [C.POINTER(Conv3dDesc), vp, vp, vp, f32, vp],
         "avsr_conv3d_bwd_weight": [C.POINTER(Conv3dDesc), vp, vp, vp, f32, vp, i64, vp],
         "avsr_conv3d_bn_finalize": [vp, i32, i32, i64, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
+        "avsr_logmel_supported": [i32, i32, i32, i32, i32],
+        "avsr_logmel_fwd": [C.POINTER(LogmelArgs), vp],
         "avsr_batchnorm_apply": [vp, vp, i32, i32, vp, vp, vp, vp, i32, vp],
         "avsr_attn_rnn_bwd": [C.POINTER(AttnRnn), vp],
         "avsr_beam_gather_tree": [vp, vp, vp, vp, i32, i32, i32, i32, vp],

@@ -13,8 +13,13 @@ Built besides the defaults: `input_dense_layers`, `instance_normalisation`, `res
 decoders (equal widths), `enable_attention=False`, `loss_fun` / `label_smoothing`, `lr_decay=('cosine_restarts', N)`, the Nadam /
 AdamW / Momentum optimisers, `write_attention_alignment` (greedy decoding), one-hot decoder inputs (`embedding_size <= 0`).  Feature / unit /
 embedding sizes may be anything (the engine pads to multiples of 4 inside, config.py `engine()`; checkpoints keep the reference's shapes).
-Not built (raise explicitly): `precision='float16'`, the `2dconv_cnn` front-end, `sync_cnn_bn` data parallelism with `3dconv_cnn`, `'wav'` audio
-(non-functional in the reference too), the monotonic attention variants and the non-default cell types.
+`audio_processing='wav'` takes waveform records (one float per step) and runs the dataset writer's log-mel pipeline inside the model
+(audio_frontend.py, csrc/audio_frontend.hip); keywords `audio_transformation` ('logmel_stack_w8s3' | 'logmel_stack_w3s3' | 'logmel'),
+`num_mel_bins` (30) and `sample_rate` (16000) arrive through **kwargs.  The reference's own 'wav' branch (avsr/avsr.py:719-724) omits
+`need_logmel`, so its encoder would get the complex STFT with lengths in samples and cannot train; the engine computes what the writer
+computes instead.
+Not built (raise explicitly): `precision='float16'`, the `2dconv_cnn` front-end, `sync_cnn_bn` data parallelism with `3dconv_cnn`, the
+writer's MFCC / delta audio transformations, the monotonic attention variants and the non-default cell types.
 """
 import glob
 import os
@@ -114,8 +119,13 @@ class AVSR(object):
             if 'cnn' in video_processing:
                 raise NotImplementedError("video_processing=%r: the `resnet_cnn` and `3dconv_cnn` front-ends are built" % video_processing)
             raise Exception('unknown visual content')                                             # avsr/avsr.py:713
-        if audio_processing is not None and audio_processing != 'features':
-            raise NotImplementedError("audio_processing=%r (the reference's 'wav' path is non-functional as well)" % audio_processing)
+        if audio_processing is not None and audio_processing not in ('features', 'wav'):
+            raise NotImplementedError("audio_processing=%r: 'features' and 'wav' are built" % audio_processing)
+        self._audio_frontend = None
+        if audio_processing == 'wav':                     # raises here for the refused transformations / sample rates / filter counts
+            from .audio_frontend import LogmelSpec
+            self._audio_frontend = LogmelSpec(kwargs.get('audio_transformation', 'logmel_stack_w8s3'), kwargs.get('num_mel_bins', 30),
+                                              kwargs.get('sample_rate', 16000))
         if decoding_algorithm not in ('greedy', 'beam_search'):
             raise Exception('The only supported algorithms are `greedy` and `beam_search`')     # decoder_unimodal.py:124
         self._decoding_algorithm, self._beam_width = decoding_algorithm, beam_width
@@ -137,6 +147,11 @@ class AVSR(object):
                     continue
                 if len(shape) != 1:
                     raise ValueError("raw video records need video_processing='resnet_cnn' or '3dconv_cnn'")
+                if key == 'audio' and proc == 'wav':
+                    if shape[0] != 1:
+                        raise ValueError("audio_processing='wav' needs a waveform record (input_size == 1), got input_size == %d" % shape[0])
+                    feats[key] = self._audio_frontend.feat
+                    continue
                 feats[key] = shape[0]
         self._cfg = ModelConfig(
             architecture=architecture, encoder_type=encoder_type, cell_type=cell_type,
@@ -156,6 +171,9 @@ class AVSR(object):
             audio_dropout=tuple(audio_encoder_dropout_probability), decoder_dropout=tuple(decoder_dropout_probability),
             sampling_probability=sampling_probability_outputs,
             video_processing=video_processing if video_processing is not None else 'features',
+            audio_processing=audio_processing if audio_processing is not None else 'features',
+            **({} if self._audio_frontend is None else dict(zip(('audio_transformation', 'num_mel_bins', 'sample_rate'),
+                                                                 self._audio_frontend.key()))),
             cnn_filters=tuple(cnn_filters), cnn_dense_units=cnn_dense_units, video_hw=video_hw,
             input_dense_layers=tuple(input_dense_layers), encoder_weight_sharing=bool(encoder_weight_sharing), residual_encoder=bool(residual_encoder), highway_encoder=bool(highway_encoder), instance_normalisation=bool(instance_normalisation))
         self._model = Seq2SeqModel(self._cfg, seed=kwargs.get('seed', 0))
@@ -196,11 +214,12 @@ class AVSR(object):
             seed = seed + self._epoch_counter                     # a new order every epoch; under data parallelism identical on every rank
         if self._video_processing is not None and self._audio_processing is not None:
             return make_iterator_from_two_records(vrec, arec, lrec, bs, self._unit_dict, shuffle=shuffle, bucket_width=45,
-                                                  seed=seed, rank=rank, world=world)
+                                                  seed=seed, rank=rank, world=world, audio_frontend=self._audio_frontend)
         rec = vrec if self._video_processing is not None else arec
         return make_iterator_from_one_record(rec, lrec, self._unit_dict, bs, shuffle=shuffle, bucket_width=45,
                                              max_sentence_length=self._max_sentence_length if self._audio_processing is not None else None,
-                                             seed=seed, rank=rank, world=world)
+                                             seed=seed, rank=rank, world=world,
+                                             audio_frontend=self._audio_frontend if self._audio_processing is not None else None)
 
     @staticmethod
     def _prefetched(it, depth=2):
@@ -258,6 +277,9 @@ class AVSR(object):
         for which in ("params", "adam_m", "adam_v"):
             for k, v in m.export_tf_weights(which).items():
                 blob[which + ":" + k] = v
+        fe = getattr(self, "_audio_frontend", None)       # (avsr.LM borrows save / restore and has no front-end)
+        if fe is not None:                                # the front-end has no variables: its configuration is the checkpoint's metadata
+            blob["meta:audio_frontend"] = np.array([str(v) for v in fe.key()])
         makedirs(path.dirname(checkpoint_path), exist_ok=True)
         np.savez(checkpoint_path + ".npz", **blob)
         return checkpoint_path
@@ -265,6 +287,11 @@ class AVSR(object):
     def restore(self, checkpoint_path):
         z = np.load(checkpoint_path if checkpoint_path.endswith(".npz") else checkpoint_path + ".npz")
         m = self._model
+        fe = getattr(self, "_audio_frontend", None)
+        if "meta:audio_frontend" in z.files and fe is not None:
+            saved, mine = [str(v) for v in z["meta:audio_frontend"]], [str(v) for v in fe.key()]
+            if saved != mine:
+                raise ValueError("checkpoint was trained with the audio front-end %s, this model has %s" % (saved, mine))
         m.load_tf_weights({k[7:]: z[k] for k in z.files if k.startswith("params:")})
         for which, buf in (("adam_m", m.adam_m), ("adam_v", m.adam_v)):
             W = {k[len(which) + 1:]: z[k] for k in z.files if k.startswith(which + ":")}

@@ -55,6 +55,12 @@ class ModelConfig:
     # visual front-end (avsr/avsr.py:24, :33-34): "features" = records already hold cnn_dense_units-d vectors,
     # "resnet_cnn" = lip crops [B, T, H, W, C] through video.resnet_cnn (cnn.py), "3dconv_cnn" = through video.conv3d_cnn (cnn3d.py)
     video_processing: str = "features"
+    # audio front-end (avsr/avsr.py:27): "features" = records already hold audio_feat-d vectors, "wav" = records hold samples and the
+    # dataset writer's log-mel pipeline runs inside the model (audio_frontend.py); audio_feat is then num_mel_bins * stacking window
+    audio_processing: str = "features"
+    audio_transformation: str = "logmel_stack_w8s3"                 # | "logmel_stack_w3s3" | "logmel" (dataset_writer.py:357-380)
+    num_mel_bins: int = 30                                          # dataset_writer.py:410
+    sample_rate: int = 16000
     cnn_filters: Tuple[int, ...] = (8, 16, 32, 64)
     cnn_dense_units: int = 128
     video_hw: Tuple[int, int, int] = (36, 36, 3)
@@ -198,6 +204,14 @@ class ModelConfig:
                 raise ValueError("video_feat must equal cnn_dense_units when the CNN front-end produces the video features")
             if any(c % 4 for c in self.cnn_filters) or self.cnn_dense_units % 4 or len(self.cnn_filters) < 1:
                 raise ValueError("cnn_filters / cnn_dense_units must be multiples of 4 for the HIP engine")
+        if self.audio_processing not in ("features", "wav"):
+            raise NotImplementedError("audio_processing=%r: 'features' and 'wav' are built" % (self.audio_processing,))
+        if self.audio_units is not None and self.audio_processing == "wav":
+            from .audio_frontend import spec_from_config
+            spec = spec_from_config(self)                  # raises for the refused transformations / sample rates / filter counts
+            if self.audio_feat not in (spec.feat, round4(spec.feat)):
+                raise ValueError("audio_feat must equal num_mel_bins * stacking window (%d) when the waveform front-end produces the "
+                                 "audio features" % spec.feat)
         if self.input_dense_layers[0] > 0 and any(u <= 0 for u in self.input_dense_layers):
             raise ValueError("input_dense_layers must be positive")
         if len(set(self.decoder_units)) != 1 or len(self.decoder_units) > 4:

@@ -44,7 +44,7 @@ def run_experiment_mixedsnrs(video_train_record=None, video_test_record=None, la
                              unit_list_file='./avsr/misc/character_list', iterations=None, learning_rates=None,
                              architecture='unimodal', logfile='tmp_experiment', **kwargs):
     full_logfile = path.join('./logs', logfile)
-    common = dict(unit=unit, unit_file=unit_list_file, audio_processing='features', audio_train_record=audio_train_record,
+    common = dict(unit=unit, unit_file=unit_list_file, audio_processing=kwargs.pop('audio_processing', 'features'), audio_train_record=audio_train_record,
                   audio_test_record=audio_test_record, video_processing=None if architecture == 'unimodal' else 'resnet_cnn',
                   video_train_record=video_train_record, video_test_record=video_test_record, labels_train_record=labels_train_record,
                   labels_test_record=labels_test_record, architecture=architecture, **kwargs)

@@ -403,9 +403,10 @@ def _pad_stack(arrs, T=None):
 
 class _Pipeline:
     """shuffle(5000) -> bucket(group_by_window) -> padded_batch over zipped (data streams..., labels)."""
+    wav = None
 
     def __init__(self, data_records, label_record, unit_dict, batch_size, shuffle, bucket_width, max_sentence_length, seed=None,
-                 rank=0, world=1):
+                 rank=0, world=1, audio_frontend=None):
         # data parallelism by utterance (SURVEY 8(e)): every rank runs the SAME pipeline (same shuffle seed) -- shuffle, bucket
         # (avsr/io_utils.py:133-147: group_by_window on the input length) and batch exactly as one process would -- and then keeps
         # its contiguous share of every bucketed batch.  "Bucket first, then split": the global batches are the reference's.
@@ -415,6 +416,13 @@ class _Pipeline:
         self.data_records, self.label_record = data_records, label_record
         self.eos = {v: k for k, v in unit_dict.items()}["EOS"]
         self.shapes = [_get_input_shape_from_record(r) for r in data_records]
+        # audio_processing='wav' (audio_frontend = the model's audio_frontend.LogmelSpec): the LAST stream holds waveforms, one float per
+        # step.  Buckets and padding then follow the FEATURE length the front-end derives from a sample count, so a waveform record and
+        # the feature record made from it give the same batches in the same order; a batch is padded to the canonical sample count of
+        # its longest feature length (LogmelSpec.samples_for_rows) and comes out as [B, N], lengths in samples.
+        self.wav, self.wav_stream = audio_frontend, len(data_records) - 1
+        if self.wav is not None and self.shapes[self.wav_stream][0] != [1]:
+            raise ValueError("audio_processing='wav' needs a waveform record (input_size == 1): %s" % data_records[self.wav_stream])
         self.batch_size, self.shuffle, self.bucket_width, self.max_len = batch_size, shuffle, bucket_width, max_sentence_length
         self.rng = random.Random(seed)
         self.shuffle_buffer = 5000
@@ -458,7 +466,18 @@ class _Pipeline:
         self._ring_pos[key] = (i + 1) % self.RING
         return slots[i][1][:n].reshape(shape)
 
+    def _wav_rows(self, s):
+        """Feature rows of a waveform stream entry; an utterance too short for one row is an error that names the file."""
+        n = s[0].shape[0] if s[0] is not None else s[2]
+        rows = self.wav.rows(n)
+        if rows < 1:
+            raise ValueError("audio_processing='wav': utterance %r has %d samples, too few for one feature row (%d needed)"
+                             % (bytes(s[3]).decode("utf-8", "replace"), n, self.wav.samples_for_rows(1)))
+        return rows
+
     def _key(self, ex):
+        if self.wav is not None and self.wav_stream == 0:
+            return self._wav_rows(ex[0][0]) // self.bucket_width
         return ex[0][0][2] // self.bucket_width                # first stream's input_length (video for AV)
 
     # Native path (include/avsr_io.h): the records of a chunk are INDEXED by the C helper (value regions, lengths, file names) and the
@@ -551,8 +570,10 @@ class _Pipeline:
         """Zero-padded [n, T, ...] inputs (and Action Units or None) of stream k from its per-utterance entries."""
         shape = tuple(self.shapes[k][0])
         idx = [i for i, s in enumerate(st) if s[0] is None]                    # indexed records: filled by the native helper
+        # (a waveform batch's canonical sample count may cut the last samples of an utterance: fewer than one frame step, part of no row)
+        clip = self.wav is not None and k == self.wav_stream
         if not idx:
-            x = _pad_stack([s[0] for s in st], T)
+            x = _pad_stack([s[0][:T] if clip else s[0] for s in st], T)
             aus = _pad_stack([s[1] for s in st], T) if st[0][1] is not None else None
             return x, aus
         N, F = self.native, self.native.F
@@ -560,13 +581,14 @@ class _Pipeline:
         rows = [s[5] if s[0] is None else None for s in st]
         col = lambda name: [0 if r is None else int(r[F[name]]) for r in rows]
         step = max(col("in_F"))
-        x = N.fill_f32(pls, col("in_off"), col("in_stride"), col("in_T"), step, T, shape, out=self._out_buffer((k, "x"), (len(st), T) + shape))
+        steps = [min(n, T) for n in col("in_T")] if clip else col("in_T")
+        x = N.fill_f32(pls, col("in_off"), col("in_stride"), steps, step, T, shape, out=self._out_buffer((k, "x"), (len(st), T) + shape))
         has_aus = any(r is not None and r[F["aus_T"]] > 0 for r in rows) or any(s[0] is not None and s[1] is not None for s in st)
         aus = N.fill_f32(pls, col("aus_off"), col("aus_stride"), col("aus_T"), 2, T, (2,),
                          out=self._out_buffer((k, "aus"), (len(st), T, 2))) if has_aus else None
         for i, s in enumerate(st):                                              # the few generically parsed ones
             if s[0] is not None:
-                x[i, :s[0].shape[0]] = s[0]
+                x[i, :min(s[0].shape[0], T) if clip else s[0].shape[0]] = s[0][:T] if clip else s[0]
                 if aus is not None and s[1] is not None:
                     aus[i, :s[1].shape[0]] = s[1]
         return x, aus
@@ -602,13 +624,19 @@ class _Pipeline:
         fstreams = list(zip(*[e[0] for e in full]))
         # (an indexed record's frame count is its input_length: the consistency of the two was checked when it was indexed)
         Tmax = [max((s[0].shape[0] if s[0] is not None else s[2]) for s in st) for st in fstreams]
+        if self.wav is not None:
+            Tmax[self.wav_stream] = self.wav.samples_for_rows(max(self._wav_rows(s) for s in fstreams[self.wav_stream]))
         inputs, payload = [], {}
         for k, (st, T) in enumerate(zip(streams, Tmax)):
             x, aus = self._stack_stream(st, k, T)
+            if self.wav is not None and k == self.wav_stream:
+                x = x.reshape(x.shape[0], x.shape[1])           # [B, N, 1] -> [B, N]
             inputs.append(x)
             if aus is not None:
                 payload["aus"] = aus
         lens = [np.array([s[2] for s in st], np.int32) for st in streams]
+        if self.wav is not None:
+            lens[self.wav_stream] = np.minimum(lens[self.wav_stream], Tmax[self.wav_stream])
         names = [[s[3] for s in st] for st in streams]
         labels = self._stack_labels([e[1] for e in exs], Lmax)
         llen = np.array([e[1][1] for e in exs], np.int32)
@@ -641,17 +669,22 @@ class _Pipeline:
 
 
 def make_iterator_from_one_record(data_record, label_record, unit_dict, batch_size, shuffle=False, reverse_input=False,
-                                  bucket_width=-1, num_cores=4, max_sentence_length=None, seed=None, rank=0, world=1):
-    """Iterable of BatchedData (avsr/io_utils.py:88-165).  reverse_input is always False in the reference's callers."""
+                                  bucket_width=-1, num_cores=4, max_sentence_length=None, seed=None, rank=0, world=1,
+                                  audio_frontend=None):
+    """Iterable of BatchedData (avsr/io_utils.py:88-165).  reverse_input is always False in the reference's callers.
+    audio_frontend (audio_frontend.LogmelSpec): the record holds waveforms (audio_processing='wav', see _Pipeline)."""
     if reverse_input:
         raise NotImplementedError("reverse_input is never enabled by the reference (avsr/avsr.py:646, :658, :671)")
-    return _Pipeline([data_record], label_record, unit_dict, batch_size, shuffle, bucket_width, max_sentence_length, seed, rank, world)
+    return _Pipeline([data_record], label_record, unit_dict, batch_size, shuffle, bucket_width, max_sentence_length, seed, rank, world,
+                     audio_frontend)
 
 
 def make_iterator_from_two_records(video_record, audio_record, label_record, batch_size, unit_dict, shuffle=False,
-                                   reverse_input=False, bucket_width=-1, num_cores=4, seed=None, rank=0, world=1):
-    """Iterable of BatchedData with (video, audio) tuples (avsr/io_utils.py:168-259); buckets on the VIDEO length."""
-    return _Pipeline([video_record, audio_record], label_record, unit_dict, batch_size, shuffle, bucket_width, None, seed, rank, world)
+                                   reverse_input=False, bucket_width=-1, num_cores=4, seed=None, rank=0, world=1, audio_frontend=None):
+    """Iterable of BatchedData with (video, audio) tuples (avsr/io_utils.py:168-259); buckets on the VIDEO length.
+    audio_frontend (audio_frontend.LogmelSpec): the audio record holds waveforms (audio_processing='wav', see _Pipeline)."""
+    return _Pipeline([video_record, audio_record], label_record, unit_dict, batch_size, shuffle, bucket_width, None, seed, rank, world,
+                     audio_frontend)
 
 
 class _LabelPipeline(_Pipeline):

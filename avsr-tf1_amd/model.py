@@ -88,6 +88,10 @@ class Seq2SeqModel(EncoderMixin, DecoderMixin):
         self.l2_segments = [(self._train_off[n], int(np.prod(self.inv[n][0]))) for n in self._train_off if PR.is_l2(n)]
         self.cnn_l2_segments = [(self._train_off[n], int(np.prod(self.inv[n][0]))) for n in self._train_off if PR.is_cnn_l2(n)]
         self.use_cnn = cfg.video_units is not None and cfg.video_processing in ("resnet_cnn", "3dconv_cnn")
+        self.audio_fe = None                     # audio_processing='wav': samples -> log-mel features at the top of _encode
+        if cfg.audio_units is not None and cfg.audio_processing == "wav":
+            from .audio_frontend import LogmelFrontend, spec_from_config
+            self.audio_fe = LogmelFrontend(spec_from_config(cfg), device)
         self.dense_l2_segments = [(self._train_off[n], int(np.prod(self.inv[n][0]))) for n in self._train_off if PR.is_dense_l2(n)]
         self.bn_sync = None                       # set by bn_sync_enable() under data parallelism
         self.n_dense = len(cfg.input_dense_layers) if cfg.input_dense_layers[0] > 0 else 0
@@ -219,6 +223,8 @@ class Seq2SeqModel(EncoderMixin, DecoderMixin):
                 E["xpad"] = z(B, T, F)                                # the batch's features, zero columns up to the engine width
             if cfg.instance_normalisation:
                 E["xi"], E["in_mean"], E["in_invstd"], E["in_dg"], E["in_db"] = z(B * T, F), z(B, F), z(B, F), z(B, F), z(B, F)
+            if s == "audio" and self.audio_fe is not None:
+                E["wav_x"], E["wav_len"] = z(B, T, F), torch.zeros(B, dtype=torch.int32, device=dev)   # the front-end's features / row counts
             if s == "video" and self.use_cnn:
                 if cfg.video_processing == "3dconv_cnn":
                     from .cnn3d import LipCNN3D
@@ -297,7 +303,7 @@ class Seq2SeqModel(EncoderMixin, DecoderMixin):
         """Allocate (or fetch) every buffer a train step on a batch of this shape needs, without launching anything.  The data-parallel
         trainer calls it ahead of a shape's first pass so that an out-of-memory surfaces before any collective of the step."""
         B, L = batch.labels.shape
-        Ta = batch.audio.shape[1] if batch.audio is not None else 0
+        Ta = self._audio_rows(batch)
         Tv = batch.video.shape[1] if batch.video is not None else 0
         self._ensure_gemm_ws()
         return self._get_ws(B, Ta, Tv, L, False)
@@ -408,7 +414,7 @@ class Seq2SeqModel(EncoderMixin, DecoderMixin):
         """Train-graph forward: encoders, teacher-forced decoder, logits, loss (stays on device)."""
         cfg = self.cfg
         B, L = batch.labels.shape
-        Ta = batch.audio.shape[1] if batch.audio is not None else 0
+        Ta = self._audio_rows(batch)
         Tv = batch.video.shape[1] if batch.video is not None else 0
         ws = self._get_ws(B, Ta, Tv, L, False)
         self._cur = (ws, batch)

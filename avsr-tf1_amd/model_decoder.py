@@ -398,7 +398,7 @@ class DecoderMixin:
         B = (batch.audio if batch.audio is not None else batch.video if batch.video is not None else batch.labels).shape[0]
         L = cfg.max_label_length if max_steps is None else max_steps
         w = length_penalty_weight if length_penalty_weight is not None else (0.5 if cfg.architecture == "bimodal" else 0.6)
-        Ta = batch.audio.shape[1] if batch.audio is not None else 0
+        Ta = self._audio_rows(batch)
         Tv = batch.video.shape[1] if batch.video is not None else 0
         ws = self._get_ws(B, Ta, Tv, 1, True)                  # encoders at batch B (decoder block of this ws is unused)
         self._refresh_derived()
@@ -492,7 +492,7 @@ class DecoderMixin:
         cfg = self.cfg
         B = (batch.audio if batch.audio is not None else batch.video if batch.video is not None else batch.labels).shape[0]
         L = cfg.max_label_length if max_steps is None else max_steps
-        Ta = batch.audio.shape[1] if batch.audio is not None else 0
+        Ta = self._audio_rows(batch)
         Tv = batch.video.shape[1] if batch.video is not None else 0
         ws = self._get_ws(B, Ta, Tv, L, True)
         self._refresh_derived()

@@ -260,14 +260,31 @@ class EncoderMixin:
             x = E["xpad"]
         return x
 
+    def _audio_rows(self, batch):
+        """T_a of a batch: its feature rows -- with the waveform front-end, the rows its padded sample count gives."""
+        if batch.audio is None:
+            return 0
+        return batch.audio.shape[1] if self.audio_fe is None else self.audio_fe.spec.rows(batch.audio.shape[1])
+
+    def _wav_features(self, E, batch):
+        """audio_processing='wav': batch.audio [B, N] samples, batch.audio_len samples per utterance -> the workspace's [B, T, F]
+        features (zero rows beyond each utterance, zero padding columns) and their row counts, in one launch."""
+        x = batch.audio
+        assert x.dim() == 2 and x.shape[0] == E["wav_x"].shape[0] and self.audio_fe.spec.rows(x.shape[1]) == E["T"], \
+            "audio_processing='wav' takes [B, N] waveforms"
+        self.audio_fe.forward(x, batch.audio_len, E["wav_x"], E["wav_len"])
+        return E["wav_x"], E["wav_len"]
+
     def _bn_sync_x(self, batch, s):
         x = batch.video if s == "video" else batch.audio
         F = self.cfg.feat(s)
-        if x.shape[-1] != F:
+        if (s == "audio" and self.audio_fe is not None) or x.shape[-1] != F:
             B, L = batch.labels.shape
-            ws = self._get_ws(B, batch.audio.shape[1] if batch.audio is not None else 0, batch.video.shape[1] if batch.video is not None else 0,
-                              L, False)
-            x = self._fit_width(ws["enc"][s], x, s)
+            ws = self._get_ws(B, self._audio_rows(batch), batch.video.shape[1] if batch.video is not None else 0, L, False)
+            if s == "audio" and self.audio_fe is not None:
+                x, _ = self._wav_features(ws["enc"][s], batch)    # (computed again in _encode: 76 MB of traffic against a collective)
+            else:
+                x = self._fit_width(ws["enc"][s], x, s)
         assert x.is_contiguous() and x.dtype == torch.float32 and x.shape[-1] == F
         return x, x.shape[0] * x.shape[1], F
 
@@ -331,6 +348,8 @@ class EncoderMixin:
             T, F = E["T"], E["F"]
             x = batch.video if s == "video" else batch.audio
             len_t = batch.video_len if s == "video" else batch.audio_len
+            if s == "audio" and self.audio_fe is not None:             # samples -> the dataset writer's log-mel features
+                x, len_t = self._wav_features(E, batch)
             if "cnn" in E:                                           # avsr/avsr.py:684-696: frames -> visual features
                 Hh, Ww, Cc = cfg.video_hw
                 assert x.shape == (B, T, Hh, Ww, Cc) and x.is_contiguous() and x.dtype == torch.float32

@@ -655,6 +655,20 @@ def conv3d_bwd_weight(d, x, dy, dw, scratch, beta=1.0):
           "avsr_conv3d_bwd_weight")
 
 
+def logmel_supported(frame_length, fft_length, num_mel_bins, window, stride):
+    return bool(_L().avsr_logmel_supported(int(frame_length), int(fft_length), int(num_mel_bins), int(window), int(stride)))
+
+
+def logmel_fwd(spec, tables, wav, wav_len, out, out_len=None):
+    """avsr_logmel_fwd: spec = audio_frontend.LogmelSpec, tables = its device tensors; wav [B, N] -> out [B, T_out, F]."""
+    a = _lib.LogmelArgs(B=wav.shape[0], N=wav.shape[1], T_out=out.shape[1], F=out.shape[2], frame_length=spec.frame_length,
+                        frame_step=spec.frame_step, fft_length=spec.fft_length, num_mel_bins=spec.num_mel_bins, window=spec.window,
+                        stride=spec.stride, mel_nnz=tables["mel_w"].numel(), wav=fptr(wav), wav_len=fptr(wav_len), hann=fptr(tables["hann"]),
+                        twiddle=fptr(tables["twiddle"]), mel_lo=fptr(tables["mel_lo"]), mel_cnt=fptr(tables["mel_cnt"]),
+                        mel_ptr=fptr(tables["mel_ptr"]), mel_w=fptr(tables["mel_w"]), out=fptr(out), out_len=fptr(out_len))
+    check(_L().avsr_logmel_fwd(C.byref(a), _s()), "avsr_logmel_fwd")
+
+
 def conv3d_bn_finalize(part, nparts, Cn, count, eps, momentum, mean, invstd, mov_mean, mov_var, gamma=None, beta=None, scale=None, shift=None):
     """avsr_bn_finalize with the biased moving variance of the non-fused (rank-5) batch norm."""
     check(_L().avsr_conv3d_bn_finalize(fptr(part), int(nparts), int(Cn), int(count), float(eps), float(momentum), fptr(mean), fptr(invstd),

@@ -596,6 +596,33 @@ int avsr_conv3d_bwd_weight(const avsr_conv3d_desc* c, const float* x, const floa
 int avsr_conv3d_bn_finalize(const float* part, int32_t nparts, int32_t C, int64_t count, float eps, float momentum, float* mean,
                             float* invstd, float* mov_mean, float* mov_var, const float* gamma, const float* beta, float* scale,
                             float* shift, void* stream);
+/* ---- waveform audio front-end (avsr/audio.py:7-41 compute_stfts / compute_log_mel_spectrograms, avsr/dataset_writer.py:549-551
+ * _stack_features): wav [B, N] (fp32 samples, wav_len[b] valid ones) -> out [B, T_out, F] in one launch (csrc/audio_frontend.hip).
+ *   frames_b = 1 + (n - frame_length) / frame_step (no pad_end); frame t = wav[frame_step*t ...] * hann, zero-padded to fft_length,
+ *   real FFT, magnitude, mel[m] = sum_c mel_w[mel_ptr[m] + c] * |X[mel_lo[m] + c]| (c < mel_cnt[m]: the non-zero bins of filter m are
+ *   contiguous), log(mel + 1e-6); out row r = frames stride*r .. stride*r + window - 1 side by side, rows_b = (frames_b - window) /
+ *   stride + 1.  Rows >= rows_b and columns >= num_mel_bins*window (F may be wider: the consumer's padded row) are written as zeros;
+ *   out_len[b] = rows_b (may be NULL).  hann [frame_length], twiddle [fft_length] pairs (cos, -sin)(2 pi k / fft_length), mel_w
+ *   [mel_nnz]: computed in fp64 by the caller.  Launches one kernel and nothing else (safe under stream capture).
+ * Covered (avsr_logmel_supported): fft_length == 512 >= frame_length, num_mel_bins <= 128, stride <= window <= 16; otherwise
+ * AVSR_ERR_UNSUPPORTED (-3). */
+typedef struct avsr_logmel_args {
+  int32_t B, N, T_out, F;
+  int32_t frame_length, frame_step, fft_length, num_mel_bins;
+  int32_t window, stride, mel_nnz, pad_;
+  const float* wav;
+  const int32_t* wav_len;
+  const float* hann;
+  const float* twiddle;
+  const int32_t* mel_lo;
+  const int32_t* mel_cnt;
+  const int32_t* mel_ptr;
+  const float* mel_w;
+  float* out;
+  int32_t* out_len;
+} avsr_logmel_args;
+int avsr_logmel_supported(int32_t frame_length, int32_t fft_length, int32_t num_mel_bins, int32_t window, int32_t stride);
+int avsr_logmel_fwd(const avsr_logmel_args* a, void* stream);
 /* y = max(x, 0);  dx = dy * [y > 0];  out = a + b (tf.nn.relu / residual tf.add of video.py) */
 int avsr_relu(const float* x, float* y, int64_t n, void* stream);
 int avsr_relu_bwd(const float* y, const float* dy, float* dx, int64_t n, void* stream);
