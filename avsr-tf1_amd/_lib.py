@@ -134,16 +134,104 @@ _STRUCTS = {"avsr_dec_layer": DecLayer, "avsr_mat": Mat, "avsr_gemm_desc": GemmD
             "avsr_conv_desc": ConvDesc, "avsr_conv3d_desc": Conv3dDesc, "avsr_logmel_args": LogmelArgs, "avsr_attn_mech": AttnMech, "avsr_attn_rnn": AttnRnn, "avsr_transpose_job": TransposeJob,
             "avsr_colsum_job": ColsumJob}
 
-EXPORTS = ["avsr_abi_version", "avsr_sizeof", "avsr_gemm", "avsr_gemm_batch", "avsr_rnn_fwd", "avsr_rnn_bwd", "avsr_rnn_set_persistent", "avsr_rnn_set_persistent_mode", "avsr_rnn_set_persistent_scratch", "avsr_attn_rnn_fwd",
-           "avsr_attn_rnn_fused_ws_floats", "avsr_attn_rnn_fused_eligible", "avsr_attn_rnn_fused_fwd_active", "avsr_attn_rnn_set_fused", "avsr_attn_rnn_set_beam_kernel", "avsr_conv_set_mfma", "avsr_conv_supported", "avsr_conv_fwd", "avsr_conv_bwd_data", "avsr_conv_bwd_weight", "avsr_bn_finalize", "avsr_batchnorm_apply", "avsr_conv_bwd_data_bn", "avsr_conv_bwd_data_bn_supported", "avsr_conv_bwd_weight_bn", "avsr_conv_bwd_weight_bn_supported", "avsr_bn_bwd_finalize", "avsr_bn_bwd_apply", "avsr_bn_bwd_stage1", "avsr_bn_eval_affine", "avsr_bn_partials_f64", "avsr_bn_finalize_f64", "avsr_bn_bwd_finalize_f64",
-           "avsr_conv3d_supported", "avsr_conv3d_wgrad_scratch_floats", "avsr_conv3d_fwd", "avsr_conv3d_bwd_data", "avsr_conv3d_bwd_weight",
-           "avsr_conv3d_bn_finalize", "avsr_logmel_supported", "avsr_logmel_fwd",
-           "avsr_attn_rnn_bwd", "avsr_beam_gather_tree", "avsr_beam_search_step", "avsr_attn_alpha_rows", "avsr_bahdanau_dkeys", "avsr_transpose", "avsr_slab_defer_begin", "avsr_slab_defer_end", "avsr_colsum",
-           "avsr_batchnorm_fwd", "avsr_batchnorm_fwd_ex", "avsr_batchnorm_bwd", "avsr_batchnorm_xhat", "avsr_im2col", "avsr_col2im",
-           "avsr_relu", "avsr_relu_bwd", "avsr_add", "avsr_selu", "avsr_selu_bwd", "avsr_conv3x3_supported", "avsr_conv3x3", "avsr_conv3x3_bwd_data_s2",
-           "avsr_conv3x3_bwd_weight", "avsr_embed_labels", "avsr_embed_grad", "avsr_dropout_rows", "avsr_seq_loss",
-           "avsr_au_loss", "avsr_au_loss_dp", "avsr_normed_v", "avsr_normed_v_bwd", "avsr_reduce_scalar", "avsr_l2_regularise",
-           "avsr_global_norm", "avsr_adam_step", "avsr_adam_step_decay", "avsr_copy_words", "avsr_zero_words", "avsr_zero_multi", "avsr_add_int", "avsr_colsum_multi", "avsr_highway_fwd", "avsr_highway_bwd", "avsr_optimiser_step", "avsr_instnorm_fwd", "avsr_instnorm_bwd", "avsr_seq_loss_fun", "avsr_seq_loss_per_utterance", "avsr_batchnorm_sync_sum", "avsr_batchnorm_sync_sqsum", "avsr_batchnorm_sync_apply", "avsr_batchnorm_sync_moments", "avsr_dp_sync_unpack", "avsr_prof_begin", "avsr_prof_end"]
+_vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+# argument types of every entry point that returns an int status (include/avsr_hip.h)
+_SIGS = {
+    "avsr_gemm": [C.POINTER(GemmDesc), _vp],
+    "avsr_gemm_batch": [C.POINTER(GemmDesc), _i32, _vp],
+    "avsr_rnn_fwd": [C.POINTER(RnnStack), _i32, _vp],
+    "avsr_rnn_bwd": [C.POINTER(RnnStack), _i32, _vp],
+    "avsr_rnn_set_persistent": [_vp, _i64],
+    "avsr_rnn_set_persistent_mode": [_i32],
+    "avsr_rnn_set_persistent_scratch": [_vp, _i64],
+    "avsr_attn_rnn_fwd": [C.POINTER(AttnRnn), _i32, _i32, _vp],
+    "avsr_attn_rnn_fused_eligible": [C.POINTER(AttnRnn)],
+    "avsr_attn_rnn_fused_fwd_active": [C.POINTER(AttnRnn)],
+    "avsr_attn_rnn_set_fused": [_i32],
+    "avsr_attn_rnn_set_beam_kernel": [_i32],
+    "avsr_conv_set_mfma": [_i32],
+    "avsr_conv_supported": [C.POINTER(ConvDesc)],
+    "avsr_conv_fwd": [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i32), _vp],
+    "avsr_conv_bwd_data": [C.POINTER(ConvDesc), _vp, _vp, _vp, _f32, _vp],
+    "avsr_conv_bwd_weight": [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _f32, _vp, _i64, _vp],
+    "avsr_conv_bwd_data_bn": [C.POINTER(ConvDesc), _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i32), _vp],
+    "avsr_conv_bwd_data_bn_supported": [C.POINTER(ConvDesc)],
+    "avsr_conv_bwd_weight_bn": [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _i64, _vp],
+    "avsr_conv_bwd_weight_bn_supported": [C.POINTER(ConvDesc)],
+    "avsr_bn_bwd_finalize": [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp],
+    "avsr_bn_bwd_apply": [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _vp],
+    "avsr_bn_bwd_stage1": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, C.POINTER(_i32), _vp],
+    "avsr_bn_partials_f64": [_vp, _i32, _i32, _vp, _vp],
+    "avsr_bn_finalize_f64": [_vp, _i32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "avsr_bn_bwd_finalize_f64": [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp],
+    "avsr_bn_eval_affine": [_vp, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _vp],
+    "avsr_bn_finalize": [_vp, _i32, _i32, _i64, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "avsr_conv3d_supported": [C.POINTER(Conv3dDesc)],
+    "avsr_conv3d_fwd": [C.POINTER(Conv3dDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i32), _vp],
+    "avsr_conv3d_bwd_data": [C.POINTER(Conv3dDesc), _vp, _vp, _vp, _f32, _vp],
+    "avsr_conv3d_bwd_weight": [C.POINTER(Conv3dDesc), _vp, _vp, _vp, _f32, _vp, _i64, _vp],
+    "avsr_conv3d_bn_finalize": [_vp, _i32, _i32, _i64, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "avsr_logmel_supported": [_i32, _i32, _i32, _i32, _i32],
+    "avsr_logmel_fwd": [C.POINTER(LogmelArgs), _vp],
+    "avsr_batchnorm_apply": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp],
+    "avsr_attn_rnn_bwd": [C.POINTER(AttnRnn), _vp],
+    "avsr_beam_gather_tree": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
+    "avsr_beam_search_step": [_vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp],
+    "avsr_attn_alpha_rows": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp],
+    "avsr_bahdanau_dkeys": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
+    "avsr_transpose": [C.POINTER(TransposeJob), _i32, _vp],
+    "avsr_colsum": [C.POINTER(Mat), C.POINTER(Mat), _i32, _i32, _f32, _f32, _vp, _vp, _i64, _vp],
+    "avsr_batchnorm_fwd": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _vp],
+    "avsr_batchnorm_xhat": [_vp, _vp, _vp, _vp, _i32, _i32, _vp],
+    "avsr_batchnorm_fwd_ex": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _f32, _f32, _i32, _i32, _vp, _i64, _vp],
+    "avsr_batchnorm_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _i64, _vp],
+    "avsr_im2col": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
+    "avsr_col2im": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp],
+    "avsr_relu": [_vp, _vp, _i64, _vp],
+    "avsr_relu_bwd": [_vp, _vp, _vp, _i64, _vp],
+    "avsr_add": [_vp, _vp, _vp, _i64, _vp],
+    "avsr_selu": [_vp, _vp, _i64, _vp],
+    "avsr_selu_bwd": [_vp, _vp, _vp, _i64, _vp],
+    "avsr_conv3x3_supported": [_i32, _i32, _i32, _i32],
+    "avsr_conv3x3": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp],
+    "avsr_conv3x3_bwd_data_s2": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp],
+    "avsr_conv3x3_bwd_weight": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _i64, _vp],
+    "avsr_embed_labels": [_vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
+    "avsr_embed_grad": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp],
+    "avsr_dropout_rows": [C.POINTER(Mat), C.POINTER(Mat), _i32, _i32, _vp, _i32, _f32, _i32, _i32, _i32, _vp],
+    "avsr_seq_loss": [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp],
+    "avsr_seq_loss_fun": [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _vp],
+    "avsr_au_loss": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp],
+    "avsr_au_loss_dp": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp],
+    "avsr_normed_v": [_vp, _vp, _vp, _i32, _vp],
+    "avsr_normed_v_bwd": [_vp, _vp, _vp, _vp, _vp, _i32, _vp],
+    "avsr_reduce_scalar": [_vp, _i32, _vp, _i32, _i32, _f32, _vp],
+    "avsr_l2_regularise": [C.POINTER(_i64), C.POINTER(_i64), _i32, _vp, _vp, _f32, _vp, _vp, _vp],
+    "avsr_global_norm": [_vp, _i64, _f32, _vp, _vp, _vp],
+    "avsr_adam_step": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _f32, _i32, _f32, _f32, _vp],
+    "avsr_batchnorm_sync_sum": [_vp, _i32, _i32, _vp, _vp, _i64, _vp],
+    "avsr_batchnorm_sync_sqsum": [_vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
+    "avsr_batchnorm_sync_apply": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _i32, _vp],
+    "avsr_batchnorm_sync_moments": [_vp, _i32, _i32, _vp, _vp, _i64, _vp],
+    "avsr_dp_sync_unpack": [_vp, _vp, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _vp],
+    "avsr_seq_loss_per_utterance": [_vp, _vp, _vp, _vp, _i32, _i32, _vp],
+    "avsr_instnorm_fwd": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _f32, _vp],
+    "avsr_instnorm_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp],
+    "avsr_optimiser_step": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _f32, _i32, _i32, _f32, _f32, _i32, _f32, _vp],
+    "avsr_highway_fwd": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp],
+    "avsr_highway_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
+    "avsr_copy_words": [_vp, _vp, _i64, _vp],
+    "avsr_zero_words": [_vp, _i64, _vp],
+    "avsr_zero_multi": [C.POINTER(_vp), C.POINTER(_i64), _i32, _vp],
+    "avsr_add_int": [_vp, _i32, _vp, _vp],
+    "avsr_colsum_multi": [C.POINTER(ColsumJob), _i32, _vp, _i64, _vp],
+    "avsr_slab_defer_begin": [], "avsr_slab_defer_end": [_vp],
+    "avsr_adam_step_decay": [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _f32, _i32, _i32, _f32, _f32, _vp],
+    "avsr_prof_begin": [_i32],
+    "avsr_prof_end": [C.POINTER(_i32), C.POINTER(_f32), C.POINTER(C.c_double)],
+}
+# every symbol the library must export: the table above plus the four whose return type load() sets on its own
+EXPORTS = ["avsr_abi_version", "avsr_sizeof", "avsr_attn_rnn_fused_ws_floats", "avsr_conv3d_wgrad_scratch_floats"] + list(_SIGS)
 
 _lib = None
 
@@ -172,106 +260,11 @@ def load():
     for sym in EXPORTS:
         if not hasattr(lib, sym):
             raise AvsrError("libavsr_hip.so does not export %s" % sym)
-    vp, i32, i64, f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
-    sigs = {
-        "avsr_gemm": [C.POINTER(GemmDesc), vp],
-        "avsr_gemm_batch": [C.POINTER(GemmDesc), i32, vp],
-        "avsr_rnn_fwd": [C.POINTER(RnnStack), i32, vp],
-        "avsr_rnn_bwd": [C.POINTER(RnnStack), i32, vp],
-        "avsr_rnn_set_persistent": [vp, i64],
-        "avsr_rnn_set_persistent_mode": [i32],
-        "avsr_rnn_set_persistent_scratch": [vp, i64],
-        "avsr_attn_rnn_fwd": [C.POINTER(AttnRnn), i32, i32, vp],
-        "avsr_attn_rnn_fused_eligible": [C.POINTER(AttnRnn)],
-        "avsr_attn_rnn_fused_fwd_active": [C.POINTER(AttnRnn)],
-        "avsr_attn_rnn_set_fused": [i32],
-        "avsr_attn_rnn_set_beam_kernel": [i32],
-        "avsr_conv_set_mfma": [i32],
-        "avsr_conv_supported": [C.POINTER(ConvDesc)],
-        "avsr_conv_fwd": [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32), vp],
-        "avsr_conv_bwd_data": [C.POINTER(ConvDesc), vp, vp, vp, f32, vp],
-        "avsr_conv_bwd_weight": [C.POINTER(ConvDesc), vp, vp, vp, vp, f32, vp, i64, vp],
-        "avsr_conv_bwd_data_bn": [C.POINTER(ConvDesc), vp, vp, vp, f32, vp, vp, vp, vp, vp, C.POINTER(i32), vp],
-        "avsr_conv_bwd_data_bn_supported": [C.POINTER(ConvDesc)],
-        "avsr_conv_bwd_weight_bn": [C.POINTER(ConvDesc), vp, vp, vp, vp, vp, vp, vp, f32, vp, i64, vp],
-        "avsr_conv_bwd_weight_bn_supported": [C.POINTER(ConvDesc)],
-        "avsr_bn_bwd_finalize": [vp, i32, i32, i64, vp, vp, vp, vp, vp, f32, vp, vp],
-        "avsr_bn_bwd_apply": [vp, vp, vp, vp, i64, i32, f32, vp],
-        "avsr_bn_bwd_stage1": [vp, vp, vp, vp, vp, vp, i64, i32, vp, C.POINTER(i32), vp],
-        "avsr_bn_partials_f64": [vp, i32, i32, vp, vp],
-        "avsr_bn_finalize_f64": [vp, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-        "avsr_bn_bwd_finalize_f64": [vp, vp, i32, vp, vp, vp, vp, vp, f32, vp, vp],
-        "avsr_bn_eval_affine": [vp, vp, vp, vp, f32, vp, vp, i32, vp],
-        "avsr_bn_finalize": [vp, i32, i32, i64, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-        "avsr_conv3d_supported": [C.POINTER(Conv3dDesc)],
-        "avsr_conv3d_fwd": [C.POINTER(Conv3dDesc), vp, vp, vp, vp, vp, vp, vp, C.POINTER(i32), vp],
-        "avsr_conv3d_bwd_data": [C.POINTER(Conv3dDesc), vp, vp, vp, f32, vp],
-        "avsr_conv3d_bwd_weight": [C.POINTER(Conv3dDesc), vp, vp, vp, f32, vp, i64, vp],
-        "avsr_conv3d_bn_finalize": [vp, i32, i32, i64, f32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp],
-        "avsr_logmel_supported": [i32, i32, i32, i32, i32],
-        "avsr_logmel_fwd": [C.POINTER(LogmelArgs), vp],
-        "avsr_batchnorm_apply": [vp, vp, i32, i32, vp, vp, vp, vp, i32, vp],
-        "avsr_attn_rnn_bwd": [C.POINTER(AttnRnn), vp],
-        "avsr_beam_gather_tree": [vp, vp, vp, vp, i32, i32, i32, i32, vp],
-        "avsr_beam_search_step": [vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, i32, vp, vp, vp],
-        "avsr_attn_alpha_rows": [vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
-        "avsr_bahdanau_dkeys": [vp, vp, i64, i64, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
-        "avsr_transpose": [C.POINTER(TransposeJob), i32, vp],
-        "avsr_colsum": [C.POINTER(Mat), C.POINTER(Mat), i32, i32, f32, f32, vp, vp, i64, vp],
-        "avsr_batchnorm_fwd": [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, i64, vp],
-        "avsr_batchnorm_xhat": [vp, vp, vp, vp, i32, i32, vp],
-        "avsr_batchnorm_fwd_ex": [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, i32, f32, f32, i32, i32, vp, i64, vp],
-        "avsr_batchnorm_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, vp, i64, vp],
-        "avsr_im2col": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp],
-        "avsr_col2im": [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp],
-        "avsr_relu": [vp, vp, i64, vp],
-        "avsr_relu_bwd": [vp, vp, vp, i64, vp],
-        "avsr_add": [vp, vp, vp, i64, vp],
-        "avsr_selu": [vp, vp, i64, vp],
-        "avsr_selu_bwd": [vp, vp, vp, i64, vp],
-        "avsr_conv3x3_supported": [i32, i32, i32, i32],
-        "avsr_conv3x3": [vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp],
-        "avsr_conv3x3_bwd_data_s2": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp],
-        "avsr_conv3x3_bwd_weight": [vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, f32, vp, i64, vp],
-        "avsr_embed_labels": [vp, vp, i32, vp, vp, i32, i32, i32, i32, vp],
-        "avsr_embed_grad": [vp, vp, vp, i32, i32, i32, i32, vp, i64, vp],
-        "avsr_dropout_rows": [C.POINTER(Mat), C.POINTER(Mat), i32, i32, vp, i32, f32, i32, i32, i32, vp],
-        "avsr_seq_loss": [vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, vp],
-        "avsr_seq_loss_fun": [vp, vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, f32, vp],
-        "avsr_au_loss": [vp, vp, vp, vp, vp, i32, i32, f32, vp],
-        "avsr_au_loss_dp": [vp, vp, vp, vp, vp, i32, i32, f32, vp, vp],
-        "avsr_normed_v": [vp, vp, vp, i32, vp],
-        "avsr_normed_v_bwd": [vp, vp, vp, vp, vp, i32, vp],
-        "avsr_reduce_scalar": [vp, i32, vp, i32, i32, f32, vp],
-        "avsr_l2_regularise": [C.POINTER(i64), C.POINTER(i64), i32, vp, vp, f32, vp, vp, vp],
-        "avsr_global_norm": [vp, i64, f32, vp, vp, vp],
-        "avsr_adam_step": [vp, vp, vp, vp, i64, vp, vp, f32, i32, f32, f32, vp],
-        "avsr_batchnorm_sync_sum": [vp, i32, i32, vp, vp, i64, vp],
-        "avsr_batchnorm_sync_sqsum": [vp, i32, i32, vp, vp, vp, vp, vp, i64, vp],
-        "avsr_batchnorm_sync_apply": [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, i32, vp],
-        "avsr_batchnorm_sync_moments": [vp, i32, i32, vp, vp, i64, vp],
-        "avsr_dp_sync_unpack": [vp, vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp],
-        "avsr_seq_loss_per_utterance": [vp, vp, vp, vp, i32, i32, vp],
-        "avsr_instnorm_fwd": [vp, vp, i32, i32, i32, vp, vp, vp, vp, f32, vp],
-        "avsr_instnorm_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, vp],
-        "avsr_optimiser_step": [vp, vp, vp, vp, i64, vp, vp, f32, i32, i32, f32, f32, i32, f32, vp],
-        "avsr_highway_fwd": [vp, vp, vp, vp, vp, i32, i32, i32, vp],
-        "avsr_highway_bwd": [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp],
-        "avsr_copy_words": [vp, vp, i64, vp],
-        "avsr_zero_words": [vp, i64, vp],
-        "avsr_zero_multi": [C.POINTER(vp), C.POINTER(i64), i32, vp],
-        "avsr_add_int": [vp, i32, vp, vp],
-        "avsr_colsum_multi": [C.POINTER(ColsumJob), i32, vp, i64, vp],
-        "avsr_slab_defer_begin": [], "avsr_slab_defer_end": [vp],
-        "avsr_adam_step_decay": [vp, vp, vp, vp, i64, vp, vp, f32, i32, i32, f32, f32, vp],
-        "avsr_prof_begin": [i32],
-        "avsr_prof_end": [C.POINTER(i32), C.POINTER(f32), C.POINTER(C.c_double)],
-    }
-    for name, at in sigs.items():
+    for name, at in _SIGS.items():
         fn = getattr(lib, name)
         fn.argtypes = at
         fn.restype = C.c_int
-    lib.avsr_attn_rnn_fused_ws_floats.argtypes = [i32, i32, i32]
+    lib.avsr_attn_rnn_fused_ws_floats.argtypes = [_i32, _i32, _i32]
     lib.avsr_attn_rnn_fused_ws_floats.restype = C.c_int64
     lib.avsr_conv3d_wgrad_scratch_floats.argtypes = [C.POINTER(Conv3dDesc)]
     lib.avsr_conv3d_wgrad_scratch_floats.restype = C.c_int64

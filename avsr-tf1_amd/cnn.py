@@ -13,8 +13,8 @@ the CONSUMING convolution (forward and weight gradient) applies max(x*scale + sh
 gradient kernel also produces the bias gradient.  Shapes those kernels do not cover fall back to the direct VALU kernels
 (avsr_conv3x3*) or to avsr_im2col + avsr_gemm (the TF kernel [kh,kw,cin,cout] IS the [kh*kw*cin, cout] operand; data gradient =
 transposed GEMM + avsr_col2im, weight gradient = split-K TN GEMM), with BN through avsr_batchnorm_fwd_ex / avsr_batchnorm_bwd.
-This file only owns buffers and the op order; all arithmetic is in csrc/conv_mfma.hip, conv_direct.hip, conv.hip, gemm.hip,
-elementwise.hip."""
+This file only owns buffers and the op order; all arithmetic is in csrc/conv_mfma.hip, conv_wgrad.hip, batchnorm.hip, conv_direct.hip,
+conv.hip, gemm.hip, elementwise.hip."""
 import os
 
 import torch
@@ -29,9 +29,10 @@ def same_pad(n, k, s):
     return out, total // 2
 
 
-def layout(hw, filters, dense):
-    """Op list of resnet_cnn.  ('conv', name, src, dst, k, stride, cin, cout) | ('bnrelu', name, src, dst, c) |
-    ('add', name, a, b, dst) | ('flatten', name, src, dst, kh, kw, cin, cout);  shapes[name] = (H, W, C) of every map."""
+def resnet_layout(hw, filters, dense, k_first, k_body, k_short):
+    """Op list and map shapes of the residual network both lip front-ends share (video.py:143-195 resnet_cnn, :198-222 conv3d_cnn), in
+    graph order.  The three kernel tokens (first layer, block body, projection shortcut) go into the conv ops as given: an int k for the
+    2-D network, a (kt, kh, kw) triple for the 3-D one, whose maps are tracked per frame (temporal stride 1, SAME: T is unchanged)."""
     H, W, C = hw
     f = list(filters)
     shapes = {"in": (H, W, C)}
@@ -39,9 +40,8 @@ def layout(hw, filters, dense):
 
     def conv(name, src, dst, k, s, cout):
         h, w, cin = shapes[src]
-        ho, _ = same_pad(h, k, s)
-        wo, _ = same_pad(w, k, s)
-        shapes[dst] = (ho, wo, cout)
+        kh, kw = (k, k) if isinstance(k, int) else k[1:]
+        shapes[dst] = (same_pad(h, kh, s)[0], same_pad(w, kw, s)[0], cout)
         ops_.append(("conv", name, src, dst, k, s, cin, cout))
 
     def bnrelu(name, src, dst):
@@ -52,20 +52,20 @@ def layout(hw, filters, dense):
         shapes[dst] = shapes[a]
         ops_.append(("add", name, a, b, dst))
 
-    conv("layer0", "in", "a0", 3, 1, f[0])
+    conv("layer0", "in", "a0", k_first, 1, f[0])
     bnrelu("layer0_bn", "a0", "b0")
-    conv("res_block_0_conv1", "b0", "r0a", 3, 1, f[0])
+    conv("res_block_0_conv1", "b0", "r0a", k_body, 1, f[0])
     bnrelu("res_block_0_second_bn", "r0a", "r0b")
-    conv("res_block_0_conv2", "r0b", "r0c", 3, 1, f[0])
+    conv("res_block_0_conv2", "r0b", "r0c", k_body, 1, f[0])
     add("res_block_0", "r0c", "b0", "x0")
     prev = "x0"
     for i, c in enumerate(f[1:], start=1):
         n = "res_block_%d" % i
         bnrelu(n + "_first_bn", prev, n + "_p")
-        conv(n + "_shortcut", prev, n + "_s", 1, 2, c)
-        conv(n + "_conv1", n + "_p", n + "_a", 3, 2, c)
+        conv(n + "_shortcut", prev, n + "_s", k_short, 2, c)
+        conv(n + "_conv1", n + "_p", n + "_a", k_body, 2, c)
         bnrelu(n + "_second_bn", n + "_a", n + "_b")
-        conv(n + "_conv2", n + "_b", n + "_c", 3, 1, c)
+        conv(n + "_conv2", n + "_b", n + "_c", k_body, 1, c)
         add(n, n + "_c", n + "_s", "x%d" % i)
         prev = "x%d" % i
     h, w, cin = shapes[prev]
@@ -74,21 +74,38 @@ def layout(hw, filters, dense):
     return ops_, shapes
 
 
-def param_shapes(hw, filters, dense):
-    """[(name, tf_shape, role)] in graph order; role: conv_kernel | bias | gamma | beta | moving_mean | moving_variance."""
+def resnet_param_shapes(ops_, bias):
+    """[(name, tf_shape, role)] of an op list in graph order.  Kernels are [k, k, cin, cout], or [kt, kh, kw, cin, cout] where the conv op
+    carries a triple (the flatten kernel then is [1, kh, kw, cin, cout]); bias: every convolution also has a bias [cout]."""
     out = []
-    for op in layout(hw, filters, dense)[0]:
-        if op[0] == "conv":
-            _, name, _, _, k, _, cin, cout = op
-            out += [(name + "/kernel", (k, k, cin, cout), "conv_kernel"), (name + "/bias", (cout,), "bias")]
-        elif op[0] == "flatten":
-            _, name, _, _, kh, kw, cin, cout = op
-            out += [(name + "/kernel", (kh, kw, cin, cout), "conv_kernel"), (name + "/bias", (cout,), "bias")]
+    triple = not isinstance(ops_[0][4], int)
+    for op in ops_:
+        if op[0] in ("conv", "flatten"):
+            if op[0] == "conv":
+                _, name, _, _, k, _, cin, cout = op
+                ks = tuple(k) if triple else (k, k)
+            else:
+                _, name, _, _, kh, kw, cin, cout = op
+                ks = (1, kh, kw) if triple else (kh, kw)
+            out.append((name + "/kernel", ks + (cin, cout), "conv_kernel"))
+            if bias:
+                out.append((name + "/bias", (cout,), "bias"))
         elif op[0] == "bnrelu":
             c = op[4]
             out += [(op[1] + "/gamma", (c,), "gamma"), (op[1] + "/beta", (c,), "beta"),
                     (op[1] + "/moving_mean", (c,), "moving_mean"), (op[1] + "/moving_variance", (c,), "moving_variance")]
     return out
+
+
+def layout(hw, filters, dense):
+    """Op list of resnet_cnn.  ('conv', name, src, dst, k, stride, cin, cout) | ('bnrelu', name, src, dst, c) |
+    ('add', name, a, b, dst) | ('flatten', name, src, dst, kh, kw, cin, cout);  shapes[name] = (H, W, C) of every map."""
+    return resnet_layout(hw, filters, dense, 3, 3, 1)
+
+
+def param_shapes(hw, filters, dense):
+    """[(name, tf_shape, role)] in graph order; role: conv_kernel | bias | gamma | beta | moving_mean | moving_variance."""
+    return resnet_param_shapes(layout(hw, filters, dense)[0], bias=True)
 
 
 class LipCNN:

@@ -18,67 +18,18 @@ VALID convolution is per frame: one GEMM over the [B*T, H'*W'*C] rows, no bias. 
 import torch
 
 from . import ops
-from .cnn import same_pad
+from .cnn import resnet_layout, resnet_param_shapes, same_pad
 
 
 def layout(hw, filters, dense):
     """Op list of conv3d_cnn in graph order.  ('conv', name, src, dst, (kt, kh, kw), stride, cin, cout) | ('bnrelu', name, src, dst, c) |
     ('add', name, a, b, dst) | ('flatten', name, src, dst, kh, kw, cin, cout);  shapes[name] = (H, W, C) of every map (per frame)."""
-    H, W, C = hw
-    f = list(filters)
-    shapes = {"in": (H, W, C)}
-    ops_ = []
-
-    def conv(name, src, dst, k, s, cout):
-        h, w, cin = shapes[src]
-        shapes[dst] = (same_pad(h, k[1], s)[0], same_pad(w, k[2], s)[0], cout)
-        ops_.append(("conv", name, src, dst, k, s, cin, cout))
-
-    def bnrelu(name, src, dst):
-        shapes[dst] = shapes[src]
-        ops_.append(("bnrelu", name, src, dst, shapes[src][2]))
-
-    def add(name, a, b, dst):
-        shapes[dst] = shapes[a]
-        ops_.append(("add", name, a, b, dst))
-
-    conv("layer0", "in", "a0", (1, 3, 3), 1, f[0])
-    bnrelu("layer0_bn", "a0", "b0")
-    conv("res_block_0_conv1", "b0", "r0a", (3, 3, 3), 1, f[0])
-    bnrelu("res_block_0_second_bn", "r0a", "r0b")
-    conv("res_block_0_conv2", "r0b", "r0c", (3, 3, 3), 1, f[0])
-    add("res_block_0", "r0c", "b0", "x0")
-    prev = "x0"
-    for i, c in enumerate(f[1:], start=1):
-        n = "res_block_%d" % i
-        bnrelu(n + "_first_bn", prev, n + "_p")
-        conv(n + "_shortcut", prev, n + "_s", (1, 1, 1), 2, c)
-        conv(n + "_conv1", n + "_p", n + "_a", (3, 3, 3), 2, c)
-        bnrelu(n + "_second_bn", n + "_a", n + "_b")
-        conv(n + "_conv2", n + "_b", n + "_c", (3, 3, 3), 1, c)
-        add(n, n + "_c", n + "_s", "x%d" % i)
-        prev = "x%d" % i
-    h, w, cin = shapes[prev]
-    shapes["out"] = (1, 1, dense)
-    ops_.append(("flatten", "flatten", prev, "out", h, w, cin, dense))
-    return ops_, shapes
+    return resnet_layout(hw, filters, dense, (1, 3, 3), (3, 3, 3), (1, 1, 1))
 
 
 def param_shapes(hw, filters, dense):
     """[(name, tf_shape, role)] in graph order; role: conv_kernel | gamma | beta | moving_mean | moving_variance (no biases)."""
-    out = []
-    for op in layout(hw, filters, dense)[0]:
-        if op[0] == "conv":
-            _, name, _, _, k, _, cin, cout = op
-            out.append((name + "/kernel", tuple(k) + (cin, cout), "conv_kernel"))
-        elif op[0] == "flatten":
-            _, name, _, _, kh, kw, cin, cout = op
-            out.append((name + "/kernel", (1, kh, kw, cin, cout), "conv_kernel"))
-        elif op[0] == "bnrelu":
-            c = op[4]
-            out += [(op[1] + "/gamma", (c,), "gamma"), (op[1] + "/beta", (c,), "beta"),
-                    (op[1] + "/moving_mean", (c,), "moving_mean"), (op[1] + "/moving_variance", (c,), "moving_variance")]
-    return out
+    return resnet_param_shapes(layout(hw, filters, dense)[0], bias=False)
 
 
 def tf_names(hw, filters, dense):

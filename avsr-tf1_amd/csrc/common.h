@@ -68,6 +68,20 @@ __device__ __forceinline__ float block_max_256(float v, float* red) {
   return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
 }
 
+// Narrow matrices (F < 256): G = 256 / F row sub-groups of F columns share a block of 256 threads; their sums are combined through LDS
+// (red: 256 floats) in group order, so every block emits ONE partial row whatever G is (deterministic).
+__device__ __forceinline__ void block_group_reduce(float s, int idx, int F, int G, float* red, float* out_row) {
+  if (G == 1) { if (idx < F) out_row[idx] = s; return; }
+  if (idx < G * F) red[idx] = s;
+  __syncthreads();
+  if (idx < F) {
+    float t = 0.f;
+    for (int g = 0; g < G; ++g) t += red[g * F + idx];
+    out_row[idx] = t;
+  }
+  __syncthreads();
+}
+
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 
@@ -90,7 +104,11 @@ __global__ static void k_copy_words_2d(uint32_t* d, long dpitch_w, const uint32_
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x)
     d[(i / width_w) * dpitch_w + i % width_w] = s[(i / width_w) * spitch_w + i % width_w];
 }
-static inline int k_blocks(long n) { long b = (n + 255) / 256; return (int)(b < 1 ? 1 : (b > 2048 ? 2048 : b)); }
+static inline int blocks_for(long n, int per = 256, int cap = 2048) {
+  long b = (n + per - 1) / per;
+  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
+}
+static inline int k_blocks(long n) { return blocks_for(n); }
 static inline hipError_t dev_zero(void* p, size_t bytes, hipStream_t s) {
   if (!bytes) return hipSuccess;
   if (bytes % 4 || !p) return hipErrorInvalidValue;

@@ -1,5 +1,5 @@
-// Lip-crop CNN front-end pieces (video.resnet_cnn, avsr/video.py:143-195): NHWC im2col / col2im around the fp32 MFMA GEMM,
-// batch-norm backward (optionally through the ReLU that follows it), ReLU and residual-add helpers.
+// Lip-crop CNN front-end pieces (video.resnet_cnn, avsr/video.py:143-195): NHWC im2col / col2im around the fp32 MFMA GEMM for the shapes
+// the frame-resident kernels do not cover, ReLU / SELU and residual-add helpers, instance norm.  (Batch norm: batchnorm.hip.)
 //
 // Convolutions are lowered to GEMMs: col[(n,ho,wo)][(i,j,c)] = x[n, ho*s - pad_t + i, wo*s - pad_l + j, c] (zero outside)
 // times the TF kernel [kh, kw, cin, cout] read as a [kh*kw*cin, cout] matrix (HWIO is already that matrix, row-major).
@@ -55,113 +55,6 @@ __global__ void col2im_kernel(const float* dcol, float* dx, int N, int H, int W,
   }
 }
 
-// ---- batch-norm backward (training statistics), optionally through a following ReLU -------------------------------
-// dy' = dy * [bn(x) > 0] (relu) ;  d beta = sum dy' ;  d gamma = sum dy' * xhat ;
-// dx = gamma * invstd * (dy' - (sum dy' + xhat * sum dy' xhat) / rows)
-__global__ void bn_bwd_partial_kernel(const float* x, const float* dy, const float* gamma, const float* beta, const float* mean,
-                                      const float* invstd, float* part, int rows, int F, int rows_per_blk, int relu) {
-  __shared__ float red[512];
-  const int G = F < 256 ? 256 / F : 1;
-  const int r0 = blockIdx.x * rows_per_blk, r1 = min(rows, r0 + rows_per_blk);
-  float* prow = part + (long)blockIdx.x * 2 * F;
-  for (int base = 0; base < (G > 1 ? 1 : F); base += blockDim.x) {      // G > 1: a single pass (G*F <= 256)
-    const int idx = base + threadIdx.x;
-    const bool on = G > 1 ? idx < G * F : idx < F;
-    const int f = G > 1 ? idx % F : idx, g = G > 1 ? idx / F : 0;
-    float s1 = 0.f, s2 = 0.f;
-    if (on) {
-      const float m = mean[f], is = invstd[f], ga = gamma[f], be = beta[f];
-      for (int r = r0 + g; r < r1; r += G) {
-        const float xh = (x[(long)r * F + f] - m) * is;
-        float d = dy[(long)r * F + f];
-        if (relu && !(xh * ga + be > 0.f)) d = 0.f;
-        s1 += d;
-        s2 += d * xh;
-      }
-    }
-    if (G > 1) {                                     // sub-groups combined through LDS in group order: one partial row per block
-      if (on) { red[idx] = s1; red[256 + idx] = s2; }
-      __syncthreads();
-      if (idx < F) {
-        float t1 = 0.f, t2 = 0.f;
-        for (int gg = 0; gg < G; ++gg) { t1 += red[gg * F + idx]; t2 += red[256 + gg * F + idx]; }
-        prow[idx] = t1; prow[F + idx] = t2;
-      }
-    } else if (on) { prow[f] = s1; prow[F + f] = s2; }
-  }
-}
-
-__global__ void bn_bwd_apply_kernel(const float* x, const float* dy, const float* gamma, const float* beta, const float* mean,
-                                    const float* invstd, const float* sum1, const float* sum2, float* dx, long n, int rows, int F, int relu,
-                                    float dx_beta) {
-  const float inv_rows = 1.0f / (float)rows;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const int f = (int)(i % F);
-    const float is = invstd[f], ga = gamma[f];
-    const float xh = (x[i] - mean[f]) * is;
-    float d = dy[i];
-    if (relu && !(xh * ga + beta[f] > 0.f)) d = 0.f;
-    const float v = ga * is * (d - (sum1[f] + xh * sum2[f]) * inv_rows);
-    dx[i] = dx_beta != 0.f ? v + dx_beta * dx[i] : v;
-  }
-}
-
-// 16-byte versions for F | 1024 (every channel count of the lip CNN): a thread owns FOUR fixed channels -- the grid stride (1024 floats
-// per block) is a multiple of F -- so the per-channel constants are loaded once and there is no per-element modulo.
-// (The scalar kernels above spent a 64-bit modulo and six table loads per element: 4 TB/s on 600 MB maps.)
-__global__ __launch_bounds__(256) void bn_bwd_partial4_kernel(const float* x, const float* dy, const float* gamma, const float* beta,
-                                                               const float* mean, const float* invstd, float* part, long n4, int F, int relu) {
-  __shared__ f32x4 red[2][256];
-  const int f = (int)((threadIdx.x * 4) % F);
-  const f32x4 m = ld4(mean + f), is = ld4(invstd + f), ga = ld4(gamma + f), be = ld4(beta + f);
-  f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = s1;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-    const f32x4 xv = ld4(x + i * 4), dv = ld4(dy + i * 4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float xh = (xv[e] - m[e]) * is[e];
-      float d = dv[e];
-      if (relu && !(xh * ga[e] + be[e] > 0.f)) d = 0.f;
-      s1[e] += d;
-      s2[e] += d * xh;
-    }
-  }
-  red[0][threadIdx.x] = s1; red[1][threadIdx.x] = s2;
-  __syncthreads();
-  const int tpf = F >> 2;                               // threads per channel period
-  if ((int)threadIdx.x < tpf) {                         // threads t, t + tpf, t + 2 tpf, ... own the same four channels
-    f32x4 t1 = {0.f, 0.f, 0.f, 0.f}, t2 = t1;
-    for (int k = threadIdx.x; k < 256; k += tpf) { t1 += red[0][k]; t2 += red[1][k]; }
-    st4(part + (long)blockIdx.x * 2 * F + 4 * threadIdx.x, t1);
-    st4(part + (long)blockIdx.x * 2 * F + F + 4 * threadIdx.x, t2);
-  }
-}
-
-__global__ __launch_bounds__(256) void bn_bwd_apply4_kernel(const float* x, const float* dy, const float* gamma, const float* beta,
-                                                             const float* mean, const float* invstd, const float* sum1, const float* sum2, float* dx,
-                                                             long n4, int rows, int F, int relu, float dx_beta) {
-  const int f = (int)((threadIdx.x * 4) % F);
-  const float inv_rows = 1.0f / (float)rows;
-  const f32x4 m = ld4(mean + f), is = ld4(invstd + f), ga = ld4(gamma + f), be = ld4(beta + f);
-  f32x4 c1 = ld4(sum1 + f), c2 = ld4(sum2 + f);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { c1[e] *= inv_rows; c2[e] *= inv_rows; }
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
-    const f32x4 xv = ld4(x + i * 4), dv = ld4(dy + i * 4);
-    f32x4 o;
-    if (dx_beta != 0.f) o = ld4(dx + i * 4);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float xh = (xv[e] - m[e]) * is[e];
-      float d = dv[e];
-      if (relu && !(xh * ga[e] + be[e] > 0.f)) d = 0.f;
-      const float v = ga[e] * is[e] * (d - (c1[e] + xh * c2[e]));
-      o[e] = dx_beta != 0.f ? v + dx_beta * o[e] : v;
-    }
-    st4(dx + i * 4, o);
-  }
-}
-
 __global__ void relu_kernel(const float* x, float* y, long n) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) y[i] = fmaxf(x[i], 0.f);
 }
@@ -197,11 +90,6 @@ static inline int blocks_for_n(long n) {
 
 }  // namespace avsr
 
-// out[f] = alpha * sum_i part[i][f] + beta * out[f]  (elementwise.hip)
-int avsr_colsum_final_launch(const float* part, int nblk, float* out, int F, float alpha, float beta, void* stream);
-int avsr_colsum_final_launch_split(const float* part, long ld, int nblk, float* out, float* out2, int split, int F, float alpha, float beta,
-                                   void* stream);
-
 using namespace avsr;
 #define S_(x) ((hipStream_t)(x))
 
@@ -220,60 +108,6 @@ extern "C" int avsr_col2im(const float* dcol, float* dx, int32_t N, int32_t H, i
   hipLaunchKernelGGL(col2im_kernel, dim3(blocks_for_n((long)N * H * W * C)), dim3(256), 0, S_(stream), dcol, dx, N, H, W, C, kh, kw,
                      stride, pad_t, pad_l, Ho, Wo, beta);
   AVSR_CHECK_LAUNCH();
-  return AVSR_OK;
-}
-
-extern "C" int avsr_batchnorm_bwd(const float* x, const float* dy, const float* gamma, const float* beta, const float* mean,
-                                  const float* invstd, float* dx, float* dgamma, float* dbeta, int32_t rows, int32_t F, int32_t relu,
-                                  float dx_beta, float* scratch, int64_t scratch_floats, void* stream) {
-  if (!x || !dy || !gamma || !beta || !mean || !invstd || !scratch || rows <= 0 || F <= 0) return AVSR_ERR_ARG;
-  const int maxblk = 2048;
-  int rpb = rows > 64 * maxblk ? (rows + maxblk - 1) / maxblk : 64;
-  int nblk = (rows + rpb - 1) / rpb;
-  if ((long)nblk * 2 * F + 2 * F > scratch_floats) {
-    nblk = (int)((scratch_floats - 2 * F) / (2L * F));
-    if (nblk < 1) return AVSR_ERR_ARG;
-    rpb = (rows + nblk - 1) / nblk;
-    nblk = (rows + rpb - 1) / rpb;
-  }
-  float* part = scratch;
-  const long n = (long)rows * F;
-  auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-  const bool vec = F >= 4 && 1024 % F == 0 && al16(x) && al16(dy) && (!dx || al16(dx)) && al16(gamma) && al16(beta) && al16(mean) && al16(invstd) &&
-                   al16(scratch) && rows >= 4096;
-  if (vec) {
-    int vb = (int)((n / 4 + 255) / 256);
-    if (vb > 1024) vb = 1024;
-    if ((long)vb * 2 * F + 2 * F > scratch_floats) vb = (int)((scratch_floats - 2 * F) / (2L * F));
-    if (vb < 1) return AVSR_ERR_ARG;
-    nblk = vb;
-  }
-  float* sums = scratch + (long)nblk * 2 * F;          // [2F]: sum dy' | sum dy' xhat
-  if (vec) hipLaunchKernelGGL(bn_bwd_partial4_kernel, dim3(nblk), dim3(256), 0, S_(stream), x, dy, gamma, beta, mean, invstd, part, n / 4, F, relu);
-  else hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(nblk), dim3(256), 0, S_(stream), x, dy, gamma, beta, mean, invstd, part, rows, F, rpb, relu);
-  AVSR_CHECK_LAUNCH();
-  // the reduced sums ARE d beta | d gamma: one reduction launch writes them where the caller wants them and the apply pass reads
-  // them from there (16-byte aligned destinations for the vector kernel; else through the scratch + two copies)
-  const bool direct = dbeta && dgamma && al16(dbeta) && al16(dgamma);
-  float* const s1 = direct ? dbeta : sums;
-  float* const s2 = direct ? dgamma : sums + F;
-  { const int rc = avsr_colsum_final_launch_split(part, 2L * F, nblk, s1, s2, F, 2 * F, 1.0f, 0.0f, stream); if (rc) return rc; }
-  if (dx) {
-    if (vec) {
-      int ab = (int)((n / 4 + 255) / 256);
-      if (ab > 4096) ab = 4096;
-      hipLaunchKernelGGL(bn_bwd_apply4_kernel, dim3(ab), dim3(256), 0, S_(stream), x, dy, gamma, beta, mean, invstd, s1, s2, dx, n / 4, rows, F, relu,
-                         dx_beta);
-    } else {
-      hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(blocks_for_n(n)), dim3(256), 0, S_(stream), x, dy, gamma, beta, mean, invstd, s1, s2, dx, n, rows,
-                         F, relu, dx_beta);
-    }
-    AVSR_CHECK_LAUNCH();
-  }
-  if (!direct) {
-    if (dbeta && avsr::dev_copy(dbeta, sums, sizeof(float) * F, S_(stream)) != hipSuccess) return AVSR_ERR_HIP;
-    if (dgamma && avsr::dev_copy(dgamma, sums + F, sizeof(float) * F, S_(stream)) != hipSuccess) return AVSR_ERR_HIP;
-  }
   return AVSR_OK;
 }
 

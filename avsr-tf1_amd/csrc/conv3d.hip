@@ -310,37 +310,6 @@ __global__ void c3_slab_sum_kernel(const float* part, int nsplit, long n, float*
   out[i] = beta != 0.f ? beta * out[i] + s : s;
 }
 
-// statistics of the non-fused batch norm (rank-5 input: TF 1.13 drops fused=True): the moving variance takes the BIASED variance
-__global__ __launch_bounds__(1024) void c3_bn_finalize_kernel(const float* part, int nparts, int C, double count, float eps, float momentum,
-                                                             float* mean, float* invstd, float* mov_mean, float* mov_var, const float* gamma,
-                                                             const float* beta, float* scale, float* shift) {
-  __shared__ double red[2][64][17];
-  const int cl = threadIdx.x & 15, rg = threadIdx.x >> 4, c = blockIdx.x * 16 + cl;
-  double s = 0.0, s2 = 0.0;
-  if (c < C)
-    for (int p = rg; p < nparts; p += 64) { s += (double)part[(long)p * 2 * C + c]; s2 += (double)part[(long)p * 2 * C + C + c]; }
-  red[0][rg][cl] = s; red[1][rg][cl] = s2;
-  __syncthreads();
-  if (threadIdx.x >= 16 || c >= C) return;
-  s = 0.0; s2 = 0.0;
-  for (int r = 0; r < 64; ++r) { s += red[0][r][cl]; s2 += red[1][r][cl]; }
-  const double m = s / count;
-  double var = s2 / count - m * m;
-  if (var < 0.0) var = 0.0;
-  const float is = rsqrtf((float)var + eps);
-  mean[c] = (float)m;
-  invstd[c] = is;
-  if (scale) {
-    const float sc = gamma[c] * is;
-    scale[c] = sc;
-    shift[c] = beta[c] - (float)m * sc;
-  }
-  if (mov_mean) {
-    mov_mean[c] = momentum * mov_mean[c] + (1.f - momentum) * (float)m;
-    mov_var[c] = momentum * mov_var[c] + (1.f - momentum) * (float)var;
-  }
-}
-
 bool desc_ok(const avsr_conv3d_desc* c) {
   if (!c || c->B <= 0 || c->T <= 0 || c->H <= 0 || c->W <= 0 || c->Ci <= 0 || c->Co <= 0) return false;
   if (c->kt < 1 || c->kt > 3 || c->kh < 1 || c->kh > 3 || c->kw < 1 || c->kw > 3) return false;
@@ -460,15 +429,5 @@ extern "C" int avsr_conv3d_bwd_weight(const avsr_conv3d_desc* c, const float* x,
   if (hipGetLastError() != hipSuccess) return AVSR_ERR_HIP;
   const long n = (long)M * c->Co;
   hipLaunchKernelGGL(c3_slab_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, S_(stream), scratch, (int)sp, n, dw, beta);
-  return hipGetLastError() == hipSuccess ? AVSR_OK : AVSR_ERR_HIP;
-}
-
-extern "C" int avsr_conv3d_bn_finalize(const float* part, int32_t nparts, int32_t C, int64_t count, float eps, float momentum, float* mean,
-                                       float* invstd, float* mov_mean, float* mov_var, const float* gamma, const float* beta, float* scale,
-                                       float* shift, void* stream) {
-  if (!part || nparts <= 0 || C <= 0 || count <= 0 || !mean || !invstd || (scale && (!gamma || !beta || !shift)) || (!mov_mean != !mov_var))
-    return AVSR_ERR_ARG;
-  hipLaunchKernelGGL(c3_bn_finalize_kernel, dim3((C + 15) / 16), dim3(1024), 0, S_(stream), part, nparts, C, (double)count, eps, momentum, mean,
-                     invstd, mov_mean, mov_var, gamma, beta, scale, shift);
   return hipGetLastError() == hipSuccess ? AVSR_OK : AVSR_ERR_HIP;
 }

@@ -1,5 +1,5 @@
 // Shared declarations of the frame-resident MFMA convolutions (conv_mfma.hip: the data-path kernels, forward and data gradients;
-// conv_wgrad.hip: the weight gradient; conv_bn.hip: the batch-norm kernels around them).  Round 6 split one 2 156-line file along these lines.
+// conv_wgrad.hip: the weight gradient; batchnorm.hip: the batch-norm kernels around them).  Round 6 split one 2 156-line file along these lines.
 #pragma once
 #include "common.h"
 #include "persist.h"

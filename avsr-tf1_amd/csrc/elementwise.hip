@@ -1,4 +1,4 @@
-// Memory-bound helper kernels of the train step: weight transposes, batch-norm, column reductions,
+// Memory-bound helper kernels of the train step: weight transposes, column reductions,
 // embedding lookup / gradient, masked sequence cross-entropy, AU regression loss, L2 + global-norm
 // clip + Adam.  All are single-pass, 16-byte vectorised where the layout allows, and deterministic
 // (two-stage reductions, no float atomics).
@@ -37,20 +37,6 @@ __global__ void transpose_kernel(const TLaunch L) {
 // two-level row addressing on a and b (same convention as avsr_gemm)
 __device__ __forceinline__ long rowoff(int r, long ld, int T, long ldo) {
   return T ? (long)(r / T) * ldo + (long)(r % T) * ld : (long)r * ld;
-}
-
-// Narrow matrices (F < 256): G = 256 / F row sub-groups of F columns share a block; their sums are combined through LDS in
-// group order, so every block emits ONE partial row whatever G is (deterministic).
-__device__ __forceinline__ void block_group_reduce(float s, int idx, int F, int G, float* red, float* out_row) {
-  if (G == 1) { if (idx < F) out_row[idx] = s; return; }
-  if (idx < G * F) red[idx] = s;
-  __syncthreads();
-  if (idx < F) {
-    float t = 0.f;
-    for (int g = 0; g < G; ++g) t += red[g * F + idx];
-    out_row[idx] = t;
-  }
-  __syncthreads();
 }
 
 __global__ void colsum_partial_kernel(const float* a, long lda, int Ta, long ldoa, const float* b, long ldb, int Tb,
@@ -105,128 +91,6 @@ __global__ __launch_bounds__(1024) void colsum_final_kernel(const float* part, l
     const float v = alpha * (float)t;
     float* const o = f < split ? out + f : out2 + (f - split);
     *o = beta != 0.f ? v + beta * *o : v;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// batch norm over rows (tf.layers.batch_normalization axis=-1, encoder.py:44-50): statistics over ALL
-// B*T rows including zero padding.  Stage 1: partial sums.  Stage 2: partial centred squares.  Stage 3:
-// normalise (+ moving-average update and saved mean / inv-std by block 0).
-// Thread layout of the row-walking BN kernels: G = 256 / F row sub-groups of F columns (F < 256), so narrow feature
-// vectors (80 audio / 128 video) still use the whole block; partials are per (block, sub-group).
-__global__ void bn_partial_sum_kernel(const float* x, float* part, int rows, int F, int rows_per_blk) {
-  __shared__ float red[256];
-  const int G = F < 256 ? 256 / F : 1;
-  const int r0 = blockIdx.x * rows_per_blk, r1 = min(rows, r0 + rows_per_blk);
-  for (int base = 0; base < (G > 1 ? 1 : F); base += blockDim.x) {      // G > 1: a single pass (G*F <= 256)
-    const int idx = base + threadIdx.x;
-    const int f = G > 1 ? idx % F : idx, g = G > 1 ? idx / F : 0;
-    float s0 = 0.f, s1 = 0.f;
-    if (G > 1 ? idx < G * F : idx < F) {
-      int r = r0 + g;
-      for (; r + G < r1; r += 2 * G) { s0 += x[(long)r * F + f]; s1 += x[(long)(r + G) * F + f]; }
-      if (r < r1) s0 += x[(long)r * F + f];
-    }
-    if (G > 1) block_group_reduce(s0 + s1, idx, F, G, red, part + (long)blockIdx.x * F);
-    else if (idx < F) part[(long)blockIdx.x * F + idx] = s0 + s1;
-  }
-}
-
-// mean[f] = sum of partials / rows   (one launch, one block per 32 columns; npart = nblk * G)
-// total != nullptr: the divisor is the (all-reduced) row count total[0] instead of `rows` (sync batch-norm).
-__global__ __launch_bounds__(1024) void bn_mean_kernel(const float* part, int npart, float* mean, int rows, int F,
-                                                       const float* total = nullptr) {
-  if (total) rows = (int)total[0];
-  __shared__ double red[32][33];
-  const int fl = threadIdx.x & 31, g = threadIdx.x >> 5;
-  const int f = blockIdx.x * 32 + fl;
-  double s = 0.0;
-  if (f < F)
-    for (int i = g; i < npart; i += 32) s += (double)part[(long)i * F + f];
-  red[g][fl] = s;
-  __syncthreads();
-  if (g == 0 && f < F) {
-    double t = 0.0;
-#pragma unroll
-    for (int j = 0; j < 32; ++j) t += red[j][fl];
-    mean[f] = (float)(t / rows);
-  }
-}
-
-__global__ void bn_partial_sq_kernel(const float* x, const float* mean_v, float* part, int rows, int F, int rows_per_blk) {
-  __shared__ float red[256];
-  const int G = F < 256 ? 256 / F : 1;
-  const int r0 = blockIdx.x * rows_per_blk, r1 = min(rows, r0 + rows_per_blk);
-  for (int base = 0; base < (G > 1 ? 1 : F); base += blockDim.x) {
-    const int idx = base + threadIdx.x;
-    const int f = G > 1 ? idx % F : idx, g = G > 1 ? idx / F : 0;
-    float s0 = 0.f, s1 = 0.f;
-    if (G > 1 ? idx < G * F : idx < F) {
-      const float mean = mean_v[f];
-      int r = r0 + g;
-      for (; r + G < r1; r += 2 * G) {
-        const float d0 = x[(long)r * F + f] - mean, d1 = x[(long)(r + G) * F + f] - mean;
-        s0 += d0 * d0; s1 += d1 * d1;
-      }
-      if (r < r1) { const float d0 = x[(long)r * F + f] - mean; s0 += d0 * d0; }
-    }
-    if (G > 1) block_group_reduce(s0 + s1, idx, F, G, red, part + (long)blockIdx.x * F);
-    else if (idx < F) part[(long)blockIdx.x * F + idx] = s0 + s1;
-  }
-}
-
-// var from the centred-square partials, inverse std, moving-average update (one launch, one block per 32 columns)
-__global__ __launch_bounds__(1024) void bn_var_kernel(const float* part, int npart, const float* mean_v, float* invstd_v, float* mov_mean,
-                                                      float* mov_var, int rows, int F, float eps, float momentum,
-                                                      int bessel, const float* total = nullptr) {
-  if (total) rows = (int)total[0];
-  __shared__ double red[32][33];
-  const int fl = threadIdx.x & 31, g = threadIdx.x >> 5;
-  const int f = blockIdx.x * 32 + fl;
-  double s = 0.0;
-  if (f < F)
-    for (int i = g; i < npart; i += 32) s += (double)part[(long)i * F + f];
-  red[g][fl] = s;
-  __syncthreads();
-  if (g == 0 && f < F) {
-    double t = 0.0;
-#pragma unroll
-    for (int j = 0; j < 32; ++j) t += red[j][fl];
-    const float var = (float)(t / rows), mean = mean_v[f];
-    invstd_v[f] = rsqrtf(var + eps);
-    if (mov_mean) {
-      // bessel = 1: the fused kernel (rank-4 CNN maps) feeds the Bessel-corrected variance to the moving average;
-      // 0: the non-fused path TF 1.13 takes for the rank-3 [B,T,F] encoder input feeds the biased tf.nn.moments variance
-      const float unbiased = bessel ? var * ((float)rows / (float)max(1, rows - 1)) : var;
-      mov_mean[f] = momentum * mov_mean[f] + (1.f - momentum) * mean;
-      mov_var[f] = momentum * mov_var[f] + (1.f - momentum) * unbiased;
-    }
-  }
-}
-
-// y = (x - mean) * invstd * gamma + beta, flat over rows * F (F % 4 == 0: one float4 per thread-iteration)
-__global__ void bn_apply_kernel(const float* x, const float* mean_v, const float* invstd_v, const float* mov_mean, const float* mov_var,
-                                const float* gamma, const float* beta, float* y, long n4, int F, int training, float eps, int relu) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-    const int f = (int)((i * 4) % F);
-    const f32x4 xv = ld4(x + i * 4);
-    f32x4 yv;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float mean = training ? mean_v[f + e] : mov_mean[f + e];
-      const float istd = training ? invstd_v[f + e] : rsqrtf(mov_var[f + e] + eps);
-      yv[e] = (xv[e] - mean) * (gamma[f + e] * istd) + beta[f + e];
-      if (relu) yv[e] = fmaxf(yv[e], 0.f);
-    }
-    st4(y + i * 4, yv);
-  }
-}
-
-// xhat[r][f] = (x - mean) * invstd  (for d gamma = sum dy * xhat)
-__global__ void bn_xhat_kernel(const float* x, const float* mean, const float* invstd, float* xhat, long n, int F) {
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const int f = (int)(i % F);
-    xhat[i] = (x[i] - mean[f]) * invstd[f];
   }
 }
 
@@ -548,11 +412,6 @@ __global__ void highway_bwd_kernel(HwView x, HwView h, HwView cpre, HwView dy, H
     float* px = dx.p + hw_off(dx, r) + c;
     *px = accumulate_dx ? *px + vdx : vdx;
   }
-}
-
-static inline int blocks_for(long n, int per = 256, int cap = 2048) {
-  long b = (n + per - 1) / per;
-  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
 }
 
 }  // namespace avsr
@@ -889,149 +748,7 @@ extern "C" int avsr_colsum(const avsr_mat* a, const avsr_mat* b, int32_t rows, i
   return AVSR_OK;
 }
 
-extern "C" int avsr_batchnorm_fwd_ex(const float* x, float* y, int32_t rows, int32_t F, const float* gamma, const float* beta,
-                                     float* moving_mean, float* moving_var, float* save_mean, float* save_invstd, int32_t training,
-                                     float eps, float momentum, int32_t relu, int32_t bessel, float* scratch, int64_t scratch_floats, void* stream);
-
-extern "C" int avsr_batchnorm_fwd(const float* x, float* y, int32_t rows, int32_t F, const float* gamma,
-                                  const float* beta, float* moving_mean, float* moving_var, float* save_mean,
-                                  float* save_invstd, int32_t training, float* scratch, int64_t scratch_floats,
-                                  void* stream) {
-  return avsr_batchnorm_fwd_ex(x, y, rows, F, gamma, beta, moving_mean, moving_var, save_mean, save_invstd, training, 1e-3f, 0.99f, 0,
-                               0 /* rank-3 input: non-fused path, biased moving variance */, scratch, scratch_floats, stream);
-}
-
-extern "C" int avsr_batchnorm_fwd_ex(const float* x, float* y, int32_t rows, int32_t F, const float* gamma, const float* beta,
-                                     float* moving_mean, float* moving_var, float* save_mean, float* save_invstd, int32_t training,
-                                     float eps, float momentum, int32_t relu, int32_t bessel, float* scratch, int64_t scratch_floats, void* stream) {
-  if (!x || !y || !gamma || !beta || rows <= 0 || F <= 0 || !scratch) return AVSR_ERR_ARG;
-  if (F % 4) return AVSR_ERR_ARG;
-  const int maxblk = 2048;
-  int rpb = rows > 64 * maxblk ? (rows + maxblk - 1) / maxblk : 64;
-  int nblk = (rows + rpb - 1) / rpb;
-  if ((long)nblk * F + 2 * F > scratch_floats) {
-    nblk = (int)((scratch_floats - 2 * F) / F);
-    if (nblk < 1) return AVSR_ERR_ARG;
-    rpb = (rows + nblk - 1) / nblk;
-    nblk = (rows + rpb - 1) / rpb;
-  }
-  // scratch: partials [nblk][F] | mean [F] | invstd [F]  (mean / invstd go to save_mean / save_invstd when given)
-  float* part = scratch;
-  float* mean_v = save_mean ? save_mean : scratch + (long)nblk * F;
-  float* invstd_v = save_invstd ? save_invstd : scratch + (long)nblk * F + F;
-  if (training) {
-    hipLaunchKernelGGL(bn_partial_sum_kernel, dim3(nblk), dim3(256), 0, S_(stream), x, part, rows, F, rpb);
-    AVSR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(bn_mean_kernel, dim3((F + 31) / 32), dim3(1024), 0, S_(stream), part, nblk, mean_v, rows, F);
-    AVSR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(bn_partial_sq_kernel, dim3(nblk), dim3(256), 0, S_(stream), x, mean_v, part, rows, F, rpb);
-    AVSR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(bn_var_kernel, dim3((F + 31) / 32), dim3(1024), 0, S_(stream), part, nblk, mean_v, invstd_v, moving_mean,
-                       moving_var, rows, F, eps, momentum, bessel);
-    AVSR_CHECK_LAUNCH();
-  } else if (!moving_mean || !moving_var) {
-    return AVSR_ERR_ARG;
-  }
-  const long n4 = (long)rows * F / 4;
-  int blocks = (int)((n4 + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(bn_apply_kernel, dim3(blocks), dim3(256), 0, S_(stream), x, mean_v, invstd_v, moving_mean, moving_var, gamma, beta, y,
-                     n4, F, training, eps, relu);
-  AVSR_CHECK_LAUNCH();
-  return AVSR_OK;
-}
-
-extern "C" int avsr_batchnorm_apply(const float* x, float* y, int32_t rows, int32_t F, const float* gamma, const float* beta, const float* mean,
-                                    const float* invstd, int32_t relu, void* stream) {
-  if (!x || !y || !gamma || !beta || !mean || !invstd || rows <= 0 || F <= 0 || F % 4) return AVSR_ERR_ARG;
-  const long n4 = (long)rows * F / 4;
-  int blocks = (int)((n4 + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(bn_apply_kernel, dim3(blocks), dim3(256), 0, S_(stream), x, mean, invstd, nullptr, nullptr, gamma, beta, y, n4, F, 1, 0.f, relu);
-  AVSR_CHECK_LAUNCH();
-  return AVSR_OK;
-}
-
-// ---- sync batch-norm over data-parallel ranks: the three local phases around the two host-side all-reduces ----
-static int bn_blocks(int rows, int F, int64_t scratch_floats, int* rpb_out) {
-  const int maxblk = 2048;
-  int rpb = rows > 64 * maxblk ? (rows + maxblk - 1) / maxblk : 64;
-  int nblk = (rows + rpb - 1) / rpb;
-  if ((long)nblk * F > scratch_floats) {
-    nblk = (int)(scratch_floats / F);
-    if (nblk < 1) return 0;
-    rpb = (rows + nblk - 1) / nblk;
-    nblk = (rows + rpb - 1) / rpb;
-  }
-  *rpb_out = rpb;
-  return nblk;
-}
-
-extern "C" int avsr_batchnorm_sync_sum(const float* x, int32_t rows, int32_t F, float* sum_out, float* scratch,
-                                       int64_t scratch_floats, void* stream) {
-  if (!x || !sum_out || !scratch || rows <= 0 || F <= 0 || F % 4) return AVSR_ERR_ARG;
-  int rpb;
-  const int nblk = bn_blocks(rows, F, scratch_floats, &rpb);
-  if (!nblk) return AVSR_ERR_ARG;
-  hipLaunchKernelGGL(bn_partial_sum_kernel, dim3(nblk), dim3(256), 0, S_(stream), x, scratch, rows, F, rpb);
-  AVSR_CHECK_LAUNCH();
-  hipLaunchKernelGGL(bn_mean_kernel, dim3((F + 31) / 32), dim3(1024), 0, S_(stream), scratch, nblk, sum_out, 1, F, nullptr);
-  AVSR_CHECK_LAUNCH();
-  return AVSR_OK;
-}
-
-extern "C" int avsr_batchnorm_sync_sqsum(const float* x, int32_t rows, int32_t F, const float* sum_global,
-                                         const float* total_rows, float* mean_out, float* sq_out, float* scratch,
-                                         int64_t scratch_floats, void* stream) {
-  if (!x || !sum_global || !total_rows || !mean_out || !sq_out || !scratch || rows <= 0 || F <= 0 || F % 4) return AVSR_ERR_ARG;
-  int rpb;
-  const int nblk = bn_blocks(rows, F, scratch_floats, &rpb);
-  if (!nblk) return AVSR_ERR_ARG;
-  hipLaunchKernelGGL(bn_mean_kernel, dim3((F + 31) / 32), dim3(1024), 0, S_(stream), sum_global, 1, mean_out, 1, F, total_rows);
-  AVSR_CHECK_LAUNCH();
-  hipLaunchKernelGGL(bn_partial_sq_kernel, dim3(nblk), dim3(256), 0, S_(stream), x, mean_out, scratch, rows, F, rpb);
-  AVSR_CHECK_LAUNCH();
-  hipLaunchKernelGGL(bn_mean_kernel, dim3((F + 31) / 32), dim3(1024), 0, S_(stream), scratch, nblk, sq_out, 1, F, nullptr);
-  AVSR_CHECK_LAUNCH();
-  return AVSR_OK;
-}
-
-// ---- ONE small collective per data-parallel step (SURVEY 8(e) collectives (2) + (3) fused) ----
-// avsr_batchnorm_sync_moments: per-feature sum x | sum x^2 of this rank's rows in DOUBLE precision into out64 [2F] (the global
-// variance is then E[x^2] - mean^2 evaluated in fp64: exact to ~1e-13 relative for feature-scale inputs, so the second,
-// mean-dependent reduction -- and its all-reduce -- is not needed).
-__global__ __launch_bounds__(256) void bn_moments_partial_kernel(const float* __restrict__ x, double* __restrict__ part, int rows, int F, int rpb) {
-  const int r0 = blockIdx.x * rpb, r1 = min(rows, r0 + rpb);
-  for (int f = threadIdx.x; f < F; f += 256) {
-    double s = 0.0, s2 = 0.0;
-    for (int r = r0; r < r1; ++r) { const double v = (double)x[(long)r * F + f]; s += v; s2 += v * v; }
-    part[(long)blockIdx.x * 2 * F + f] = s;
-    part[(long)blockIdx.x * 2 * F + F + f] = s2;
-  }
-}
-__global__ __launch_bounds__(256) void bn_moments_final_kernel(const double* __restrict__ part, int nblk, int F2, double* __restrict__ out) {
-  const int f = blockIdx.x * 256 + threadIdx.x;
-  if (f >= F2) return;
-  double s = 0.0;
-  for (int i = 0; i < nblk; ++i) s += part[(long)i * F2 + f];
-  out[f] = s;
-}
-extern "C" int avsr_batchnorm_sync_moments(const float* x, int32_t rows, int32_t F, double* out64, float* scratch, int64_t scratch_floats,
-                                           void* stream) {
-  if (!x || !out64 || !scratch || rows <= 0 || F <= 0 || ((uintptr_t)scratch & 7)) return AVSR_ERR_ARG;
-  int nblk = (rows + 63) / 64;
-  if (nblk > 1024) nblk = 1024;
-  while (nblk > 1 && (long)nblk * 2 * F * 2 > scratch_floats) nblk /= 2;
-  if ((long)nblk * 2 * F * 2 > scratch_floats) return AVSR_ERR_ARG;
-  const int rpb = (rows + nblk - 1) / nblk;
-  nblk = (rows + rpb - 1) / rpb;
-  double* part = reinterpret_cast<double*>(scratch);
-  hipLaunchKernelGGL(bn_moments_partial_kernel, dim3(nblk), dim3(256), 0, S_(stream), x, part, rows, F, rpb);
-  AVSR_CHECK_LAUNCH();
-  hipLaunchKernelGGL(bn_moments_final_kernel, dim3((2 * F + 255) / 256), dim3(256), 0, S_(stream), part, nblk, 2 * F, out64);
-  AVSR_CHECK_LAUNCH();
-  return AVSR_OK;
-}
+// ---- ONE small collective per data-parallel step: avsr_batchnorm_sync_moments (batchnorm.hip) fills the per-stream part of its buffer ----
 // avsr_dp_sync_unpack: the all-reduced buffer [sum(mask), AU count | per stream: sum x [F], sum x^2 [F], rows] -> the float32 operands
 // the step's kernels read: dp_norm[0..1]; per stream mean [F], centred squares sum (x - mean)^2 [F] = sum x^2 - rows*mean^2, rows.
 struct DpUnpack { const double* buf; float* dp_norm; int nstream; int off[4]; int F[4]; float* mean[4]; float* sq[4]; float* rows[4]; };
@@ -1064,33 +781,6 @@ extern "C" int avsr_dp_sync_unpack(const double* buf, float* dp_norm, int32_t ns
     if (F[s] > maxF) maxF = F[s];
   }
   hipLaunchKernelGGL(dp_sync_unpack_kernel, dim3((maxF + 255) / 256), dim3(256), 0, S_(stream), U);
-  AVSR_CHECK_LAUNCH();
-  return AVSR_OK;
-}
-
-extern "C" int avsr_batchnorm_sync_apply(const float* x, float* y, int32_t rows, int32_t F, const float* gamma,
-                                         const float* beta, float* moving_mean, float* moving_var, const float* mean,
-                                         const float* sq_global, const float* total_rows, float* invstd_out, float eps,
-                                         float momentum, int32_t relu, void* stream) {
-  if (!x || !y || !gamma || !beta || !mean || !sq_global || !total_rows || !invstd_out || rows <= 0 || F <= 0 || F % 4)
-    return AVSR_ERR_ARG;
-  hipLaunchKernelGGL(bn_var_kernel, dim3((F + 31) / 32), dim3(1024), 0, S_(stream), sq_global, 1, mean, invstd_out, moving_mean,
-                     moving_var, 1, F, eps, momentum, 0, total_rows);
-  AVSR_CHECK_LAUNCH();
-  const long n4 = (long)rows * F / 4;
-  int blocks = (int)((n4 + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(bn_apply_kernel, dim3(blocks), dim3(256), 0, S_(stream), x, mean, invstd_out, moving_mean, moving_var, gamma, beta, y,
-                     n4, F, 1, eps, relu);
-  AVSR_CHECK_LAUNCH();
-  return AVSR_OK;
-}
-
-extern "C" int avsr_batchnorm_xhat(const float* x, const float* mean, const float* invstd, float* xhat, int32_t rows,
-                                   int32_t F, void* stream) {
-  if (!x || !mean || !invstd || !xhat) return AVSR_ERR_ARG;
-  const long n = (long)rows * F;
-  hipLaunchKernelGGL(bn_xhat_kernel, dim3(blocks_for(n)), dim3(256), 0, S_(stream), x, mean, invstd, xhat, n, F);
   AVSR_CHECK_LAUNCH();
   return AVSR_OK;
 }

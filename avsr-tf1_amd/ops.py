@@ -1,5 +1,6 @@
 """Thin Python wrappers over the C ABI: torch tensors are only containers for device memory."""
 import ctypes as C
+import os
 
 import torch
 
@@ -82,8 +83,7 @@ class gemm_group:
         return False
 
 
-import os as _os
-_GROUP_ON = _os.environ.get("AVSR_GEMM_GROUP", "1") != "0"
+_GROUP_ON = os.environ.get("AVSR_GEMM_GROUP", "1") != "0"
 
 
 def gemm(A, B, Cm, M, N, K, trans_a=False, trans_b=False, alpha=1.0, beta=0.0, bias=None,
@@ -482,7 +482,7 @@ def rnn_persistent_error():
     return bool(_persist_sync is not None and int(_persist_sync[:1].item()) != 0)
 
 
-# ---- lip-crop CNN front-end helpers (csrc/conv.hip) -------------------------------------------------------------------
+# ---- lip-crop CNN front-end helpers (csrc/batchnorm.hip, conv.hip) -------------------------------------------------------------------
 def batchnorm_fwd_ex(x, y, rows, F, gamma, beta, mov_mean, mov_var, save_mean, save_invstd, training, eps, momentum, relu, scratch, bessel=1):
     check(_L().avsr_batchnorm_fwd_ex(fptr(x), fptr(y), rows, F, fptr(gamma), fptr(beta), fptr(mov_mean), fptr(mov_var), fptr(save_mean),
                                      fptr(save_invstd), int(training), float(eps), float(momentum), int(relu), int(bessel), fptr(scratch),
