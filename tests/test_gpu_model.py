@@ -139,7 +139,7 @@ CASES = {
 }
 
 
-def make(case, B=5, Ta=21, Tv=9, L=7, ragged=True, **over):
+def make(case, B=5, Ta=21, Tv=9, L=7, ragged=True, seed=2001, batch_seed=1000, **over):
     from avsr_tf1_amd.config import ModelConfig
     from oracle import avsr_oracle as O
     kw = dict(decoder_units=(32,), embedding_size=16, video_feat=12, audio_feat=20)
@@ -147,7 +147,7 @@ def make(case, B=5, Ta=21, Tv=9, L=7, ragged=True, **over):
     kw.update(over)
     ocfg = O.OracleConfig(**kw)
     mcfg = ModelConfig(**{f.name: getattr(ocfg, f.name) for f in dataclasses.fields(ModelConfig) if hasattr(ocfg, f.name)})
-    W = O.init_params(ocfg, seed=2001)
+    W = O.init_params(ocfg, seed=seed)
     # non-trivial biases / BN parameters so that every term is exercised
     rng = np.random.default_rng(7)
     for k in W:
@@ -157,7 +157,7 @@ def make(case, B=5, Ta=21, Tv=9, L=7, ragged=True, **over):
             W[k] = (1.0 + rng.standard_normal(W[k].shape) * 0.1).astype(np.float32)
         if k.endswith("/g"):
             W[k] = (W[k] * 1.3).astype(np.float32)
-    batch = O.synthetic_batch(ocfg, B=B, T_a=Ta, T_v=Tv, L=L, ragged=ragged)
+    batch = O.synthetic_batch(ocfg, B=B, T_a=Ta, T_v=Tv, L=L, ragged=ragged, seed=batch_seed)
     return O, ocfg, mcfg, W, batch
 
 
