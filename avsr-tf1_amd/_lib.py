@@ -106,6 +106,16 @@ class AttnRnn(C.Structure):
                 ("fused_ws", C.c_void_p), ("fused_ws_floats", C.c_int64)]
 
 
+MAX_LM_LAYERS = 4
+
+
+class BeamLm(C.Structure):
+    _fields_ = [("n_layers", C.c_int32), ("H", C.c_int32), ("E", C.c_int32), ("V", C.c_int32),
+                ("one_hot", C.c_int32), ("n_rows", C.c_int32), ("lm_weight", C.c_float), ("pad_", C.c_int32),
+                ("embedding", C.c_void_p), ("wt", C.c_void_p * MAX_LM_LAYERS), ("bias", C.c_void_p * MAX_LM_LAYERS),
+                ("wout_t", C.c_void_p), ("bout", C.c_void_p), ("state_c", C.c_void_p), ("state_h", C.c_void_p), ("lm_logp", C.c_void_p)]
+
+
 class ConvDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("N", "H", "W", "Ci", "Co", "k", "stride", "pad_t", "pad_l", "Ho", "Wo", "pad_")] + \
                [("bn_scale", C.c_void_p), ("bn_shift", C.c_void_p)]
@@ -132,7 +142,7 @@ class TransposeJob(C.Structure):
 
 _STRUCTS = {"avsr_dec_layer": DecLayer, "avsr_mat": Mat, "avsr_gemm_desc": GemmDesc, "avsr_rnn_layer": RnnLayer, "avsr_rnn_stack": RnnStack,
             "avsr_conv_desc": ConvDesc, "avsr_conv3d_desc": Conv3dDesc, "avsr_logmel_args": LogmelArgs, "avsr_attn_mech": AttnMech, "avsr_attn_rnn": AttnRnn, "avsr_transpose_job": TransposeJob,
-            "avsr_colsum_job": ColsumJob}
+            "avsr_colsum_job": ColsumJob, "avsr_beam_lm": BeamLm}
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 # argument types of every entry point that returns an int status (include/avsr_hip.h)
@@ -177,6 +187,11 @@ _SIGS = {
     "avsr_attn_rnn_bwd": [C.POINTER(AttnRnn), _vp],
     "avsr_beam_gather_tree": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
     "avsr_beam_search_step": [_vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp],
+    "avsr_beam_lm_supported": [C.POINTER(BeamLm)],
+    "avsr_beam_lm_step": [C.POINTER(BeamLm), _vp, _vp, _i32, _i32, _vp],
+    "avsr_beam_search_step_lm": [_vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp,
+                                 _vp, _f32, _vp],
+    "avsr_attn_rnn_fwd_lm": [C.POINTER(AttnRnn), C.POINTER(BeamLm), _i32, _i32, _vp],
     "avsr_attn_alpha_rows": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp],
     "avsr_bahdanau_dkeys": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
     "avsr_transpose": [C.POINTER(TransposeJob), _i32, _vp],

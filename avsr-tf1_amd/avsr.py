@@ -20,6 +20,10 @@ embedding sizes may be anything (the engine pads to multiples of 4 inside, confi
 computes instead.
 Not built (raise explicitly): `precision='float16'`, the `2dconv_cnn` front-end, `sync_cnn_bn` data parallelism with `3dconv_cnn`, the
 writer's MFCC / delta audio transformations, the monotonic attention variants and the non-default cell types.
+Shallow fusion of a language model into beam search (not in the reference, which trains `avsr.LM` but never uses it in the recogniser):
+`lm_checkpoint` (a checkpoint written by `LM.train`), `lm_weight` (0.3: a conventional value, not a tuned one),
+`lm_units_per_layer` ((256,)), `lm_embedding_size` (128), `lm_cell_type` ('lstm') arrive through **kwargs; `evaluate` then scores an
+unfinished beam's continuation with log p_model + lm_weight * log p_lm (csrc/beam_lm.hip).
 """
 import glob
 import os
@@ -134,6 +138,17 @@ class AVSR(object):
             raise NotImplementedError("write_attention_alignment=True needs decoding_algorithm='greedy' (the alignment history is "
                                       "kept by the greedy decode only)")
 
+        # shallow-fusion language model: everything that can be refused is refused here, on the host, before any engine is built
+        self._lm, self._lm_weight = None, float(kwargs.get('lm_weight', 0.3))
+        lm_checkpoint, lm_cfg, lm_weights = kwargs.get('lm_checkpoint'), None, None
+        if lm_checkpoint is not None:
+            from . import lm as _lm                                 # (lm.py imports this module: bound late)
+            if decoding_algorithm != 'beam_search':
+                raise ValueError("lm_checkpoint needs decoding_algorithm='beam_search': the fusion is defined on the beam")
+            lm_cfg = _lm.fusion_config(self._unit_dict, kwargs.get('lm_units_per_layer', (256,)), kwargs.get('lm_embedding_size', 128),
+                                       kwargs.get('lm_cell_type', 'lstm'))
+            lm_weights = _lm.checkpoint_weights(lm_cfg, lm_checkpoint)
+
         reverse = {v: k for k, v in self._unit_dict.items()}
         feats, video_hw = {}, (36, 36, 3)
         for idx, (proc, key) in enumerate(((video_processing, 'video'), (audio_processing, 'audio'))):
@@ -177,6 +192,8 @@ class AVSR(object):
             cnn_filters=tuple(cnn_filters), cnn_dense_units=cnn_dense_units, video_hw=video_hw,
             input_dense_layers=tuple(input_dense_layers), encoder_weight_sharing=bool(encoder_weight_sharing), residual_encoder=bool(residual_encoder), highway_encoder=bool(highway_encoder), instance_normalisation=bool(instance_normalisation))
         self._model = Seq2SeqModel(self._cfg, seed=kwargs.get('seed', 0))
+        if lm_cfg is not None:
+            self._lm = _lm.load_fusion_engine(lm_cfg, lm_weights)
         self._shuffle_seed = kwargs.get('shuffle_seed')        # None = a fresh order every run, as tf.data's unseeded shuffle(5000)
         # Data parallelism (the reference's num_gpus is deprecated and ignored, avsr/avsr.py:67,:127): when the process was started
         # under torch.distributed (one process per GPU, `torchrun`), every rank builds the same model, reads the same records,
@@ -425,7 +442,8 @@ class AVSR(object):
         for bd in it:
             batch, names = self._to_batch(bd)
             if self._decoding_algorithm == 'beam_search':     # avsr.py:58-59 default: width 10, first beam returned
-                ids = self._model.beam_search_decode(batch, beam_width=self._beam_width, max_steps=self._cfg.max_label_length)
+                ids = self._model.beam_search_decode(batch, beam_width=self._beam_width, max_steps=self._cfg.max_label_length,
+                                                     lm=self._lm, lm_weight=self._lm_weight if self._lm is not None else 0.0)
             else:
                 ids = self._model.greedy_decode(batch, max_steps=self._cfg.max_label_length)
             ids = ids.cpu().numpy()

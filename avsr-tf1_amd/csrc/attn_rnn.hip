@@ -16,6 +16,8 @@ namespace avsr {
 bool beam_dense_on();
 int beam_cell_launch(const avsr_attn_rnn& d, int l, hipStream_t s);
 int beam_attention_layer_launch(const avsr_attn_rnn& d, int l, hipStream_t s);
+int beam_lm_check(const avsr_beam_lm* m);                                                                  // beam_lm.hip
+int beam_lm_step_launch(const avsr_beam_lm& m, const int32_t* tok, const int32_t* parent_rows, int step, hipStream_t s);
 }
 int avsr_dec_persist_fwd(const avsr_attn_rnn* d, int32_t l_begin, int32_t l_end, void* stream);   // dec_persist.hip
 int avsr_dec_persist_bwd(const avsr_attn_rnn* d, void* stream);                                      // dec_persist_bwd.hip
@@ -201,12 +203,16 @@ __global__ __launch_bounds__(256) void logits_sample_kernel(const float* x, long
 // the attention output [K x O] times Wout^T [O x V] as NCT 16-column tiles of v_mfma_f32_16x16x4_f32, wave w taking the O / 4 inputs
 // [w O / 4, (w + 1) O / 4), the four partial tiles summed through LDS -- one launch and one read-back of the logits less per step
 // (the separate projection was a 7 us launch of 640 x 31 outputs).  Needs K <= 16, V <= 16 NCT, O % 256 == 0.  NCT == 0: logits given.
-template <int NCT>
+// LM: shallow fusion (avsr_beam_lm): an unfinished beam's step log-probability gets + lm_weight * lm_logp[row][v], lm_logp = the
+// language model's log_softmax [B * K][V] (beam_lm.hip).  Weight 0 takes the branch without the term, so the search is bit for bit the
+// one without a model; LM == false compiles the term out (lm_logp / lm_weight unused): the instruction stream of the search as it was.
+template <int NCT, bool LM>
 __global__ __launch_bounds__(256) void beam_step_kernel(float* logits, long logits_sb, int V, int K, int l, int eos, float w,
                                  const float* logp_in, const int32_t* fin_in, const int32_t* len_in,
                                  float* logp_out, int32_t* fin_out, int32_t* len_out, int32_t* tok, int32_t* parent_rows,
                                  int32_t* step_ids, int32_t* parent_ids, int32_t* n_unfinished,
-                                 const float* xa, long xsb, int O, const float* wout_t, const float* bout) {
+                                 const float* xa, long xsb, int O, const float* wout_t, const float* bout,
+                                 const float* lm_logp, float lm_weight) {
   extern __shared__ __attribute__((aligned(16))) float sm[];   // logits [K*V] | lse [K] | max [K] | sum [K] | penalties [K][2] | fin [K] | len [K] | logp [K] | alive | winners [2][4] x 64 bit
   const int n = K * V;
   float* lg_s = sm;
@@ -315,7 +321,10 @@ __global__ __launch_bounds__(256) void beam_step_kernel(float* logits, long logi
     if (i < n) {
       const int k = i / V, v = i - k * V;
       const bool fin = fin_s[k] != 0;
-      const float sl = fin ? (v == eos ? 0.f : FMIN) : lg_s[i] - lse_s[k];
+      float sl = fin ? (v == eos ? 0.f : FMIN) : lg_s[i] - lse_s[k];
+      if constexpr (LM) {
+        if (!fin && lm_weight != 0.f) sl += lm_weight * lm_logp[(long)(b * K + k) * V + v];
+      }
       const float t = logp_s[k] + sl;
       const float sc = t / pen[2 * k + ((fin || v == eos) ? 0 : 1)];
       const unsigned u = __builtin_bit_cast(unsigned, sc);
@@ -469,7 +478,8 @@ static void fill_attn_launch(const avsr_attn_rnn& d, int l, AttnLaunch& AL) {
 
 }  // namespace avsr
 
-extern "C" int avsr_attn_rnn_fwd(const avsr_attn_rnn* dp, int32_t l_begin, int32_t l_end, void* stream) {
+// lm != NULL (mode 3 only, checked by the caller): the language-model step runs ahead of every step's selection
+static int attn_rnn_fwd_impl(const avsr_attn_rnn* dp, const avsr_beam_lm* lm, int32_t l_begin, int32_t l_end, void* stream) {
   using namespace avsr;
   int rc = validate(dp);
   if (rc) return rc;
@@ -532,6 +542,8 @@ extern "C" int avsr_attn_rnn_fwd(const avsr_attn_rnn* dp, int32_t l_begin, int32
   // beam search: the B * K-row cell and attention-layer steps as 64 x 64-tiled products with row-gathered operands (beam_gemm.hip)
   const bool beam_dense = d.mode == 3 && !gru && d.n_extra == 0 && !drop && beam_dense_on();
   for (int l = l_first; l < l_end; ++l) {
+    // ---- K0: language-model step on the symbols and parents the previous selection left (independent of the decoder's chain) ----
+    if (lm && (rc = beam_lm_step_launch(*lm, d.tok, d.parent_rows, l, s))) return rc;
     // ---- K1: LSTM step -------------------------------------------------------------------
     bool cell_done = false;
     if (beam_dense) {
@@ -707,13 +719,14 @@ extern "C" int avsr_attn_rnn_fwd(const avsr_attn_rnn* dp, int32_t l_begin, int32
                            d.ids + l, (long)L, d.tok, d.steplen, d.n_unfinished, B, l, d.eos_id);
       } else if (d.mode == 3) {
         const int K = d.beam_width, pin = l & 1, pout = (l + 1) & 1;
-#define BS_GO(NCT_)                                                                                                                       \
-  hipLaunchKernelGGL(beam_step_kernel<NCT_>, dim3(B / K), dim3(256), (K * d.V + 8 * K + 24 + 1024 * NCT_) * sizeof(float), s,               \
+#define BS_GO(NCT_, LM_)                                                                                                                  \
+  hipLaunchKernelGGL((beam_step_kernel<NCT_, LM_>), dim3(B / K), dim3(256), (K * d.V + 8 * K + 24 + 1024 * NCT_) * sizeof(float), s,        \
                      d.logits + (long)l * d.V, (long)L * d.V, d.V, K, l, d.eos_id, d.length_penalty, d.beam_logp + (long)pin * B,           \
                      d.beam_fin + (long)pin * B, d.beam_len + (long)pin * B, d.beam_logp + (long)pout * B, d.beam_fin + (long)pout * B,    \
                      d.beam_len + (long)pout * B, d.tok, d.parent_rows, d.step_ids + (long)l * B, d.parent_ids + (long)l * B,              \
-                     d.n_unfinished + l, xa, xsb, O, d.wout_t, d.bout)
-        if (bs_nct == 2) BS_GO(2); else if (bs_nct == 4) BS_GO(4); else BS_GO(0);
+                     d.n_unfinished + l, xa, xsb, O, d.wout_t, d.bout, lm ? lm->lm_logp : nullptr, lm ? lm->lm_weight : 0.f)
+        if (lm) { if (bs_nct == 2) BS_GO(2, true); else if (bs_nct == 4) BS_GO(4, true); else BS_GO(0, true); }
+        else { if (bs_nct == 2) BS_GO(2, false); else if (bs_nct == 4) BS_GO(4, false); else BS_GO(0, false); }
 #undef BS_GO
       } else {
         hipLaunchKernelGGL(sched_sample_kernel, dim3(B), dim3(128), sizeof(float) * d.V, s, d.logits + (long)l * d.V, (long)L * d.V, d.V, d.labels,
@@ -729,6 +742,19 @@ extern "C" int avsr_attn_rnn_fwd(const avsr_attn_rnn* dp, int32_t l_begin, int32
     if (db.flush() != hipSuccess) return AVSR_ERR_HIP;
   }
   return AVSR_OK;
+}
+
+extern "C" int avsr_attn_rnn_fwd(const avsr_attn_rnn* dp, int32_t l_begin, int32_t l_end, void* stream) {
+  return attn_rnn_fwd_impl(dp, nullptr, l_begin, l_end, stream);
+}
+
+extern "C" int avsr_attn_rnn_fwd_lm(const avsr_attn_rnn* dp, const avsr_beam_lm* lm, int32_t l_begin, int32_t l_end, void* stream) {
+  if (!dp || !lm) return AVSR_ERR_ARG;
+  if (dp->mode != 3) return AVSR_ERR_ARG;                      // fusion is defined on the beam
+  const int rc = avsr::beam_lm_check(lm);
+  if (rc) return rc;
+  if (lm->V != dp->V || lm->n_rows != dp->B) return AVSR_ERR_ARG;
+  return attn_rnn_fwd_impl(dp, lm, l_begin, l_end, stream);
 }
 
 extern "C" int avsr_attn_rnn_bwd(const avsr_attn_rnn* dp, void* stream) {
@@ -978,11 +1004,12 @@ extern "C" int avsr_beam_gather_tree(const int32_t* step_ids, const int32_t* par
   return AVSR_OK;
 }
 
-extern "C" int avsr_beam_search_step(float* logits, int32_t n_utt, int32_t beam_width, int32_t V, int32_t step, int32_t eos_id,
-                                     float length_penalty_weight, const float* logp_in, const int32_t* fin_in, const int32_t* len_in,
-                                     float* logp_out, int32_t* fin_out, int32_t* len_out, int32_t* tok, int32_t* parent_rows,
-                                     int32_t* step_ids, int32_t* parent_ids, int32_t* n_unfinished, const float* x, int64_t x_stride,
-                                     int32_t O, const float* wout_t, const float* bout, void* stream) {
+extern "C" int avsr_beam_search_step_lm(float* logits, int32_t n_utt, int32_t beam_width, int32_t V, int32_t step, int32_t eos_id,
+                                        float length_penalty_weight, const float* logp_in, const int32_t* fin_in, const int32_t* len_in,
+                                        float* logp_out, int32_t* fin_out, int32_t* len_out, int32_t* tok, int32_t* parent_rows,
+                                        int32_t* step_ids, int32_t* parent_ids, int32_t* n_unfinished, const float* x, int64_t x_stride,
+                                        int32_t O, const float* wout_t, const float* bout, const float* lm_logp, float lm_weight,
+                                        void* stream) {
   using namespace avsr;
   if (!logits || !logp_in || !fin_in || !len_in || !logp_out || !fin_out || !len_out || !tok || !parent_rows || !step_ids || !parent_ids ||
       !n_unfinished || n_utt <= 0 || beam_width <= 0 || V <= 0 || step < 0 || eos_id < 0 || eos_id >= V)
@@ -998,12 +1025,23 @@ extern "C" int avsr_beam_search_step(float* logits, int32_t n_utt, int32_t beam_
     if (K > 16 || V > 64 || O % 256 != 0 || x_stride % 4 != 0 || (((uintptr_t)x | (uintptr_t)wout_t) & 15) != 0) return AVSR_ERR_UNSUPPORTED;
     nct = V <= 32 ? 2 : 4;
   }
-#define BS_GO(NCT_)                                                                                                                       \
-  hipLaunchKernelGGL(beam_step_kernel<NCT_>, dim3(n_utt), dim3(256), (K * V + 8 * K + 24 + 1024 * NCT_) * sizeof(float), s, logits, (long)V, V, K,  \
+#define BS_GO(NCT_, LM_)                                                                                                                  \
+  hipLaunchKernelGGL((beam_step_kernel<NCT_, LM_>), dim3(n_utt), dim3(256), (K * V + 8 * K + 24 + 1024 * NCT_) * sizeof(float), s, logits, (long)V, V, K,  \
                      step, eos_id, length_penalty_weight, logp_in, fin_in, len_in, logp_out, fin_out, len_out, tok, parent_rows,                     \
-                     step_ids + (long)step * B, parent_ids + (long)step * B, n_unfinished + step, x, (long)x_stride, O, wout_t, bout)
-  if (nct == 2) BS_GO(2); else if (nct == 4) BS_GO(4); else BS_GO(0);
+                     step_ids + (long)step * B, parent_ids + (long)step * B, n_unfinished + step, x, (long)x_stride, O, wout_t, bout, lm_logp,       \
+                     lm_weight)
+  if (lm_logp) { if (nct == 2) BS_GO(2, true); else if (nct == 4) BS_GO(4, true); else BS_GO(0, true); }
+  else { if (nct == 2) BS_GO(2, false); else if (nct == 4) BS_GO(4, false); else BS_GO(0, false); }
 #undef BS_GO
   AVSR_CHECK_LAUNCH();
   return AVSR_OK;
+}
+
+extern "C" int avsr_beam_search_step(float* logits, int32_t n_utt, int32_t beam_width, int32_t V, int32_t step, int32_t eos_id,
+                                     float length_penalty_weight, const float* logp_in, const int32_t* fin_in, const int32_t* len_in,
+                                     float* logp_out, int32_t* fin_out, int32_t* len_out, int32_t* tok, int32_t* parent_rows,
+                                     int32_t* step_ids, int32_t* parent_ids, int32_t* n_unfinished, const float* x, int64_t x_stride,
+                                     int32_t O, const float* wout_t, const float* bout, void* stream) {
+  return avsr_beam_search_step_lm(logits, n_utt, beam_width, V, step, eos_id, length_penalty_weight, logp_in, fin_in, len_in, logp_out, fin_out,
+                                  len_out, tok, parent_rows, step_ids, parent_ids, n_unfinished, x, x_stride, O, wout_t, bout, nullptr, 0.f, stream);
 }

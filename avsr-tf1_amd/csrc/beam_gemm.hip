@@ -19,23 +19,9 @@
 #include "prof.h"
 #include "attn.h"
 #include "step.h"
+#include "beam_gemm.h"
 
 namespace avsr {
-
-#define BG_MAX_SRC 3
-#define BG_MAX_PROB 2
-#define BG_T 64            // tile rows = tile columns
-#define BG_K 128           // K per stage
-
-struct BGSrc { const float* a; long sb; const int* gather; int K, pad; };
-struct BGProb {
-  BGSrc src[BG_MAX_SRC];
-  int nsrc, R, N, tile0, ntx, pad;
-  const float* wt; long ldw;                     // weights [N][ldw], K contiguous
-  float* out; long out_sb;                       // LINEAR: out[r * out_sb + n]
-  const float* bias; const float* c_in; const int* parent; float* c_out; float* h_out; float* seq_out; long seq_sb;   // LSTM
-};
-struct BGLaunch { int nprob, ntiles; BGProb p[BG_MAX_PROB]; };
 
 // Operand staging.  Both operands are K-contiguous in memory (gathered activation rows; weight rows [N][ldw]).  A wave-instruction
 // fetches 4 rows x 256 contiguous bytes (16 lanes x 16 bytes per row: 8 full 128-byte lines; one lane per ROW, the obvious mapping,
@@ -291,6 +277,15 @@ __global__ __launch_bounds__(256) void beam_ctx_merge_kernel(const BCLaunch L) {
 int g_beam_dense = 1;         // avsr_attn_rnn_set_beam_kernel
 
 bool beam_dense_on() { return g_beam_dense != 0; }
+
+// one launch of a filled descriptor (beam_gemm.h): the language-model step of csrc/beam_lm.hip runs its cells through the same kernel
+int beam_gemm_launch(const BGLaunch& G, bool lstm, hipStream_t s) {
+  if (G.nprob < 1 || G.nprob > BG_MAX_PROB || G.ntiles < 1) return AVSR_ERR_ARG;
+  if (lstm) hipLaunchKernelGGL(beam_gemm_kernel<true>, dim3(G.ntiles), dim3(512), 0, s, G);
+  else hipLaunchKernelGGL(beam_gemm_kernel<false>, dim3(G.ntiles), dim3(512), 0, s, G);
+  AVSR_CHECK_LAUNCH();
+  return AVSR_OK;
+}
 
 // the LSTM cell step of all B rows.  Returns AVSR_ERR_UNSUPPORTED where the tiled kernel does not apply (the caller then runs step_kernel).
 int beam_cell_launch(const avsr_attn_rnn& d, int l, hipStream_t s) {

@@ -23,6 +23,44 @@ from .model import Batch, Seq2SeqModel
 from .parallel import DataParallelTrainer
 
 
+def fusion_config(unit_dict, units_per_layer=(256,), embedding_size=128, cell_type='lstm'):
+    """Evaluate-graph configuration (no dropout, no sampling) of a language model handed to the recogniser's beam search
+    (`AVSR(lm_checkpoint=...)`, shallow fusion: model_decoder.beam_search_decode(lm=...))."""
+    if cell_type != 'lstm':
+        raise NotImplementedError("lm_cell_type=%r: beam search fuses LSTM language models only" % (cell_type,))
+    reverse = {v: k for k, v in unit_dict.items()}
+    return ModelConfig(architecture='lm', video_units=None, audio_units=None, cell_type=cell_type, decoder_units=tuple(units_per_layer),
+                       embedding_size=embedding_size, vocab_size=len(unit_dict) - 1, go_id=reverse['GO'], eos_id=reverse['EOS'],
+                       use_dropout=False, sampling_probability=0.0, warmup_steps=0)
+
+
+def checkpoint_weights(cfg, checkpoint_path):
+    """{name: array} of a checkpoint written by `LM.train`, checked against `cfg` on the host: a vocabulary, width, depth or embedding
+    size that does not match raises ValueError naming the variable."""
+    from . import params as PR
+    cfg.validate()
+    z = np.load(checkpoint_path if checkpoint_path.endswith(".npz") else checkpoint_path + ".npz")
+    W = {k[7:]: z[k] for k in z.files if k.startswith("params:")}
+    inv = PR.inventory(cfg)
+    if "dec/out/bias" in W and W["dec/out/bias"].shape[0] != cfg.vocab_size:
+        raise ValueError("language-model checkpoint %s was trained over %d symbols, the recogniser has %d"
+                         % (checkpoint_path, W["dec/out/bias"].shape[0], cfg.vocab_size))
+    extra, missing = sorted(set(W) - set(inv)), sorted(set(inv) - set(W))
+    if extra or missing:
+        raise ValueError("language-model checkpoint %s does not hold the configured model (lm_units_per_layer / lm_embedding_size / "
+                         "lm_cell_type): missing %s, unexpected %s" % (checkpoint_path, missing, extra))
+    for k, (shape, _kind, _init) in inv.items():
+        if tuple(W[k].shape) != tuple(shape):
+            raise ValueError("language-model checkpoint %s: %s has shape %s, the configured model needs %s"
+                             % (checkpoint_path, k, tuple(W[k].shape), tuple(shape)))
+    return W
+
+
+def load_fusion_engine(cfg, weights, seed=0):
+    """The evaluate-mode engine of `fusion_config` carrying `checkpoint_weights`."""
+    return Seq2SeqModel(cfg, seed=seed, weights=weights)
+
+
 class LM(object):
     def __init__(self,
                  unit,

@@ -8,7 +8,7 @@ import os
 import numpy as np
 import torch
 from . import ops, params as PR
-from ._lib import AttnRnn, RnnStack
+from ._lib import AttnRnn, BeamLm, MAX_LM_LAYERS, RnnStack
 from .config import ATT_CODE, BAHDANAU_TYPES, CELL_ID_DECODER, LUONG_TYPES, ModelConfig, encoder_cell_id
 from .model_base import Batch, Ref, SeqBuf, _FlagReader, _PtrView, _splitk, desc_steplen  # noqa: F401
 
@@ -372,25 +372,32 @@ class DecoderMixin:
     def beam_search_decode(self, *args, **kw):
         """See _beam_search_decode.  If a persistent kernel's bounded wait expired during the pass (workgroups not co-resident) the
         results are invalid: check_persistent() has then switched the one-launch paths off and the pass is redone with one launch
-        per step (the ids written to .mlf files and error rates never come from a flagged pass)."""
+        per step (the ids written to .mlf files and error rates never come from a flagged pass); the redo carries `lm` along."""
         out = self._beam_search_decode(*args, **kw)
         if self.check_persistent():
             out = self._beam_search_decode(*args, **kw)
         return out
 
-    def greedy_decode(self, *args, **kw):
+    def greedy_decode(self, *args, lm=None, **kw):
         """See _greedy_decode; redone through the per-step launches if a persistent kernel flagged its pass (as above)."""
+        if lm is not None:
+            raise ValueError("greedy_decode: language-model fusion is defined on the beam (beam_search_decode(lm=...))")
         out = self._greedy_decode(*args, **kw)
         if self.check_persistent():
             out = self._greedy_decode(*args, **kw)
         return out
 
     def _beam_search_decode(self, batch: Batch, beam_width: int = 10, length_penalty_weight: Optional[float] = None,
-                            max_steps: Optional[int] = None, check_every: int = 8, return_all: bool = False):
+                            max_steps: Optional[int] = None, check_every: int = 8, return_all: bool = False, lm=None,
+                            lm_weight: float = 0.0):
         """Eval graph with BeamSearchDecoder (decoder_unimodal.py:222-271, decoder_bimodal.py:328-381): ids of beam 0,
         int32 [B, T_out]; positions after the first EOS hold EOS (gather_tree).  length_penalty_weight defaults to the
-        reference's 0.6 (unimodal / av_align) or 0.5 (bimodal)."""
+        reference's 0.6 (unimodal / av_align) or 0.5 (bimodal).
+        lm: a Seq2SeqModel with architecture='lm' (LSTM) over the same vocabulary -- shallow fusion: an unfinished beam's step score is
+        log_softmax(logits)[v] + lm_weight * log_softmax(lm logits)[v] (include/avsr_hip.h avsr_beam_lm; csrc/beam_lm.hip)."""
         cfg, K = self.cfg, int(beam_width)
+        if lm is not None:
+            self._check_lm(lm)
         if K < 1 or K > 64 or K * cfg.vocab_size > 1024:
             # beam_step_kernel keeps the K * V candidates of an utterance in registers, four per thread of one workgroup
             raise ValueError("beam search: beam_width must be in 1..64 with beam_width * vocabulary <= 1024 (got %d x %d); "
@@ -446,6 +453,7 @@ class DecoderMixin:
         logp.copy_(X["logp0"])
         prow.copy_(X["prow0"])
         ops.zero_multi([fin, ln])
+        lmd = self._beam_lm_desc(lm, lm_weight, X, R) if lm is not None else None
         self._decoder_init_state(wsb)
         self._block_prepare(wsb, D)
         d = self._block_desc(wsb, D, D["steplen"], 3, D["h0"], D["c0"], with_bwd=False)
@@ -465,7 +473,10 @@ class DecoderMixin:
         l, pending = 0, False
         while l < L:
             l1 = min(L, l + check_every)
-            ops.attn_rnn_fwd(d, l, l1)
+            if lmd is None:
+                ops.attn_rnn_fwd(d, l, l1)
+            else:
+                ops.attn_rnn_fwd_lm(d, lmd, l, l1)
             if pending and fr.value() == 0:
                 l = l1
                 break
@@ -481,6 +492,42 @@ class DecoderMixin:
         if return_all:
             return out
         return out[:, :, 0].contiguous()
+
+    def _check_lm(self, lm):
+        cfg = self.cfg
+        lc = getattr(lm, "cfg", None)
+        if lc is None or lc.architecture != "lm":
+            raise ValueError("beam search: lm must be a Seq2SeqModel with architecture='lm'")
+        if lc.cell_type != "lstm":
+            raise NotImplementedError("beam search: only LSTM language models are fused (cell_type=%r)" % (lc.cell_type,))
+        if (lc.vocab_size, lc.go_id, lc.eos_id) != (cfg.vocab_size, cfg.go_id, cfg.eos_id):
+            raise ValueError("beam search: the language model's vocabulary / GO / EOS (%d, %d, %d) differ from the recogniser's (%d, %d, %d)"
+                             % (lc.vocab_size, lc.go_id, lc.eos_id, cfg.vocab_size, cfg.go_id, cfg.eos_id))
+        if len(lc.decoder_units) > MAX_LM_LAYERS:
+            raise NotImplementedError("beam search: language models of up to %d layers" % MAX_LM_LAYERS)
+
+    def _beam_lm_desc(self, lm, lm_weight, X, R):
+        """avsr_beam_lm over the language model's own (4-padded) weights; its state ping-pong and log-probability scratch live in the
+        cached beam workspace X, keyed by the model's shape."""
+        lc, dev = lm.cfg, self.dev
+        nl, H, E, V = len(lc.decoder_units), lc.decoder_units[0], lc.embedding_size, lc.vocab_size
+        lm._refresh_derived()
+        key = ("lm", nl, H)
+        if key not in X:
+            X[key] = dict(c=torch.zeros(2, nl, R, H, device=dev), h=torch.zeros(2, nl, R, H, device=dev), logp=torch.zeros(R, V, device=dev))
+        buf = X[key]
+        m = BeamLm()
+        m.n_layers, m.H, m.E, m.V, m.one_hot, m.n_rows, m.lm_weight = nl, H, E, V, int(lm.onehot is not None), R, float(lm_weight)
+        m.embedding = ops.fptr(*lm._emb())
+        for j in range(nl):
+            m.wt[j] = ops.fptr(lm.derived, lm.Tr["dec/l%d/kernel" % j].off)
+            m.bias[j] = ops.fptr(lm.params, lm.P["dec/l%d/bias" % j].off)
+        m.wout_t = ops.fptr(lm.derived, lm.Tr["dec/out/kernel"].off)
+        m.bout = ops.fptr(lm.params, lm.P["dec/out/bias"].off)
+        m.state_c, m.state_h, m.lm_logp = ops.fptr(buf["c"]), ops.fptr(buf["h"]), ops.fptr(buf["logp"])
+        if not ops.beam_lm_supported(m):
+            raise ValueError("beam search: the language model's shape is outside avsr_beam_lm_supported")
+        return m
 
     def _flag_reader(self):
         if getattr(self, "_fr", None) is None:

@@ -171,6 +171,28 @@ def beam_search_step(logits, n_utt, beam_width, V, step, eos_id, length_penalty_
           "avsr_beam_search_step")
 
 
+def beam_search_step_lm(logits, n_utt, beam_width, V, step, eos_id, length_penalty_weight, logp_in, fin_in, len_in, logp_out, fin_out, len_out,
+                        tok, parent_rows, step_ids, parent_ids, n_unfinished, lm_logp, lm_weight, x=None, x_stride=0, O=0, wout_t=None, bout=None):
+    """beam_search_step with the shallow-fusion term + lm_weight * lm_logp on unfinished beams (lm_logp None: beam_search_step exactly)."""
+    check(_L().avsr_beam_search_step_lm(fptr(logits), n_utt, beam_width, V, step, eos_id, float(length_penalty_weight), fptr(logp_in), fptr(fin_in),
+                                        fptr(len_in), fptr(logp_out), fptr(fin_out), fptr(len_out), fptr(tok), fptr(parent_rows), fptr(step_ids),
+                                        fptr(parent_ids), fptr(n_unfinished), fptr(x), x_stride, O, fptr(wout_t), fptr(bout), fptr(lm_logp),
+                                        float(lm_weight), _s()), "avsr_beam_search_step_lm")
+
+
+def beam_lm_supported(desc):
+    return bool(_L().avsr_beam_lm_supported(C.byref(desc)))
+
+
+def beam_lm_step(desc, tok, parent_rows, n_rows, step):
+    """One language-model step over the hypothesis rows (include/avsr_hip.h avsr_beam_lm): writes desc.lm_logp and the state's other half."""
+    check(_L().avsr_beam_lm_step(C.byref(desc), fptr(tok), fptr(parent_rows), int(n_rows), int(step), _s()), "avsr_beam_lm_step")
+
+
+def attn_rnn_fwd_lm(desc, lm_desc, l_begin, l_end):
+    check(_L().avsr_attn_rnn_fwd_lm(C.byref(desc), C.byref(lm_desc), int(l_begin), int(l_end), _s()), "avsr_attn_rnn_fwd_lm")
+
+
 def beam_gather_tree(step_ids, parent_ids, beam_len, out, n_utt, beam_width, T, eos_id):
     check(_L().avsr_beam_gather_tree(fptr(step_ids), fptr(parent_ids), fptr(beam_len), fptr(out), n_utt, beam_width, T, eos_id, _s()),
           "avsr_beam_gather_tree")

@@ -400,6 +400,51 @@ int avsr_beam_search_step(float* logits, int32_t n_utt, int32_t beam_width, int3
                           int32_t* step_ids, int32_t* parent_ids, int32_t* n_unfinished, const float* x, int64_t x_stride,
                           int32_t O, const float* wout_t, const float* bout, void* stream);
 
+/* Shallow fusion of a language model into beam search (csrc/beam_lm.hip).  The reference trains such a model (avsr/lm.py,
+ * experiment_lrs2_lm.py) but never connects it to the recogniser; the scoring rule is this project's own:
+ *   step_logp[k][v] = log_softmax(logits_am[k])[v] + lm_weight * log_softmax(logits_lm[k])[v]        (unfinished beam k)
+ * and everything else of the step is avsr_beam_search_step unchanged (a finished beam continues with EOS at log-probability 0, no
+ * language-model term; EOS gets its term like any other symbol).  lm_weight == 0 reproduces the search without a model bit for bit.
+ * The model is avsr.LM's evaluate graph: embedding (or one-hot rows) of the previous symbol -> n_layers LSTM layers of width H from the
+ * zero state (TF gate order i, j, f, o, forget bias 1, cell clip 1, the cell of avsr_rnn_layer) -> Dense(V) -> log_softmax.  Each
+ * hypothesis row keeps (c, h) of every layer; after a selection row r continues from the state of row parent_rows[r], read out of the
+ * other half of a ping-pong (step s reads half s & 1 and writes half (s + 1) & 1; step 0 zeroes half 0 first).
+ * Buffers: embedding [V][E] (one_hot != 0: the unit rows, E >= V, that the engine keeps for embedding_size <= 0; the flag is
+ * informational -- the kernels read the table either way, only the host check E >= V looks at it), wt[j] [4H][K_j] with
+ * K_0 = E + H and K_j = 2H (rows: input part, then recurrent part; gate columns unit-interleaved as everywhere), bias[j] [H][4],
+ * wout_t [V][H], bout [V], state_c / state_h [2][n_layers][n_rows][H], lm_logp [n_rows][V].  H % 4 == 0, E % 4 == 0, V <= 1024,
+ * 1 <= n_layers <= AVSR_MAX_LM_LAYERS.  tok[r] must lie in [0, V) and parent_rows[r] in [0, n_rows): what avsr_beam_search_step writes. */
+#define AVSR_MAX_LM_LAYERS 4
+typedef struct avsr_beam_lm {
+  int32_t n_layers, H, E, V;
+  int32_t one_hot, n_rows;
+  float lm_weight;
+  int32_t pad_;
+  const float* embedding;
+  const float* wt[AVSR_MAX_LM_LAYERS];
+  const float* bias[AVSR_MAX_LM_LAYERS];
+  const float* wout_t;
+  const float* bout;
+  float* state_c;
+  float* state_h;
+  float* lm_logp;
+} avsr_beam_lm;
+/* 1 if avsr_beam_lm_step runs this descriptor, else 0 (decided on the host; nothing is dereferenced). */
+int avsr_beam_lm_supported(const avsr_beam_lm* lm);
+/* One language-model step over n_rows (== lm->n_rows) hypothesis rows: n_layers launches of the row-gathered MFMA cell product
+ * (beam_gemm_kernel) and one of the output layer + log_softmax; rows past n_rows of a partial tile contribute and write nothing. */
+int avsr_beam_lm_step(const avsr_beam_lm* lm, const int32_t* tok, const int32_t* parent_rows, int32_t n_rows, int32_t step, void* stream);
+/* avsr_beam_search_step with the language-model term: lm_logp [n_utt * beam_width][V] (NULL = avsr_beam_search_step exactly). */
+int avsr_beam_search_step_lm(float* logits, int32_t n_utt, int32_t beam_width, int32_t V, int32_t step, int32_t eos_id,
+                             float length_penalty_weight, const float* logp_in, const int32_t* fin_in, const int32_t* len_in,
+                             float* logp_out, int32_t* fin_out, int32_t* len_out, int32_t* tok, int32_t* parent_rows,
+                             int32_t* step_ids, int32_t* parent_ids, int32_t* n_unfinished, const float* x, int64_t x_stride,
+                             int32_t O, const float* wout_t, const float* bout, const float* lm_logp, float lm_weight, void* stream);
+/* avsr_attn_rnn_fwd in mode 3 with avsr_beam_lm_step ahead of every selection (lm->n_rows == d->B, lm->V == d->V), under every
+ * avsr_attn_rnn_set_beam_kernel setting.  A step queued after the search has ended advances the model harmlessly (tok = EOS,
+ * parent_rows = identity) and its output is not read. */
+int avsr_attn_rnn_fwd_lm(const avsr_attn_rnn* d, const avsr_beam_lm* lm, int32_t l_begin, int32_t l_end, void* stream);
+
 /* Post-loop helpers of the attention backward (see csrc/attention.hip). */
 int avsr_attn_alpha_rows(float* scores, const float* dscores, const int32_t* len, const int32_t* steplen,
                          const float* g, float* rowdot, int32_t B, int32_t L, int32_t T, void* stream);
