@@ -14,7 +14,7 @@ gradient kernel also produces the bias gradient.  Shapes those kernels do not co
 (avsr_conv3x3*) or to avsr_im2col + avsr_gemm (the TF kernel [kh,kw,cin,cout] IS the [kh*kw*cin, cout] operand; data gradient =
 transposed GEMM + avsr_col2im, weight gradient = split-K TN GEMM), with BN through avsr_batchnorm_fwd_ex / avsr_batchnorm_bwd.
 This file only owns buffers and the op order; all arithmetic is in csrc/conv_mfma.hip, conv_wgrad.hip, batchnorm.hip, conv_direct.hip,
-conv.hip, gemm.hip, elementwise.hip."""
+conv.hip, gemm.hip, reduce.hip."""
 import os
 
 import torch

@@ -25,12 +25,8 @@
 // biased variance, bessel = 0.  The normalisation itself always uses the biased variance.
 //
 // Every reduction here runs in a fixed order (two stages, no float atomics): results are deterministic.
-#include "common.h"
+#include "reduce.h"
 #include "avsr_hip.h"
-
-// columns [0, split) of the reduced partial rows -> out, [split, F) -> out2  (elementwise.hip)
-int avsr_colsum_final_launch_split(const float* part, long ld, int nblk, float* out, float* out2, int split, int F, float alpha, float beta,
-                                   void* stream);
 
 using namespace avsr;
 #define S_(x) ((hipStream_t)(x))

@@ -82,6 +82,11 @@ __device__ __forceinline__ void block_group_reduce(float s, int idx, int F, int 
   __syncthreads();
 }
 
+// two-level row addressing (avsr_mat): row r of a [.., T, ..] record whose outer slices are ldo apart; T = 0: plain rows
+__device__ __forceinline__ long rowoff(int r, long ld, int T, long ldo) {
+  return T ? (long)(r / T) * ldo + (long)(r % T) * ld : (long)r * ld;
+}
+
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
 

@@ -9,7 +9,7 @@
 //                                      per (tap, cin, cout) element walking the pixels; per-block partials are summed in block
 //                                      order by the column-sum finaliser (deterministic)
 // Layers with more channels (32, 64: 9x9 and 5x5 maps, few rows) stay on im2col + avsr_gemm (conv.hip).
-#include "common.h"
+#include "reduce.h"
 #include "prof.h"
 #include "avsr_hip.h"
 
@@ -213,7 +213,6 @@ __global__ __launch_bounds__(256) void conv3x3_bwd_weight_kernel(const float* __
 
 }  // namespace avsr
 
-int avsr_colsum_final_launch(const float* part, int nblk, float* out, int F, float alpha, float beta, void* stream);
 // conv_mfma.hip: frame-resident MFMA kernels (AVSR_ERR_UNSUPPORTED -> the direct kernels below)
 int avsr_conv3x3_mfma(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Ci, int Co, int stride, int pad_t,
                       int pad_l, int Ho, int Wo, int flip, float beta, float* stats, int* nstat, void* stream);

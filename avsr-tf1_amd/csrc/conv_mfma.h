@@ -119,16 +119,8 @@ struct WGArgs {
 
 
 extern int g_conv_mfma;                 // avsr_conv_set_mfma: 0 sends every layer to the direct / im2col paths (tests)
-bool slab_defer_push(const float* part, long ld, int nblk, int F, float* out, float* out2, int split, int kind, int Ci, float alpha, float beta,
-                     hipStream_t s);
-bool slab_deferring();
 
 }  // namespace avsr
-
-int avsr_colsum_final_launch(const float* part, int nblk, float* out, int F, float alpha, float beta, void* stream);
-int avsr_colsum_final_launch_ld(const float* part, long ld, int nblk, float* out, int F, float alpha, float beta, void* stream);
-int avsr_colsum_final_launch_split(const float* part, long ld, int nblk, float* out, float* out2, int split, int F, float alpha, float beta,
-                                   void* stream);
 
 #define S_(x) ((hipStream_t)(x))
 

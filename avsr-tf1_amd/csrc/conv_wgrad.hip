@@ -2,6 +2,7 @@
 // (rows = (tap, cin), columns = cout, depth = positions) with the frame staged in LDS and dy streamed; per-workgroup partial slabs, reduced
 // by the column-sum launches of elementwise.hip (deferred to the end of the CNN's backward pass: avsr_slab_defer_*).
 #include "conv_mfma.h"
+#include "reduce.h"
 
 namespace avsr {
 

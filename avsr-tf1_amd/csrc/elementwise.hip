@@ -1,8 +1,8 @@
-// Memory-bound helper kernels of the train step: weight transposes, column reductions,
-// embedding lookup / gradient, masked sequence cross-entropy, AU regression loss, L2 + global-norm
-// clip + Adam.  All are single-pass, 16-byte vectorised where the layout allows, and deterministic
-// (two-stage reductions, no float atomics).
-#include "common.h"
+// Memory-bound helper kernels of the train step: weight transposes, embedding lookup / gradient,
+// dropout, masked sequence cross-entropy, AU regression loss, highway, L2 + global-norm clip + Adam.
+// All are single-pass and deterministic (two-stage reductions, no float atomics; column
+// reductions are reduce.hip's).
+#include "reduce.h"
 #include "avsr_hip.h"
 
 namespace avsr {
@@ -29,68 +29,6 @@ __global__ void transpose_kernel(const TLaunch L) {
       if (r < J.rows && c < J.cols) J.dst[(long)c * J.rows + r] = tile[tx][j];
     }
     __syncthreads();
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// column reduction: out[f] = alpha * sum_r a[r][f] * (b ? b[r][f] : 1) + beta * out[f]
-// two-level row addressing on a and b (same convention as avsr_gemm)
-__device__ __forceinline__ long rowoff(int r, long ld, int T, long ldo) {
-  return T ? (long)(r / T) * ldo + (long)(r % T) * ld : (long)r * ld;
-}
-
-__global__ void colsum_partial_kernel(const float* a, long lda, int Ta, long ldoa, const float* b, long ldb, int Tb,
-                                      long ldob, float* part, int rows, int F, int rows_per_blk) {
-  __shared__ float red[256];
-  const int G = F < 256 ? 256 / F : 1;
-  const int r0 = blockIdx.x * rows_per_blk, r1 = min(rows, r0 + rows_per_blk);
-  if (G > 1) {
-    const int idx = threadIdx.x, f = idx % F, g = idx / F;
-    float s = 0.f;
-    if (idx < G * F)
-      for (int r = r0 + g; r < r1; r += G) {
-        const float x = a[rowoff(r, lda, Ta, ldoa) + f];
-        s += b ? x * b[rowoff(r, ldb, Tb, ldob) + f] : x;
-      }
-    block_group_reduce(s, idx, F, G, red, part + (long)blockIdx.x * F);
-    return;
-  }
-  for (int f = threadIdx.x; f < F; f += blockDim.x) {
-    float s = 0.f;
-    for (int r = r0; r < r1; ++r) {
-      const float x = a[rowoff(r, lda, Ta, ldoa) + f];
-      s += b ? x * b[rowoff(r, ldb, Tb, ldob) + f] : x;
-    }
-    part[(long)blockIdx.x * F + f] = s;
-  }
-}
-
-// one block per 32 columns: 32 row-groups x 32 columns of threads walk the partials (4 loads in flight), then an LDS tree
-// columns f < split go to out[f], the rest to out2[f - split] (split = F: one destination)
-__global__ __launch_bounds__(1024) void colsum_final_kernel(const float* part, long ld, int nblk, float* out, int F, float alpha, float beta,
-                                                            float* out2 = nullptr, int split = 0x7fffffff) {
-  __shared__ double red[32][33];
-  const int fl = threadIdx.x & 31, g = threadIdx.x >> 5;
-  const int f = blockIdx.x * 32 + fl;
-  double s = 0.0;
-  if (f < F) {
-    int i = g;
-    for (; i + 96 < nblk; i += 128) {
-      const float a0 = part[(long)i * ld + f], a1 = part[(long)(i + 32) * ld + f];
-      const float a2 = part[(long)(i + 64) * ld + f], a3 = part[(long)(i + 96) * ld + f];
-      s += ((double)a0 + (double)a1) + ((double)a2 + (double)a3);
-    }
-    for (; i < nblk; i += 32) s += (double)part[(long)i * ld + f];
-  }
-  red[g][fl] = s;
-  __syncthreads();
-  if (g == 0 && f < F) {
-    double t = 0.0;
-#pragma unroll
-    for (int j = 0; j < 32; ++j) t += red[j][fl];
-    const float v = alpha * (float)t;
-    float* const o = f < split ? out + f : out2 + (f - split);
-    *o = beta != 0.f ? v + beta * *o : v;
   }
 }
 
@@ -124,7 +62,7 @@ __global__ void dropout_rows_kernel(const float* x, long ldx, int Tx, long ldox,
 // d emb[v, :] = sum over rows whose input token == v.  Block (v, chunk of 256 rows): the token ids of the chunk are
 // staged in LDS, every thread owns embedding columns and walks the chunk in row order with UNCONDITIONAL loads (the
 // select is on the value, so 8 rows are in flight); per-chunk partials [nchunk][V*E] are then summed in chunk order
-// by colsum_final_kernel (deterministic summation order).
+// by avsr_colsum_final_launch (deterministic summation order).
 #define EG_ROWS 256
 __global__ void embed_grad_partial_kernel(const float* dx, const int32_t* fed, float* part, int rows, int E, int V) {
   __shared__ int toks[EG_ROWS];
@@ -439,254 +377,6 @@ extern "C" int avsr_transpose(const avsr_transpose_job* jobs, int32_t n, void* s
   return AVSR_OK;
 }
 
-int avsr_colsum_final_launch(const float* part, int nblk, float* out, int F, float alpha, float beta, void* stream) {
-  hipLaunchKernelGGL(colsum_final_kernel, dim3((F + 31) / 32), dim3(1024), 0, S_(stream), part, (long)F, nblk, out, F, alpha, beta);
-  AVSR_CHECK_LAUNCH();
-  return AVSR_OK;
-}
-
-// one launch, two destinations: columns [0, split) -> out, [split, F) -> out2 (the weight and bias gradients of a convolution's slab)
-int avsr_colsum_final_launch_split(const float* part, long ld, int nblk, float* out, float* out2, int split, int F, float alpha, float beta,
-                                   void* stream) {
-  hipLaunchKernelGGL(colsum_final_kernel, dim3((F + 31) / 32), dim3(1024), 0, S_(stream), part, ld, nblk, out, F, alpha, beta, out2, split);
-  AVSR_CHECK_LAUNCH();
-  return AVSR_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Deferred slab reductions.  Every weight-gradient launch of the lip CNN leaves per-workgroup partial slabs that a tiny kernel then sums
-// (5 us of launch latency for ~1 MB, twelve times per step, each in line behind its convolution).  Nothing reads a weight gradient
-// before the optimiser, so between avsr_slab_defer_begin() and avsr_slab_defer_end() those reductions are only RECORDED (the caller
-// gives every convolution its own scratch region) and run as ONE launch at the end.  Same arithmetic per job as the kernels they replace.
-#define SLABJ_MAX 32
-struct SlabJob { const float* part; long ld; int nblk, F; float* out; float* out2; int split, kind, Ci, blk0; float alpha, beta; };
-struct SlabLaunch { int n; SlabJob job[SLABJ_MAX]; };
-__global__ __launch_bounds__(1024) void slab_final_multi_kernel(const SlabLaunch L) {
-  __shared__ double red[32][33];
-  int j = 0;
-#pragma unroll 1
-  for (int k = 1; k < L.n; ++k) if ((int)blockIdx.x >= L.job[k].blk0) j = k;
-  j = __builtin_amdgcn_readfirstlane(j);
-  const float* const part = L.job[j].part;
-  const long ld = L.job[j].ld;
-  const int nblk = L.job[j].nblk, F = L.job[j].F, Ci = L.job[j].Ci, kind = L.job[j].kind;
-  const int fl = threadIdx.x & 31, g = threadIdx.x >> 5;
-  const int f = ((int)blockIdx.x - L.job[j].blk0) * 32 + fl;
-  long o0 = -1, o1 = -1;
-  const int nw = 9 * Ci * 8;                          // (kind 1: kernel entries of the pixel-pair slab, then 8 bias entries)
-  if (kind == 0) { if (f < F) o0 = f; }
-  else if (f < nw) {
-    const int co = f & 7, ci = (f >> 3) % Ci, t = (f >> 3) / Ci, ti = t / 3, tj = t - ti * 3;
-    o0 = ((ti * 4 + tj) * Ci + ci) * 16 + co;
-    o1 = ((ti * 4 + tj + 1) * Ci + ci) * 16 + 8 + co;
-  } else if (f < nw + 8 && L.job[j].out2) { o0 = 12 * Ci * 16 + (f - nw); o1 = o0 + 8; }
-  double s = 0.0;
-  if (o0 >= 0) {
-    int i = g;
-    if (kind == 0) {
-      for (; i + 96 < nblk; i += 128) {
-        const float a0 = part[(long)i * ld + o0], a1 = part[(long)(i + 32) * ld + o0];
-        const float a2 = part[(long)(i + 64) * ld + o0], a3 = part[(long)(i + 96) * ld + o0];
-        s += ((double)a0 + (double)a1) + ((double)a2 + (double)a3);
-      }
-      for (; i < nblk; i += 32) s += (double)part[(long)i * ld + o0];
-    } else {
-      for (; i + 96 < nblk; i += 128) {
-        const float a0 = part[(long)i * ld + o0], b0 = part[(long)i * ld + o1];
-        const float a1 = part[(long)(i + 32) * ld + o0], b1 = part[(long)(i + 32) * ld + o1];
-        const float a2 = part[(long)(i + 64) * ld + o0], b2 = part[(long)(i + 64) * ld + o1];
-        const float a3 = part[(long)(i + 96) * ld + o0], b3 = part[(long)(i + 96) * ld + o1];
-        s += (double)a0 + (double)b0;
-        s += (double)a1 + (double)b1;
-        s += (double)a2 + (double)b2;
-        s += (double)a3 + (double)b3;
-      }
-      for (; i < nblk; i += 32) s += (double)part[(long)i * ld + o0] + (double)part[(long)i * ld + o1];
-    }
-  }
-  red[g][fl] = s;
-  __syncthreads();
-  if (g == 0 && o0 >= 0) {
-    double t = 0.0;
-#pragma unroll
-    for (int k = 0; k < 32; ++k) t += red[k][fl];
-    const float beta = L.job[j].beta;
-    float* o;
-    float v;
-    if (kind == 0) { v = L.job[j].alpha * (float)t; o = f < L.job[j].split ? L.job[j].out + f : L.job[j].out2 + (f - L.job[j].split); }
-    else { v = (float)t; o = f < nw ? L.job[j].out + f : L.job[j].out2 + (f - nw); }
-    *o = beta != 0.f ? v + beta * *o : v;
-  }
-}
-
-namespace avsr {
-static thread_local bool g_slab_defer = false;
-static thread_local SlabLaunch g_slab_jobs;
-// record a reduction instead of launching it; false: not deferring (the caller launches as before)
-bool slab_defer_push(const float* part, long ld, int nblk, int F, float* out, float* out2, int split, int kind, int Ci, float alpha, float beta,
-                     hipStream_t s);
-bool slab_deferring() { return g_slab_defer; }
-static int slab_flush(hipStream_t s) {
-  SlabLaunch& L = g_slab_jobs;
-  if (!L.n) return AVSR_OK;
-  int blocks = 0;
-  for (int j = 0; j < L.n; ++j) { L.job[j].blk0 = blocks; blocks += ((L.job[j].kind ? 9 * L.job[j].Ci * 8 + 8 : L.job[j].F) + 31) / 32; }
-  hipLaunchKernelGGL(slab_final_multi_kernel, dim3(blocks), dim3(1024), 0, s, L);
-  L.n = 0;
-  return hipGetLastError() == hipSuccess ? AVSR_OK : AVSR_ERR_HIP;
-}
-bool slab_defer_push(const float* part, long ld, int nblk, int F, float* out, float* out2, int split, int kind, int Ci, float alpha, float beta,
-                     hipStream_t s) {
-  if (!g_slab_defer) return false;
-  if (g_slab_jobs.n == SLABJ_MAX && slab_flush(s) != AVSR_OK) return false;
-  SlabJob& J = g_slab_jobs.job[g_slab_jobs.n++];
-  J = SlabJob{part, ld, nblk, F, out, out2, split, kind, Ci, 0, alpha, beta};
-  return true;
-}
-}  // namespace avsr
-
-extern "C" int avsr_slab_defer_begin(void) {
-  avsr::g_slab_jobs.n = 0;                            // (a collection left open by an aborted pass is dropped)
-  avsr::g_slab_defer = true;
-  return AVSR_OK;
-}
-extern "C" int avsr_slab_defer_end(void* stream) {
-  avsr::g_slab_defer = false;
-  return avsr::slab_flush(S_(stream));
-}
-
-// partial rows `ld` floats apart (F <= ld): several column ranges of one slab are reduced to different destinations
-int avsr_colsum_final_launch_ld(const float* part, long ld, int nblk, float* out, int F, float alpha, float beta, void* stream) {
-  hipLaunchKernelGGL(colsum_final_kernel, dim3((F + 31) / 32), dim3(1024), 0, S_(stream), part, ld, nblk, out, F, alpha, beta);
-  AVSR_CHECK_LAUNCH();
-  return AVSR_OK;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Many column sums in TWO launches (bias gradients of a train step: one per cell / layer, each a pass over a [B*T, F] record
-// followed by a tiny reduction -- 12 + 33 launches of ~5-20 us before; seq2seq.py:222 tf.gradients of the `bias` variables).
-// The jobs are independent; every block finds its job by its block index in the jobs' prefix sums.
-#define CSM_MAX 32
-struct CsmJob { const float* a; const float* b; float* out; float* part; long lda, ldoa, ldb, ldob; int Ta, Tb, rows, F, rpb, blk0, fblk0; float alpha, beta; };
-struct CsmLaunch { int n; CsmJob job[CSM_MAX]; };
-
-__global__ __launch_bounds__(256) void colsum_multi_partial_kernel(const CsmLaunch L) {
-  __shared__ float red[256];
-  int j = 0;
-#pragma unroll 1
-  for (int k = 1; k < L.n; ++k) if ((int)blockIdx.x >= L.job[k].blk0) j = k;
-  const CsmJob& J = L.job[j];
-  const int blk = blockIdx.x - J.blk0, F = J.F;
-  const int G = F < 256 ? 256 / F : 1;
-  const int r0 = blk * J.rpb, r1 = min(J.rows, r0 + J.rpb);
-  const float* a = J.a; const float* b = J.b;
-  if (G > 1) {
-    const int idx = threadIdx.x, f = idx % F, g = idx / F;
-    float s = 0.f;
-    if (idx < G * F)
-      for (int r = r0 + g; r < r1; r += G) {
-        const float x = a[rowoff(r, J.lda, J.Ta, J.ldoa) + f];
-        s += b ? x * b[rowoff(r, J.ldb, J.Tb, J.ldob) + f] : x;
-      }
-    block_group_reduce(s, idx, F, G, red, J.part + (long)blk * F);
-    return;
-  }
-  // wide records (the [B*T, 4H] gate gradients: 131 MB each): 16-byte loads, eight rows in flight per thread -- a bandwidth stream,
-  // not a latency chain (two 4-byte loads in flight per thread ran at 2.4 TB/s)
-  const bool vec = (F & 3) == 0 && ((uintptr_t)a & 15) == 0 && (J.lda & 3) == 0 && (J.ldoa & 3) == 0 &&
-                   (!b || (((uintptr_t)b & 15) == 0 && (J.ldb & 3) == 0 && (J.ldob & 3) == 0));
-  if (vec) {
-    for (int f = threadIdx.x * 4; f < F; f += 4 * blockDim.x) {
-      f32x4 acc[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-      for (int r = r0; r < r1; r += 8) {
-        f32x4 x[8], y[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const bool in = r + u < r1;
-          x[u] = in ? ld4(a + rowoff(r + u, J.lda, J.Ta, J.ldoa) + f) : f32x4{0.f, 0.f, 0.f, 0.f};
-          if (b) y[u] = in ? ld4(b + rowoff(r + u, J.ldb, J.Tb, J.ldob) + f) : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc[u] += b ? x[u] * y[u] : x[u];
-      }
-      st4(J.part + (long)blk * F + f, ((acc[0] + acc[1]) + (acc[2] + acc[3])) + ((acc[4] + acc[5]) + (acc[6] + acc[7])));
-    }
-    return;
-  }
-  for (int f = threadIdx.x; f < F; f += blockDim.x) {
-    float s0 = 0.f, s1 = 0.f;
-    int r = r0;
-    for (; r + 1 < r1; r += 2) {                        // two independent chains: two loads in flight per thread
-      const float x0 = a[rowoff(r, J.lda, J.Ta, J.ldoa) + f], x1 = a[rowoff(r + 1, J.lda, J.Ta, J.ldoa) + f];
-      s0 += b ? x0 * b[rowoff(r, J.ldb, J.Tb, J.ldob) + f] : x0;
-      s1 += b ? x1 * b[rowoff(r + 1, J.ldb, J.Tb, J.ldob) + f] : x1;
-    }
-    if (r < r1) { const float x0 = a[rowoff(r, J.lda, J.Ta, J.ldoa) + f]; s0 += b ? x0 * b[rowoff(r, J.ldb, J.Tb, J.ldob) + f] : x0; }
-    J.part[(long)blk * F + f] = s0 + s1;
-  }
-}
-
-__global__ __launch_bounds__(1024) void colsum_multi_final_kernel(const CsmLaunch L) {
-  __shared__ double red[32][33];
-  int j = 0;
-#pragma unroll 1
-  for (int k = 1; k < L.n; ++k) if ((int)blockIdx.x >= L.job[k].fblk0) j = k;
-  const CsmJob& J = L.job[j];
-  const int F = J.F, nblk = (J.rows + J.rpb - 1) / J.rpb;
-  const int fl = threadIdx.x & 31, g = threadIdx.x >> 5;
-  const int f = (blockIdx.x - J.fblk0) * 32 + fl;
-  const float* part = J.part;
-  double s = 0.0;
-  if (f < F)
-    for (int i = g; i < nblk; i += 32) s += (double)part[(long)i * F + f];
-  red[g][fl] = s;
-  __syncthreads();
-  if (g == 0 && f < F) {
-    double t = 0.0;
-#pragma unroll
-    for (int k = 0; k < 32; ++k) t += red[k][fl];
-    const float v = J.alpha * (float)t;
-    J.out[f] = J.beta != 0.f ? v + J.beta * J.out[f] : v;
-  }
-}
-
-extern "C" int avsr_colsum_multi(const avsr_colsum_job* jobs, int32_t n, float* scratch, int64_t scratch_floats, void* stream) {
-  if (n <= 0) return AVSR_OK;
-  if (!jobs || !scratch) return AVSR_ERR_ARG;
-  for (int j0 = 0; j0 < n; j0 += CSM_MAX) {              // more than 32 jobs: consecutive launch pairs
-    const int m = n - j0 < CSM_MAX ? n - j0 : CSM_MAX;
-    CsmLaunch L = {};
-    L.n = m;
-    long used = 0;
-    int blocks = 0, fblocks = 0;
-    for (int k = 0; k < m; ++k) {
-      const avsr_colsum_job& Q = jobs[j0 + k];
-      if (!Q.a.ptr || !Q.out || Q.rows <= 0 || Q.F <= 0) return AVSR_ERR_ARG;
-      CsmJob& J = L.job[k];
-      J.a = Q.a.ptr; J.lda = Q.a.ld; J.Ta = Q.a.T; J.ldoa = Q.a.ldo;
-      J.b = Q.b.ptr; J.ldb = Q.b.ld; J.Tb = Q.b.T; J.ldob = Q.b.ldo;
-      J.out = Q.out; J.rows = Q.rows; J.F = Q.F; J.alpha = Q.alpha; J.beta = Q.beta;
-      // <= 256 partial rows per job (the big records are [32000, 1024]: 125 rows per block), >= 32 rows per block
-      int rpb = (Q.rows + 255) / 256;
-      if (rpb < 32) rpb = 32;
-      J.rpb = rpb;
-      const int nblk = (Q.rows + rpb - 1) / rpb;
-      J.part = scratch + used;
-      used += (long)nblk * Q.F;
-      J.blk0 = blocks; blocks += nblk;
-      J.fblk0 = fblocks; fblocks += (Q.F + 31) / 32;
-    }
-    if (used > scratch_floats) return AVSR_ERR_ARG;
-    hipLaunchKernelGGL(colsum_multi_partial_kernel, dim3(blocks), dim3(256), 0, S_(stream), L);
-    AVSR_CHECK_LAUNCH();
-    hipLaunchKernelGGL(colsum_multi_final_kernel, dim3(fblocks), dim3(1024), 0, S_(stream), L);
-    AVSR_CHECK_LAUNCH();
-  }
-  return AVSR_OK;
-}
-
 // Zero up to 8 buffers (32-bit words) per launch: the fills at the start of the backward pass as ONE engine kernel.
 struct ZmLaunch { uint32_t* p[8]; long n[8]; int cnt; };
 __global__ __launch_bounds__(256) void zero_multi_kernel(const ZmLaunch L) {
@@ -723,27 +413,6 @@ __global__ void add_int_kernel(const int32_t* a, int32_t b, int32_t* out) { out[
 extern "C" int avsr_add_int(const int32_t* a, int32_t b, int32_t* out, void* stream) {
   if (!a || !out) return AVSR_ERR_ARG;
   hipLaunchKernelGGL(add_int_kernel, dim3(1), dim3(1), 0, S_(stream), a, b, out);
-  AVSR_CHECK_LAUNCH();
-  return AVSR_OK;
-}
-
-extern "C" int avsr_colsum(const avsr_mat* a, const avsr_mat* b, int32_t rows, int32_t F, float alpha, float beta,
-                           float* out, float* scratch, int64_t scratch_floats, void* stream) {
-  if (!a || !a->ptr || !out || !scratch || rows <= 0 || F <= 0) return AVSR_ERR_ARG;
-  const int maxblk = 2048;                                     // at most 2048 partial rows: the final pass stays one short launch
-  int rpb = rows > 32 * maxblk ? (rows + maxblk - 1) / maxblk : 32;
-  int nblk = (rows + rpb - 1) / rpb;
-  if ((long)nblk * F > scratch_floats) {
-    nblk = (int)(scratch_floats / F);
-    if (nblk < 1) return AVSR_ERR_ARG;
-    rpb = (rows + nblk - 1) / nblk;
-    nblk = (rows + rpb - 1) / rpb;
-  }
-  const int th = 256;
-  hipLaunchKernelGGL(colsum_partial_kernel, dim3(nblk), dim3(th), 0, S_(stream), a->ptr, (long)a->ld, a->T, (long)a->ldo,
-                     b ? b->ptr : nullptr, b ? (long)b->ld : 0, b ? b->T : 0, b ? (long)b->ldo : 0, scratch, rows, F, rpb);
-  AVSR_CHECK_LAUNCH();
-  hipLaunchKernelGGL(colsum_final_kernel, dim3((F + 31) / 32), dim3(1024), 0, S_(stream), scratch, (long)F, nblk, out, F, alpha, beta);
   AVSR_CHECK_LAUNCH();
   return AVSR_OK;
 }
@@ -803,9 +472,7 @@ extern "C" int avsr_embed_grad(const float* dx, const int32_t* fed, float* demb,
   hipLaunchKernelGGL(embed_grad_partial_kernel, dim3(V, nchunk), dim3(E >= 256 ? 256 : ((E + 63) / 64) * 64), 0, S_(stream), dx, fed,
                      scratch, rows, E, V);
   AVSR_CHECK_LAUNCH();
-  hipLaunchKernelGGL(colsum_final_kernel, dim3((V * E + 31) / 32), dim3(1024), 0, S_(stream), scratch, (long)V * E, nchunk, demb, V * E, 1.0f, 0.0f);
-  AVSR_CHECK_LAUNCH();
-  return AVSR_OK;
+  return avsr_colsum_final_launch(scratch, nchunk, demb, V * E, 1.0f, 0.0f, stream);
 }
 
 extern "C" int avsr_dropout_rows(const avsr_mat* x, const avsr_mat* y, int32_t rows, int32_t cols, const int32_t* seed,
