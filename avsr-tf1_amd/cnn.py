@@ -10,9 +10,11 @@ Convolutions run on the frame-resident MFMA kernels of csrc/conv_mfma.hip (avsr_
 fusions around them: the producing convolution's epilogue adds the residual and emits the batch-norm statistics of what it wrote;
 the batch norm itself is never materialised in training -- avsr_bn_finalize turns the statistics into per-channel scale / shift and
 the CONSUMING convolution (forward and weight gradient) applies max(x*scale + shift, 0) while it stages frames in LDS; the weight
-gradient kernel also produces the bias gradient.  Shapes those kernels do not cover fall back to the direct VALU kernels
-(avsr_conv3x3*) or to avsr_im2col + avsr_gemm (the TF kernel [kh,kw,cin,cout] IS the [kh*kw*cin, cout] operand; data gradient =
-transposed GEMM + avsr_col2im, weight gradient = split-K TN GEMM), with BN through avsr_batchnorm_fwd_ex / avsr_batchnorm_bwd.
+gradient kernel also produces the bias gradient.  LipCNN.__init__ makes the one tiering decision, per layer and for all three of its
+ops together: avsr_conv_supported -> those kernels; else a 3x3 layer avsr_conv3x3_supported accepts -> the direct VALU kernels
+(avsr_conv3x3*, csrc/conv_direct.hip: they launch nothing else); else avsr_im2col + avsr_gemm (the TF kernel [kh,kw,cin,cout] IS the
+[kh*kw*cin, cout] operand; data gradient = transposed GEMM + avsr_col2im, weight gradient = split-K TN GEMM).  The two lower tiers
+take their BN through avsr_batchnorm_fwd_ex / avsr_batchnorm_bwd.
 This file only owns buffers and the op order; all arithmetic is in csrc/conv_mfma.hip, conv_wgrad.hip, batchnorm.hip, conv_direct.hip,
 conv.hip, gemm.hip, reduce.hip."""
 import os

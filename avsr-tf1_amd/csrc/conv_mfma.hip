@@ -10,9 +10,10 @@
 // One kernel covers every data-path convolution through a tap list: out[a, b] = sum_t src[a*S + da_t, b*S + db_t] . W_t
 //   forward, stride s:            S = s, taps (i - pt, j - pl)
 //   data gradient, stride 1:      src = dy, taps (pt - i, pl - j), weights read transposed
-//   data gradient, stride 2:      one launch per parity class (ph, pw) of the input pixels: the taps whose parity matches, OS = 2
+//   data gradient, stride 2:      per parity class (ph, pw) of the input pixels the taps whose parity matches, OS = 2: the four classes
+//                                 as sub-position columns of one launch where they fit, one launch per class otherwise
 // The weight gradient is the transposed GEMM (rows = (tap, cin), cols = cout, depth = positions) with the frame and its output
-// gradient staged the same way; per-workgroup partial sums are reduced by avsr_colsum_final_launch.
+// gradient staged the same way (conv_wgrad.hip); per-workgroup partial sums are reduced by slab_reduce (reduce.hip).
 // The epilogue of the data-path kernel can emit per-channel sum / sum-of-squares partials of what it wrote (batch-norm
 // statistics of the producing convolution: removes two full passes over the map per batch norm).
 #include "conv_mfma.h"
@@ -832,61 +833,6 @@ static int cg_launch(CGArgs& A, hipStream_t s, int kind, double flops, bool dry 
   return grid;
 }
 
-// Forward (flip = 0) / stride-1 data gradient (flip = 1) of a 3x3 convolution, same contract as avsr_conv3x3.
-// stats (may be NULL): >= 1024 * 2 * Co floats; returns the number of partial rows written through *nstat.
-int avsr_conv3x3_mfma(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Ci, int Co, int stride, int pad_t,
-                      int pad_l, int Ho, int Wo, int flip, float beta, float* stats, int* nstat, void* stream) {
-  if (!g_conv_mfma) return AVSR_ERR_UNSUPPORTED;
-  if (Co % 4 || (Ci % 4 && Ci >= 4) || pad_t > 1 || pad_l > 1 || (flip && stride != 1)) return AVSR_ERR_UNSUPPORTED;
-  CGArgs A = {};
-  A.src = x; A.w = w; A.bias = bias; A.dst = y; A.stats = stats;
-  A.N = N; A.SH = H; A.SW = W; A.Cs = Ci; A.CsL = (Ci + 3) & ~3;
-  A.DH = Ho; A.DW = Wo; A.Cd = Co; A.OA = Ho; A.OB = Wo; A.S = stride; A.OS = 1; A.oh0 = 0; A.ow0 = 0;
-  A.ntap = 9; A.wmode = flip; A.beta = beta;
-  for (int t = 0; t < 9; ++t) {
-    const int i = t / 3, j = t % 3;
-    if (!flip) A.tap[t] = cgtap1(i - pad_t, j - pad_l, t);
-    else A.tap[t] = cgtap1(pad_t - i, pad_l - j, t);      // dx[h, w] += dy[h + pt - i, w + pl - j] . W[i, j]^T
-  }
-  A.F = cg_frames(H, W, A.CsL, Ho * Wo);
-  const int rc = cg_launch(A, S_(stream), flip ? PROF_CONV_BWD_DATA : PROF_CONV_FWD, 2.0 * N * Ho * Wo * 9.0 * Ci * Co);
-  if (rc < 0) return rc;
-  if (nstat) *nstat = rc;
-  return AVSR_OK;
-}
-
-// stride-2 data gradient: dx [N,H,W,Ci] (+)= from dy [N,Ho,Wo,Co]; one launch per parity class of the input pixels
-int avsr_conv3x3_bwd_data_s2_mfma(const float* dy, const float* w, float* dx, int N, int H, int W, int Ci, int Co, int pad_t, int pad_l, int Ho,
-                                  int Wo, float beta, void* stream) {
-  if (!g_conv_mfma) return AVSR_ERR_UNSUPPORTED;
-  if (Co % 4 || Ci % 4 || pad_t > 1 || pad_l > 1) return AVSR_ERR_UNSUPPORTED;
-  for (int ph = 0; ph < 2; ++ph)
-    for (int pw = 0; pw < 2; ++pw) {
-      CGArgs A = {};
-      A.src = dy; A.w = w; A.bias = nullptr; A.dst = dx; A.stats = nullptr;
-      A.N = N; A.SH = Ho; A.SW = Wo; A.Cs = Co; A.CsL = Co;
-      A.DH = H; A.DW = W; A.Cd = Ci; A.OA = (H - ph + 1) / 2; A.OB = (W - pw + 1) / 2; A.S = 1; A.OS = 2; A.oh0 = ph; A.ow0 = pw;
-      A.wmode = 1; A.beta = beta;
-      int nt = 0;
-      for (int i = 0; i < 3; ++i) {
-        if ((ph + pad_t - i) & 1) continue;
-        for (int j = 0; j < 3; ++j) {
-          if ((pw + pad_l - j) & 1) continue;
-          // dx[2a+ph, 2b+pw] += dy[a + (ph+pt-i)/2, b + (pw+pl-j)/2] . W[i, j]^T   (arithmetic shift: -1/2 -> floor)
-          A.tap[nt++] = cgtap1((ph + pad_t - i) >> 1, (pw + pad_l - j) >> 1, i * 3 + j);
-        }
-      }
-      A.ntap = nt;
-      if (A.OA <= 0 || A.OB <= 0) continue;
-      if (nt == 0) return AVSR_ERR_UNSUPPORTED;
-      A.F = cg_frames(Ho, Wo, A.CsL, A.OA * A.OB);
-      const int rc = cg_launch(A, S_(stream), PROF_CONV_BWD_DATA, 2.0 * N * A.OA * A.OB * nt * (double)Ci * Co);
-      if (rc < 0) return rc;
-    }
-  return AVSR_OK;
-}
-
-
 // =====================================================================================================================
 // Descriptor API (include/avsr_hip.h: avsr_conv_desc): k = 1 or 3, stride 1 or 2, 3..64 channels; BN-ReLU of the input applied by the
 // loader; kernels deeper than one wave's register budget run as several launches over tap groups (the later ones accumulate).
@@ -943,6 +889,13 @@ static int cg_pair_taps(CGArgs& A, const CGTap* taps, int ntaps, CGTap* wide) {
   return nw;
 }
 
+// "pair taps or plain taps": the tail the forward and the stride-1 data gradient share.  flops_per_tap counts the plain taps.
+static int cg_run_paired(CGArgs& A, const CGTap* taps, int nt, hipStream_t s, int kind, double flops_per_tap, bool dry, int* grid_out) {
+  CGTap wide[CG_MAXTAP];
+  const int nw = cg_pair_taps(A, taps, nt, wide);
+  return nw ? cg_run(A, wide, nw, s, kind, flops_per_tap * nt / nw, dry, grid_out) : cg_run(A, taps, nt, s, kind, flops_per_tap, dry, grid_out);
+}
+
 int conv_fwd_impl(const avsr_conv_desc* c, const float* x, const float* w, const float* bias, const float* res, const float* res_sc,
                          const float* res_sh, float* y, float* stats, int32_t* nparts, void* stream, bool dry) {
   CGArgs A = {};
@@ -955,14 +908,21 @@ int conv_fwd_impl(const avsr_conv_desc* c, const float* x, const float* w, const
   const int nt = c->k * c->k;
   for (int t = 0; t < nt; ++t) taps[t] = cgtap1(t / c->k - c->pad_t, t % c->k - c->pad_l, t);
   A.F = cg_frames(c->H, c->W, A.CsL, c->Ho * c->Wo);
-  int grid = 0;
-  CGTap wide[CG_MAXTAP];
-  const int nw = cg_pair_taps(A, taps, nt, wide);
-  const int rc = nw ? cg_run(A, wide, nw, S_(stream), PROF_CONV_FWD, 2.0 * c->N * c->Ho * c->Wo * (double)c->Ci * c->Co * nt / nw, dry, &grid)
-                    : cg_run(A, taps, nt, S_(stream), PROF_CONV_FWD, 2.0 * c->N * c->Ho * c->Wo * (double)c->Ci * c->Co, dry, &grid);
-  if (rc < 0) return rc;
-  if (nparts) *nparts = grid;
-  return AVSR_OK;
+  return cg_run_paired(A, taps, nt, S_(stream), PROF_CONV_FWD, 2.0 * c->N * c->Ho * c->Wo * (double)c->Ci * c->Co, dry, nparts);
+}
+
+// The taps of a stride-2 data gradient that reach parity class (ph, pw) of the input pixels, (da, db, kernel tap) each:
+// dx[2a + ph, 2b + pw] += dy[a + (ph + pt - i) / 2, b + (pw + pl - j) / 2] . W[i, j]^T for the (i, j) whose parities match
+static int cg_class_taps(const avsr_conv_desc* c, int ph, int pw, CGTap* taps) {
+  int nt = 0;
+  for (int i = 0; i < c->k; ++i) {
+    if ((ph + c->pad_t - i) & 1) continue;
+    for (int j = 0; j < c->k; ++j) {
+      if ((pw + c->pad_l - j) & 1) continue;
+      taps[nt++] = cgtap1((ph + c->pad_t - i) >> 1, (pw + c->pad_l - j) >> 1, i * c->k + j);   // arithmetic shift: -1/2 -> floor
+    }
+  }
+  return nt;
 }
 
 // acc (may be NULL): dx = beta*acc + ... instead of beta*dx.  bnb_x != NULL: batch-norm backward stage 1 in the epilogue (see CGArgs):
@@ -972,58 +932,47 @@ int conv_bwd_data_impl(const avsr_conv_desc* c, const float* dy, const float* w,
                               const float* bnb_sh, float* stats, int32_t* nparts) {
   if (c->Ci % 4) return AVSR_ERR_UNSUPPORTED;
   const int k = c->k;
-  auto fuse = [&](CGArgs& A) { A.acc = acc; A.bnb_x = bnb_x; A.bnb_sc = bnb_sc; A.bnb_sh = bnb_sh; A.stats = stats; };
-  if (c->stride == 1) {
+  // the arguments of every form: source dy, weights read transposed, OA x OB product rows written OS pixels apart from (oh0, ow0)
+  auto args = [&](int OA, int OB, int OS, int oh0, int ow0) {
     CGArgs A = {};
     A.src = dy; A.w = w; A.dst = dx;
     A.N = c->N; A.SH = c->Ho; A.SW = c->Wo; A.Cs = c->Co; A.CsL = c->Co;
-    A.DH = c->H; A.DW = c->W; A.Cd = c->Ci; A.OA = c->H; A.OB = c->W; A.S = 1; A.OS = 1;
+    A.DH = c->H; A.DW = c->W; A.Cd = c->Ci; A.OA = OA; A.OB = OB; A.S = 1; A.OS = OS; A.oh0 = oh0; A.ow0 = ow0;
     A.wmode = 1; A.beta = beta;
-    fuse(A);
+    A.acc = acc; A.bnb_x = bnb_x; A.bnb_sc = bnb_sc; A.bnb_sh = bnb_sh; A.stats = stats;   // (all NULL on the per-class path, see below)
+    A.F = cg_frames(c->Ho, c->Wo, A.CsL, OA * OB);
+    return A;
+  };
+  if (c->stride == 1) {
+    CGArgs A = args(c->H, c->W, 1, 0, 0);
     CGTap taps[9];
     for (int t = 0; t < k * k; ++t) taps[t] = cgtap1(c->pad_t - t / k, c->pad_l - t % k, t);   // dx[h, w] += dy[h + pt - i, w + pl - j] . W[i, j]^T
-    A.F = cg_frames(c->Ho, c->Wo, A.CsL, c->H * c->W);
-    CGTap wide[CG_MAXTAP];
-    const int nw = cg_pair_taps(A, taps, k * k, wide);
-    if (nw) return cg_run(A, wide, nw, S_(stream), PROF_CONV_BWD_DATA, 2.0 * c->N * c->H * c->W * (double)c->Ci * c->Co * (k * k) / nw, dry, nparts);
-    return cg_run(A, taps, k * k, S_(stream), PROF_CONV_BWD_DATA, 2.0 * c->N * c->H * c->W * (double)c->Ci * c->Co, dry, nparts);
+    return cg_run_paired(A, taps, k * k, S_(stream), PROF_CONV_BWD_DATA, 2.0 * c->N * c->H * c->W * (double)c->Ci * c->Co, dry, nparts);
   }
   if (k == 3 && c->Ci * 4 <= 64) {
     // all four parity classes of a 2x2 destination cell in one launch: columns (class, channel), rows = cells
-    CGArgs A = {};
-    A.src = dy; A.w = w; A.dst = dx;
-    A.N = c->N; A.SH = c->Ho; A.SW = c->Wo; A.Cs = c->Co; A.CsL = c->Co;
-    A.DH = c->H; A.DW = c->W; A.Cd = c->Ci; A.OA = (c->H + 1) / 2; A.OB = (c->W + 1) / 2; A.S = 1; A.OS = 2;
-    A.wmode = 1; A.beta = beta;
-    fuse(A);
+    CGArgs A = args((c->H + 1) / 2, (c->W + 1) / 2, 2, 0, 0);
     A.nsp = 4; A.SB = 1; A.OSA = 2; A.OSB = 2; A.lin = 0;
-    CGTap wide[CG_MAXTAP];
+    CGTap wide[CG_MAXTAP], cls[9];
     int nw = 0, ntot = 0;
     bool fits = true;
-    for (int ph = 0; ph < 2 && fits; ++ph)
-      for (int pw = 0; pw < 2 && fits; ++pw) {
-        const int sp = ph * 2 + pw;
-        A.sp_dh[sp] = (signed char)ph; A.sp_dw[sp] = (signed char)pw;
-        for (int i = 0; i < 3; ++i) {
-          if ((ph + c->pad_t - i) & 1) continue;
-          for (int j = 0; j < 3; ++j) {
-            if ((pw + c->pad_l - j) & 1) continue;
-            const int da = (ph + c->pad_t - i) >> 1, db = (pw + c->pad_l - j) >> 1;      // arithmetic shift: -1/2 -> floor
-            int kk = 0;
-            for (; kk < nw; ++kk)
-              if (wide[kk].da == da && wide[kk].db == db) break;
-            if (kk == nw) {
-              if (nw == CG_MAXTAP) { fits = false; break; }
-              wide[nw] = cgtap1(da, db, -1);
-              ++nw;
-            }
-            wide[kk].w[sp] = (short)(i * 3 + j);
-            ++ntot;
-          }
+    for (int sp = 0; sp < 4 && fits; ++sp) {
+      const int ph = sp >> 1, pw = sp & 1;
+      A.sp_dh[sp] = (signed char)ph; A.sp_dw[sp] = (signed char)pw;
+      const int nc = cg_class_taps(c, ph, pw, cls);
+      for (int t = 0; t < nc && fits; ++t) {                // the wide tap at this class tap's source offset: found or appended
+        int kk = 0;
+        for (; kk < nw; ++kk)
+          if (wide[kk].da == cls[t].da && wide[kk].db == cls[t].db) break;
+        if (kk == nw) {
+          if (nw == CG_MAXTAP) { fits = false; break; }
+          wide[nw++] = cgtap1(cls[t].da, cls[t].db, -1);
         }
+        wide[kk].w[sp] = cls[t].w[0];
+        ++ntot;
       }
+    }
     if (fits && nw > 0) {
-      A.F = cg_frames(c->Ho, c->Wo, A.CsL, A.OA * A.OB);
       const int rc = cg_run(A, wide, nw, S_(stream), PROF_CONV_BWD_DATA, 2.0 * c->N * A.OA * A.OB * (double)c->Ci * c->Co * ntot / nw, dry, nparts);
       if (rc != AVSR_ERR_UNSUPPORTED) return rc;
     }
@@ -1035,26 +984,15 @@ int conv_bwd_data_impl(const avsr_conv_desc* c, const float* dy, const float* w,
   // convolution (beta == 0 is then refused: the caller orders its contributions so that this one accumulates)
   for (int ph = 0; ph < 2; ++ph)
     for (int pw = 0; pw < 2; ++pw) {
-      CGArgs A = {};
-      A.src = dy; A.w = w; A.dst = dx;
-      A.N = c->N; A.SH = c->Ho; A.SW = c->Wo; A.Cs = c->Co; A.CsL = c->Co;
-      A.DH = c->H; A.DW = c->W; A.Cd = c->Ci; A.OA = (c->H - ph + 1) / 2; A.OB = (c->W - pw + 1) / 2; A.S = 1; A.OS = 2; A.oh0 = ph; A.ow0 = pw;
-      A.wmode = 1; A.beta = beta;
+      const int OA = (c->H - ph + 1) / 2, OB = (c->W - pw + 1) / 2;
+      if (OA <= 0 || OB <= 0) continue;                   // a one-pixel-wide map has no odd class
+      CGArgs A = args(OA, OB, 2, ph, pw);
       CGTap taps[9];
-      int nt = 0;
-      for (int i = 0; i < k; ++i) {
-        if ((ph + c->pad_t - i) & 1) continue;
-        for (int j = 0; j < k; ++j) {
-          if ((pw + c->pad_l - j) & 1) continue;
-          taps[nt++] = cgtap1((ph + c->pad_t - i) >> 1, (pw + c->pad_l - j) >> 1, i * k + j);   // arithmetic shift: -1/2 -> floor
-        }
-      }
-      if (A.OA <= 0 || A.OB <= 0) continue;
+      const int nt = cg_class_taps(c, ph, pw, taps);
       if (nt == 0) {
         if (beta == 0.f) return AVSR_ERR_UNSUPPORTED;
         continue;
       }
-      A.F = cg_frames(c->Ho, c->Wo, A.CsL, A.OA * A.OB);
       const int rc = cg_run(A, taps, nt, S_(stream), PROF_CONV_BWD_DATA, 2.0 * c->N * A.OA * A.OB * (double)c->Ci * c->Co, dry, nullptr);
       if (rc < 0) return rc;
     }

@@ -1,6 +1,6 @@
 // Weight (+ bias) gradient of the frame-resident MFMA convolutions (conv_mfma.h; split out of conv_mfma.hip in round 6): the transposed GEMM
 // (rows = (tap, cin), columns = cout, depth = positions) with the frame staged in LDS and dy streamed; per-workgroup partial slabs, reduced
-// by the column-sum launches of elementwise.hip (deferred to the end of the CNN's backward pass: avsr_slab_defer_*).
+// by slab_reduce (reduce.hip: at once, or deferred to the end of the CNN's backward pass between avsr_slab_defer_begin and _end).
 #include "conv_mfma.h"
 #include "reduce.h"
 
@@ -261,60 +261,6 @@ __global__ __launch_bounds__(256, WG_WPC(MT * NTC)) void conv_wgrad_kernel(const
 
 using namespace avsr;
 
-// weight gradient: dw[3,3,Ci,Co] = beta*dw + sum x (x) dy; scratch >= 256 * 9*Ci*Co floats
-int avsr_conv3x3_bwd_weight_mfma(const float* x, const float* dy, float* dw, int N, int H, int W, int Ci, int Co, int stride, int pad_t,
-                                 int pad_l, int Ho, int Wo, float beta, float* scratch, long scratch_floats, void* stream) {
-  if (!g_conv_mfma) return AVSR_ERR_UNSUPPORTED;
-  if (Co % 4 || (Ci % 4 && Ci >= 4) || pad_t > 1 || pad_l > 1) return AVSR_ERR_UNSUPPORTED;
-  WGArgs A = {};
-  A.x = x; A.dy = dy; A.part = scratch; A.N = N; A.H = H; A.W = W; A.Ci = Ci; A.CiL = (Ci + 3) & ~3; A.Ho = Ho; A.Wo = Wo; A.Co = Co;
-  A.S = stride; A.pt = pad_t; A.pl = pad_l;
-  A.t0 = 0; A.nt = 9; A.kw = 3; A.slab = 9 * Ci * Co; A.want_bias = 0; A.pad = WG_PAD;
-  const int MT = (9 * A.CiL + 15) / 16, NTC = (Co + 15) / 16;
-  if (MT > 18 || NTC > 2 || MT * NTC > 36) return AVSR_ERR_UNSUPPORTED;
-  A.F = cg_frames(H, W, A.CiL + WG_PAD, Ho * Wo);
-  const int nout = 9 * Ci * Co;
-  A.m_opf = fmagic(Ho * Wo); A.m_wo = fmagic(Wo); A.m_w = fmagic(W);
-  if (Ci % 4 == 0) {
-    const int rq = W * Ci / 4;
-    if (rq > 256 || rq < 1) return AVSR_ERR_UNSUPPORTED;
-    const int rpp = 256 / rq;
-    while (A.F > 1 && A.F * ((H + rpp - 1) / rpp) > 12) --A.F;
-    if (A.F * ((H + rpp - 1) / rpp) > 12) return AVSR_ERR_UNSUPPORTED;
-    A.m_rq = fmagic(rq); A.m_per = fmagic(H * rq);
-  } else {
-    while (A.F > 1 && (A.F * H * W * Ci / 4 + 255) / 256 > 4) --A.F;
-    if ((A.F * H * W * Ci / 4 + 255) / 256 > 4 || (long)A.F * H * W * Ci >= 65536) return AVSR_ERR_UNSUPPORTED;
-    A.m_rq = fmagic(Ci); A.m_per = fmagic(H * W * Ci);
-  }
-  if ((long)A.F * ((Ho * Wo + 15) / 16) >= 65536 || (long)N * Ho * Wo * Co * 4 >= (1L << 31)) return AVSR_ERR_UNSUPPORTED;
-  const size_t red = sizeof(float) * 4 * 256;
-  size_t lds = sizeof(float) * (size_t)A.F * (size_t)(H + 2) * (W + 2) * (A.CiL + WG_PAD);
-  if (lds < red) lds = red;
-  if (lds > 64 * 1024) return AVSR_ERR_UNSUPPORTED;
-  int wpc = (int)((150 * 1024) / (lds + 512));
-  if (wpc > 2) wpc = 2;
-  if (wpc < 1) wpc = 1;
-  if (nout > 2048) wpc = 1;                              // large kernels: the partial slabs, not the staging, are the traffic
-  int grid = (N + A.F - 1) / A.F;
-  if (grid > 256 * wpc) grid = 256 * wpc;
-  if ((long)grid * nout > scratch_floats) grid = (int)(scratch_floats / nout);
-  if (grid < 1) return AVSR_ERR_ARG;
-  hipStream_t s = S_(stream);
-  {
-    ProfScope ps(PROF_CONV_BWD_WEIGHT, s, 2.0 * N * Ho * Wo * 9.0 * Ci * Co);
-#define WG_GO(M_, N_, C_) hipLaunchKernelGGL((conv_wgrad_kernel<M_, N_, C_>), dim3(grid), dim3(256), lds, s, A)
-    if (Ci % 4) { if (MT <= 3 && NTC == 1) WG_GO(3, 1, false); else return AVSR_ERR_UNSUPPORTED; }
-    else if (NTC == 1) { if (MT <= 5) WG_GO(5, 1, true); else if (MT <= 9) WG_GO(9, 1, true); else WG_GO(18, 1, true); }
-    else { if (MT <= 5) WG_GO(5, 2, true); else if (MT <= 9) WG_GO(9, 2, true); else WG_GO(18, 2, true); }
-#undef WG_GO
-    if (hipGetLastError() != hipSuccess) return AVSR_ERR_HIP;
-  }
-  if (avsr::slab_defer_push(scratch, nout, grid, nout, dw, nullptr, 0x7fffffff, 0, 0, 1.0f, beta, S_(stream))) return AVSR_OK;
-  return avsr_colsum_final_launch(scratch, grid, dw, nout, 1.0f, beta, stream);
-}
-
-
 // Workgroups per CU and LDS pixel padding of a weight-gradient launch whose passes hold ONE frame: up to WG_WPC(tiles) workgroups where
 // the frames fit the CU's 160 KB side by side -- with + 1 float of padding instead of + 2 where that is what makes the next one fit
 // (36x36x8: 3 x 52 KB; the odd pixel stride costs 4-byte staging stores and measured nothing on the operand reads).
@@ -345,48 +291,57 @@ static int wg_pick_frames(int N, int Fmax, int slots) {
   return bestF;
 }
 
-// final reduction of the pixel-pair weight gradient (below): part [nblk][12*Ci*16 (+16)] with rows (ti, tj', ci), columns (pp, co):
-// dw[ti][tj][ci][co] = sum_blk part[(ti*4 + tj)*Ci + ci][co] + part[(ti*4 + tj + 1)*Ci + ci][8 + co];  dbias[co] = sum_blk bias[co] + bias[8 + co]
-__global__ __launch_bounds__(1024) void wgrad_pair_final_kernel(const float* __restrict__ part, int nblk, int slab, int Ci, float* __restrict__ dw,
-                                                               float* __restrict__ dbias, float beta) {
-  // 32 outputs per workgroup, 32 slices of the slab list each (one thread per (slice, output): 512 slabs = 16 dependent fp64 adds per
-  // thread with four slabs' loads in flight; 8 slices of 64 slabs took 22 us per launch, three launches per step)
-  __shared__ double red[32][33];
-  const int fl = threadIdx.x & 31, g = threadIdx.x >> 5;
-  const int nw = 9 * Ci * 8, f = blockIdx.x * 32 + fl;              // outputs: 9*Ci*8 kernel entries, then 8 bias entries
-  int o0 = -1, o1 = -1;
-  if (f < nw) {
-    const int co = f & 7, ci = (f >> 3) % Ci, t = (f >> 3) / Ci, ti = t / 3, tj = t - ti * 3;
-    o0 = ((ti * 4 + tj) * Ci + ci) * 16 + co;
-    o1 = ((ti * 4 + tj + 1) * Ci + ci) * 16 + 8 + co;
-  } else if (f < nw + 8 && dbias) {
-    o0 = 12 * Ci * 16 + (f - nw);
-    o1 = o0 + 8;
+// The staging plan of one weight-gradient call, worked out once for both forms below.  The caller has set the geometry (N, H, W, Ci, CiL,
+// Ho, Wo, Co as the kernel sees them: the pixel-pair form passes half the width and 16 columns) and bn_sc; this fills A.pad, A.F and the
+// division magics and returns the dynamic LDS bytes and the workgroups per CU, or false where the kernel cannot stage the layer.
+//   occ_tiles   accumulator tiles per wave of the instantiation that will run: wg_occupancy decides pad and the occupancy cap from it;
+//               0 = WG_PAD and two workgroups per CU without asking (the general form with Ci % 4: one instantiation, <3, 1, false>)
+//   slab_floats floats of the (first) launch's slab: above 2048 the partial slabs, not the staging, are the traffic, and the frames per
+//               pass are chosen for 256 workgroups instead of 256 * cap (wg_grid caps the grid the same way).  The pixel-pair slabs are
+//               at most 12*8*16 + 16 floats, so this only ever bites in the general form.
+//   shrink      frames that overflow 64 KB of LDS: true = drop frames until they fit (general form); false = give up, so that the
+//               pixel-pair form falls through to the general one
+struct WGPlan { size_t lds; int wpc, wpc_cap; };
+static bool wg_plan(WGArgs& A, int occ_tiles, int slab_floats, bool shrink, WGPlan* P) {
+  const int N = A.N, H = A.H, W = A.W, Ci = A.Ci, opf = A.Ho * A.Wo;
+  P->wpc_cap = occ_tiles ? wg_occupancy(occ_tiles, H, W, A.CiL, &A.pad) : (A.pad = WG_PAD, 2);
+  A.F = cg_frames(H, W, A.CiL + A.pad, opf);
+  A.m_opf = fmagic(opf); A.m_wo = fmagic(A.Wo); A.m_w = fmagic(W);
+  // a pass must fit the prefetch registers of a staging thread: 12 row pieces (Ci % 4 == 0) or 4 linear pieces
+  if (Ci % 4 == 0) {
+    const int rq = W * Ci / 4;
+    if (rq > 256 || rq < 1) return false;
+    const int rpp = 256 / rq;
+    while (A.F > 1 && A.F * ((H + rpp - 1) / rpp) > 12) --A.F;
+    if (A.F * ((H + rpp - 1) / rpp) > 12) return false;
+    A.m_rq = fmagic(rq); A.m_per = fmagic(H * rq);
+  } else {
+    if (A.bn_sc) return false;                           // the BN-ReLU loader is part of the row-structured staging only (both forms)
+    while (A.F > 1 && (A.F * H * W * Ci / 4 + 255) / 256 > 4) --A.F;
+    if ((A.F * H * W * Ci / 4 + 255) / 256 > 4 || (long)A.F * H * W * Ci >= 65536) return false;
+    A.m_rq = fmagic(Ci); A.m_per = fmagic(H * W * Ci);
   }
-  double s = 0.0;
-  if (o0 >= 0) {
-    int i = g;
-    for (; i + 96 < nblk; i += 128) {
-      const float a0 = part[(long)i * slab + o0], b0 = part[(long)i * slab + o1];
-      const float a1 = part[(long)(i + 32) * slab + o0], b1 = part[(long)(i + 32) * slab + o1];
-      const float a2 = part[(long)(i + 64) * slab + o0], b2 = part[(long)(i + 64) * slab + o1];
-      const float a3 = part[(long)(i + 96) * slab + o0], b3 = part[(long)(i + 96) * slab + o1];
-      s += (double)a0 + (double)b0;
-      s += (double)a1 + (double)b1;
-      s += (double)a2 + (double)b2;
-      s += (double)a3 + (double)b3;
-    }
-    for (; i < nblk; i += 32) s += (double)part[(long)i * slab + o0] + (double)part[(long)i * slab + o1];
-  }
-  red[g][fl] = s;
-  __syncthreads();
-  if (g == 0 && o0 >= 0) {
-    double t = 0.0;
-#pragma unroll
-    for (int k = 0; k < 32; ++k) t += red[k][fl];
-    float* const o = f < nw ? dw + f : dbias + (f - nw);
-    *o = beta != 0.f ? (float)t + beta * *o : (float)t;
-  }
+  const size_t frame = sizeof(float) * (size_t)(H + 2) * (W + 2) * (A.CiL + A.pad);
+  if (shrink) while (A.F > 1 && A.F * frame > 64 * 1024) --A.F;
+  A.F = wg_pick_frames(N, A.F, slab_floats > 2048 ? 256 : 256 * P->wpc_cap);
+  if ((long)A.F * ((opf + 15) / 16) >= 65536 || (long)N * opf * A.Co * 4 >= (1L << 31)) return false;   // 16-bit chunk index, 32-bit dy offsets
+  P->lds = A.F * frame;
+  if (P->lds < sizeof(float) * 4 * 256) P->lds = sizeof(float) * 4 * 256;       // the cross-wave reduction's staging area
+  if (P->lds > 64 * 1024) return false;
+  P->wpc = (int)((160 * 1024) / (P->lds + 512));
+  if (P->wpc > P->wpc_cap) P->wpc = P->wpc_cap;
+  if (P->wpc < 1) P->wpc = 1;
+  return true;
+}
+
+// workgroups of one launch: one per pass of F frames, at most 256 * wpc (256 for slabs above 2048 floats, see wg_plan), and no more than
+// the scratch holds slabs for (< 1: the scratch is too small)
+static int wg_grid(int N, int F, int slab, int wpc, long scratch_floats) {
+  int grid = (N + F - 1) / F;
+  const int cap = 256 * (slab > 2048 ? 1 : wpc);
+  if (grid > cap) grid = cap;
+  if ((long)grid * slab > scratch_floats) grid = (int)(scratch_floats / slab);
+  return grid;
 }
 
 int conv_bwd_weight_impl(const avsr_conv_desc* c, const float* x, const float* dy, float* dw, float* dbias, float beta, float* scratch,
@@ -399,7 +354,7 @@ int conv_bwd_weight_impl(const avsr_conv_desc* c, const float* x, const float* d
   // every 16-column MFMA tile multiplies padding.  dy is read as [N, Ho, Wo/2, 16] (the same bytes): a column is (pixel parity pp,
   // channel), the depth index a PAIR of horizontally adjacent output pixels; the rows run over the union of the two pixels' windows
   // (3 x 4 taps, source step 2 along W): C[(ti, tj', ci)][(pp, co)] is the gradient of tap (ti, tj' - pp) where that is a tap at all.
-  // 6 row tiles per pair instead of 2 x 5 per two positions; the reduction kernel above adds the two parities' valid entries.
+  // 6 row tiles per pair instead of 2 x 5 per two positions; the reduction (a kind-1 job of reduce.hip) adds the two parities' valid entries.
   if (Co == 8 && c->stride == 1 && k == 3 && (Wo & 1) == 0 && Wo == W && Ho == H) {
     WGArgs A = {};
     A.x = x; A.dy = dy; A.part = scratch; A.N = N; A.H = H; A.W = W; A.Ci = Ci; A.CiL = (Ci + 3) & ~3; A.Ho = Ho; A.Wo = Wo / 2; A.Co = 16;
@@ -408,53 +363,23 @@ int conv_bwd_weight_impl(const avsr_conv_desc* c, const float* x, const float* d
     A.fy = fold_y; A.fk = fold_k; A.fC = 8; A.fdx = fold_dx;
     A.slab = 12 * Ci * 16 + (A.want_bias ? 16 : 0);
     const int MT = (12 * A.CiL + 15) / 16;
-    bool ok = (Ci % 4 == 0) ? MT <= 6 : (MT <= 3 && !c->bn_scale);
-    const int wpc_cap = wg_occupancy(MT, H, W, A.CiL, &A.pad);
-    A.F = cg_frames(H, W, A.CiL + A.pad, Ho * A.Wo);
-    A.m_opf = fmagic(Ho * A.Wo); A.m_wo = fmagic(A.Wo); A.m_w = fmagic(W);
-    if (Ci % 4 == 0) {
-      const int rq = W * Ci / 4;
-      ok = ok && rq <= 256 && rq >= 1;
-      if (ok) {
-        const int rpp = 256 / rq;
-        while (A.F > 1 && A.F * ((H + rpp - 1) / rpp) > 12) --A.F;
-        ok = A.F * ((H + rpp - 1) / rpp) <= 12;
-        A.m_rq = fmagic(rq); A.m_per = fmagic(H * rq);
-      }
-    } else {
-      while (A.F > 1 && (A.F * H * W * Ci / 4 + 255) / 256 > 4) --A.F;
-      ok = ok && (A.F * H * W * Ci / 4 + 255) / 256 <= 4 && (long)A.F * H * W * Ci < 65536;
-      A.m_rq = fmagic(Ci); A.m_per = fmagic(H * W * Ci);
-    }
-    if (ok) A.F = wg_pick_frames(N, A.F, 256 * wpc_cap);
-    size_t lds = sizeof(float) * (size_t)A.F * (size_t)(H + 2) * (W + 2) * (A.CiL + A.pad);
-    if (lds < sizeof(float) * 4 * 256) lds = sizeof(float) * 4 * 256;
-    ok = ok && lds <= 64 * 1024 && (long)A.F * ((Ho * A.Wo + 15) / 16) < 65536 && (long)N * Ho * Wo * Co * 4 < (1L << 31);
-    if (ok) {
-      int wpc = (int)((160 * 1024) / (lds + 512));
-      if (wpc > wpc_cap) wpc = wpc_cap;
-      if (wpc < 1) wpc = 1;
-      int grid = (N + A.F - 1) / A.F;
-      if (grid > 256 * wpc) grid = 256 * wpc;
-      if ((long)grid * A.slab > scratch_floats) grid = (int)(scratch_floats / A.slab);
+    WGPlan P;
+    if ((Ci % 4 == 0 ? MT <= 6 : MT <= 3) && wg_plan(A, MT, A.slab, false, &P)) {
+      const int grid = wg_grid(N, A.F, A.slab, P.wpc, scratch_floats);
       if (grid < 1) return AVSR_ERR_ARG;
       if (dry) return AVSR_OK;
       hipStream_t s = S_(stream);
       {
         ProfScope ps(PROF_CONV_BWD_WEIGHT, s, 2.0 * N * Ho * Wo * 9.0 * Ci * Co);
-        if (fold && Ci % 4 && fold_dx) hipLaunchKernelGGL((conv_wgrad_kernel<3, 1, false, false, 2>), dim3(grid), dim3(256), lds, s, A);
-        else if (fold && Ci % 4) hipLaunchKernelGGL((conv_wgrad_kernel<3, 1, false, false, 1>), dim3(grid), dim3(256), lds, s, A);
-        else if (fold && fold_dx) hipLaunchKernelGGL((conv_wgrad_kernel<6, 1, true, false, 2>), dim3(grid), dim3(256), lds, s, A);
-        else if (fold) hipLaunchKernelGGL((conv_wgrad_kernel<6, 1, true, false, 1>), dim3(grid), dim3(256), lds, s, A);
-        else if (Ci % 4) hipLaunchKernelGGL((conv_wgrad_kernel<3, 1, false>), dim3(grid), dim3(256), lds, s, A);
-        else hipLaunchKernelGGL((conv_wgrad_kernel<6, 1, true>), dim3(grid), dim3(256), lds, s, A);
+#define WG_PAIR(M_, C_, F_) hipLaunchKernelGGL((conv_wgrad_kernel<M_, 1, C_, false, F_>), dim3(grid), dim3(256), P.lds, s, A)
+        const int fm = fold ? (fold_dx ? 2 : 1) : 0;
+        if (Ci % 4) { if (fm == 2) WG_PAIR(3, false, 2); else if (fm == 1) WG_PAIR(3, false, 1); else WG_PAIR(3, false, 0); }
+        else { if (fm == 2) WG_PAIR(6, true, 2); else if (fm == 1) WG_PAIR(6, true, 1); else WG_PAIR(6, true, 0); }
+#undef WG_PAIR
         if (hipGetLastError() != hipSuccess) return AVSR_ERR_HIP;
       }
-      const int nout = 9 * Ci * 8 + 8;
-      if (avsr::slab_defer_push(scratch, A.slab, grid, nout, dw, dbias, 0, 1, Ci, 1.0f, beta, s)) return AVSR_OK;
-      hipLaunchKernelGGL(wgrad_pair_final_kernel, dim3((nout + 31) / 32), dim3(1024), 0, s, scratch, grid, A.slab, Ci, dw, dbias, beta);
-      if (hipGetLastError() != hipSuccess) return AVSR_ERR_HIP;
-      return AVSR_OK;
+      // kind 1: the two parities' valid entries of every tap, then the bias columns (reduce.hip)
+      return slab_reduce(scratch, A.slab, grid, 9 * Ci * 8 + 8, dw, dbias, 0, 1, Ci, 1.0f, beta, s);
     }
   }
   WGArgs A = {};
@@ -469,35 +394,12 @@ int conv_bwd_weight_impl(const avsr_conv_desc* c, const float* x, const float* d
   // (tiles of the form the first launch takes: the tap groups of one call share the staging layout)
   const int mt_first = ((k * k < G ? k * k : G) * A.CiL + 15) / 16;
   const int tiles_first = (mt_first <= 5 ? 5 : (mt_first <= 9 ? 9 : 18)) * (NTC == 1 ? 1 : (NTC == 2 ? 2 : 4));
-  const int wpc_cap = (Ci % 4 == 0) ? wg_occupancy(tiles_first, H, W, A.CiL, &A.pad) : (A.pad = WG_PAD, 2);
-  A.F = cg_frames(H, W, A.CiL + A.pad, Ho * Wo);
-  A.m_opf = fmagic(Ho * Wo); A.m_wo = fmagic(Wo); A.m_w = fmagic(W);
-  if (Ci % 4 == 0) {
-    const int rq = W * Ci / 4;
-    if (rq > 256 || rq < 1) return AVSR_ERR_UNSUPPORTED;
-    const int rpp = 256 / rq;
-    while (A.F > 1 && A.F * ((H + rpp - 1) / rpp) > 12) --A.F;
-    if (A.F * ((H + rpp - 1) / rpp) > 12) return AVSR_ERR_UNSUPPORTED;
-    A.m_rq = fmagic(rq); A.m_per = fmagic(H * rq);
-  } else {
-    if (c->bn_scale) return AVSR_ERR_UNSUPPORTED;
-    while (A.F > 1 && (A.F * H * W * Ci / 4 + 255) / 256 > 4) --A.F;
-    if ((A.F * H * W * Ci / 4 + 255) / 256 > 4 || (long)A.F * H * W * Ci >= 65536) return AVSR_ERR_UNSUPPORTED;
-    A.m_rq = fmagic(Ci); A.m_per = fmagic(H * W * Ci);
-  }
-  while (A.F > 1 && sizeof(float) * (size_t)A.F * (size_t)(H + 2) * (W + 2) * (A.CiL + A.pad) > 64 * 1024) --A.F;
+  WGPlan P;
   {
     const int nt0 = k * k < G ? k * k : G;
-    A.F = wg_pick_frames(N, A.F, (nt0 * Ci * Co + Co > 2048) ? 256 : 256 * wpc_cap);
+    if (!wg_plan(A, Ci % 4 == 0 ? tiles_first : 0, nt0 * Ci * Co + Co, true, &P)) return AVSR_ERR_UNSUPPORTED;
   }
-  if ((long)A.F * ((Ho * Wo + 15) / 16) >= 65536 || (long)N * Ho * Wo * Co * 4 >= (1L << 31)) return AVSR_ERR_UNSUPPORTED;
-  const size_t red = sizeof(float) * 4 * 256;
-  size_t lds = sizeof(float) * (size_t)A.F * (size_t)(H + 2) * (W + 2) * (A.CiL + A.pad);
-  if (lds < red) lds = red;
-  if (lds > 64 * 1024) return AVSR_ERR_UNSUPPORTED;
-  int wpc = (int)((160 * 1024) / (lds + 512));
-  if (wpc > wpc_cap) wpc = wpc_cap;
-  if (wpc < 1) wpc = 1;
+  const size_t lds = P.lds;
   hipStream_t s = S_(stream);
   bool bias_done = dbias == nullptr;
   // deep layers (64 destination channels, more (tap, channel) rows than one wave's accumulators hold): the row-split form, one launch
@@ -517,10 +419,7 @@ int conv_bwd_weight_impl(const avsr_conv_desc* c, const float* x, const float* d
     A.slab = wF + (A.want_bias ? Co : 0);
     const int MT = rs ? ((A.nt * A.CiL + 3) / 4 + 15) / 16 : (A.nt * A.CiL + 15) / 16;      // (rs: row tiles per WAVE)
     if (Ci % 4 && (MT > 3 || NTC != 1)) return AVSR_ERR_UNSUPPORTED;
-    int grid = (N + A.F - 1) / A.F;
-    const int cap = 256 * (A.slab > 2048 ? 1 : wpc);      // large kernels: the partial slabs, not the staging, are the traffic
-    if (grid > cap) grid = cap;
-    if ((long)grid * A.slab > scratch_floats) grid = (int)(scratch_floats / A.slab);
+    const int grid = wg_grid(N, A.F, A.slab, P.wpc, scratch_floats);
     if (grid < 1) return AVSR_ERR_ARG;
     if (dry) continue;
     {
@@ -543,15 +442,10 @@ int conv_bwd_weight_impl(const avsr_conv_desc* c, const float* x, const float* d
 #undef WG_GO
       if (hipGetLastError() != hipSuccess) return AVSR_ERR_HIP;
     }
-    int rc;
-    if (A.want_bias) {                                     // weight and bias gradients of the slab in one reduction launch
-      if (avsr::slab_defer_push(scratch, A.slab, grid, A.slab, dw + (long)t0 * Ci * Co, dbias, wF, 0, 0, 1.0f, beta, s)) rc = AVSR_OK;
-      else rc = avsr_colsum_final_launch_split(scratch, A.slab, grid, dw + (long)t0 * Ci * Co, dbias, wF, A.slab, 1.0f, beta, stream);
-      bias_done = true;
-    } else {
-      if (avsr::slab_defer_push(scratch, A.slab, grid, wF, dw + (long)t0 * Ci * Co, nullptr, 0x7fffffff, 0, 0, 1.0f, beta, s)) rc = AVSR_OK;
-      else rc = avsr_colsum_final_launch_ld(scratch, A.slab, grid, dw + (long)t0 * Ci * Co, wF, 1.0f, beta, stream);
-    }
+    // weight and (first launch) bias gradients of the slab in one reduction job
+    const int rc = slab_reduce(scratch, A.slab, grid, A.slab, dw + (long)t0 * Ci * Co, A.want_bias ? dbias : nullptr,
+                               A.want_bias ? wF : 0x7fffffff, 0, 0, 1.0f, beta, s);
+    bias_done = true;
     if (rc != AVSR_OK) return rc;
     // (deferred reductions: the next tap group of this call must not overwrite the slabs just recorded)
     if (avsr::slab_deferring()) { scratch += (long)grid * A.slab; scratch_floats -= (long)grid * A.slab; A.part = scratch; }

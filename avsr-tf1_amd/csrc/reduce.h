@@ -3,17 +3,17 @@
 #include "common.h"
 
 namespace avsr {
-// Record the final reduction of a set of partial slabs instead of launching it (between avsr_slab_defer_begin and _end);
-// false: not deferring, the caller launches as before.  kind 0: columns [0, split) -> out, [split, F) -> out2;
-// kind 1: the pixel-pair slab of an 8-channel weight gradient (conv_wgrad.hip), alpha is not applied.
-bool slab_defer_push(const float* part, long ld, int nblk, int F, float* out, float* out2, int split, int kind, int Ci, float alpha, float beta,
-                     hipStream_t s);
+// The final reduction of a set of partial slabs (a FinalJob of reduce.hip): out[f] = alpha * sum_i part[i * ld + column(f)] + beta * out[f].
+// kind 0: columns [0, split) -> out, [split, F) -> out2 (split >= F: no out2);  kind 1: the pixel-pair slab of an 8-channel weight gradient
+// (conv_wgrad.hip; F is not read).  Between avsr_slab_defer_begin and _end the job is only recorded -- the slabs must stay untouched
+// until _end, which runs every recorded job in one launch -- otherwise it is launched here.  Either way the same kernel sums in the same order.
+int slab_reduce(const float* part, long ld, int nblk, int F, float* out, float* out2, int split, int kind, int Ci, float alpha, float beta,
+                hipStream_t s);
 bool slab_deferring();
 }  // namespace avsr
 
 // The final pass alone, over nblk partial rows written by another kernel: out[f] = alpha * sum_i part[i][f] + beta * out[f].
-// _ld: rows `ld` floats apart (F <= ld);  _split: columns [0, split) -> out, [split, F) -> out2.
+// _split: rows `ld` floats apart (F <= ld), columns [0, split) -> out, [split, F) -> out2.
 int avsr_colsum_final_launch(const float* part, int nblk, float* out, int F, float alpha, float beta, void* stream);
-int avsr_colsum_final_launch_ld(const float* part, long ld, int nblk, float* out, int F, float alpha, float beta, void* stream);
 int avsr_colsum_final_launch_split(const float* part, long ld, int nblk, float* out, float* out2, int split, int F, float alpha, float beta,
                                    void* stream);

@@ -5,9 +5,10 @@
 // Who runs what:
 //   avsr_colsum                          one job through both passes (32 rows per block, <= 2048 blocks)
 //   avsr_colsum_multi                    the train step's bias gradients: all jobs of a half-pass in two launches
-//   avsr_colsum_final_launch[_ld|_split] the final pass alone over partial rows another kernel wrote (split-K / weight-gradient slabs,
-//                                        batch-norm statistics, the embedding gradient)
-//   slab_defer_push                      the same, recorded between avsr_slab_defer_begin and _end and run as one launch at the end
+//   avsr_colsum_final_launch[_split]     the final pass alone over partial rows another kernel wrote (split-K / direct weight-gradient
+//                                        slabs, batch-norm statistics, the embedding gradient)
+//   slab_reduce                          the same for the slabs of conv_wgrad.hip (either kind of job): launched at once, or recorded
+//                                        between avsr_slab_defer_begin and _end and run as one launch at the end
 #include "reduce.h"
 #include "avsr_hip.h"
 
@@ -176,12 +177,13 @@ static int slab_flush(hipStream_t s) {
   return rc;
 }
 bool slab_deferring() { return g_slab_defer; }
-bool slab_defer_push(const float* part, long ld, int nblk, int F, float* out, float* out2, int split, int kind, int Ci, float alpha, float beta,
-                     hipStream_t s) {
-  if (!g_slab_defer) return false;
-  if (g_slab_jobs.n == RED_JOBS && slab_flush(s) != AVSR_OK) return false;
-  g_slab_jobs.job[g_slab_jobs.n++] = FinalJob{part, ld, nblk, F, out, out2, split, kind, Ci, kind ? 1.0f : alpha, beta};
-  return true;
+int slab_reduce(const float* part, long ld, int nblk, int F, float* out, float* out2, int split, int kind, int Ci, float alpha, float beta,
+                hipStream_t s) {
+  const FinalJob J{part, ld, nblk, F, out, out2, split, kind, Ci, alpha, beta};
+  if (!g_slab_defer) return final_launch_one(J, s);
+  if (g_slab_jobs.n == RED_JOBS) { const int rc = slab_flush(s); if (rc != AVSR_OK) return rc; }
+  g_slab_jobs.job[g_slab_jobs.n++] = J;
+  return AVSR_OK;
 }
 
 }  // namespace avsr
@@ -200,9 +202,6 @@ extern "C" int avsr_slab_defer_end(void* stream) {
 
 int avsr_colsum_final_launch(const float* part, int nblk, float* out, int F, float alpha, float beta, void* stream) {
   return final_launch_one(FinalJob{part, (long)F, nblk, F, out, nullptr, 0x7fffffff, 0, 0, alpha, beta}, stream);
-}
-int avsr_colsum_final_launch_ld(const float* part, long ld, int nblk, float* out, int F, float alpha, float beta, void* stream) {
-  return final_launch_one(FinalJob{part, ld, nblk, F, out, nullptr, 0x7fffffff, 0, 0, alpha, beta}, stream);
 }
 int avsr_colsum_final_launch_split(const float* part, long ld, int nblk, float* out, float* out2, int split, int F, float alpha, float beta,
                                    void* stream) {

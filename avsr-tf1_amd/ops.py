@@ -545,6 +545,12 @@ def conv3x3(x, w, bias, y, N, H, W, Ci, Co, stride, pad_t, pad_l, Ho, Wo, flip=0
           "avsr_conv3x3")
 
 
+def conv_set_mfma(on):
+    """avsr_conv_set_mfma: 0 = the descriptor API refuses every layer (avsr_conv_supported == 0), so a LipCNN built afterwards runs on the
+    direct kernels and im2col + GEMM; 1 (the default) restores it.  Process-wide: for tests and A/B timing."""
+    check(_L().avsr_conv_set_mfma(int(on)), "avsr_conv_set_mfma")
+
+
 def conv_desc(N, H, W, Ci, Co, k, stride, pad_t, pad_l, Ho, Wo, bn=None):
     """avsr_conv_desc; bn = (scale, shift) device vectors when the input is normalised by the loader."""
     from ._lib import ConvDesc

@@ -519,16 +519,19 @@ int avsr_im2col(const float* x, float* col, int32_t N, int32_t H, int32_t W, int
                 int32_t pad_t, int32_t pad_l, int32_t Ho, int32_t Wo, void* stream);
 int avsr_col2im(const float* dcol, float* dx, int32_t N, int32_t H, int32_t W, int32_t C, int32_t kh, int32_t kw, int32_t stride,
                 int32_t pad_t, int32_t pad_l, int32_t Ho, int32_t Wo, float beta, void* stream);
-/* Direct 3x3 convolutions on NHWC maps for the shallow layers of the lip CNN (cin*cout <= 256; avsr_conv3x3_supported):
+/* Direct 3x3 convolutions on NHWC maps for the shallow layers of the lip CNN (cin*cout <= 1024, cout in {4, 8, 16, 32}, cin in {1..3, 4n};
+ * avsr_conv3x3_supported), on the fp32 VALU (csrc/conv_direct.hip) -- these entry points never run the MFMA kernels below:
  * the same tf.layers.conv2d(3x3, SAME) and its gradients as the im2col + avsr_gemm route, without the 9x operand.
  *   avsr_conv3x3(flip=0): y = conv(x, w[3,3,Ci,Co]) + bias (+ beta*y).
  *   avsr_conv3x3(flip=1): stride-1 data gradient: x = dy [.,Ci = cout], y = dx [.,Co = cin], w = the FORWARD kernel [3,3,Co,Ci].
  *   avsr_conv3x3_bwd_data_s2: data gradient of a stride-2 conv (dx [N,H,W,Ci] from dy [N,Ho,Wo,Co]).
- *   avsr_conv3x3_bwd_weight: dw[3,3,Ci,Co] = beta*dw + sum x (x) dy; Co in {4, 8, 16}; scratch >= ceil(N/4) * (256/(9*Ci)) * 9*Ci*Co floats (fewer blocks if smaller). */
+ *   avsr_conv3x3_bwd_weight: dw[3,3,Ci,Co] = beta*dw + sum x (x) dy; Co in {4, 8, 16, 32}; scratch >= ceil(N/4) * (256/(9*Ci)) * 9*Ci*Co floats (fewer blocks if smaller). */
 int avsr_conv3x3_supported(int32_t Ci, int32_t Co, int32_t H, int32_t W);
-/* The three entry points below run the frame-resident MFMA kernels of csrc/conv_mfma.hip where they cover the shape (whole frames
- * staged in LDS, implicit GEMM on v_mfma_f32_16x16x4_f32) and the direct VALU kernels otherwise; this switch (default 1) forces the
- * latter (A/B timing, tests). */
+/* The frame-resident MFMA kernels (csrc/conv_mfma.hip, conv_wgrad.hip: whole frames staged in LDS, implicit GEMM on
+ * v_mfma_f32_16x16x4_f32) are reached through the descriptor API below and nowhere else.  The caller picks the tier per layer:
+ * avsr_conv_supported -> the descriptor API; else k == 3 and avsr_conv3x3_supported -> the direct kernels above; else im2col + avsr_gemm.
+ * This switch (default 1): 0 makes avsr_conv_supported and its siblings answer 0 and the descriptor entry points return
+ * AVSR_ERR_UNSUPPORTED, which sends every layer to the other two tiers (A/B timing, tests). */
 int avsr_conv_set_mfma(int32_t on);
 /* Frame-resident MFMA convolutions of the lip CNN through ONE descriptor (csrc/conv_mfma.hip; tf.layers.conv2d of video.py:18-30 with
  * k = 1 (the stride-2 projection shortcut, video.py:70-75) or 3, stride 1 / 2, Ci in {1..3, 4n}, Co = 4n <= 64):
@@ -543,7 +546,7 @@ int avsr_conv_set_mfma(int32_t on);
  *   avsr_conv_bwd_weight: dw = beta*dw + sum x (x) dy, dbias (may be NULL) = beta*dbias + column sums of dy (same pass over dy);
  *     scratch >= 256 * (k*k*Ci*Co + Co) floats.
  * AVSR_ERR_UNSUPPORTED (-3) for shapes outside the kernels' register / LDS budget (avsr_conv_supported == 0): the caller then uses
- * im2col + avsr_gemm. */
+ * the direct kernels or im2col + avsr_gemm for the whole layer. */
 typedef struct avsr_conv_desc {
   int32_t N, H, W, Ci, Co, k, stride, pad_t, pad_l, Ho, Wo, pad_;
   const float* bn_scale;

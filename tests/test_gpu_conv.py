@@ -32,6 +32,11 @@ def _close(a, b, tol=2e-5):
 @pytest.mark.parametrize("N,H,Ci,Co,s", [(3, 12, 3, 8, 1), (2, 12, 8, 8, 1), (2, 12, 8, 16, 2), (2, 9, 16, 16, 1), (5, 9, 16, 16, 2), (2, 7, 4, 4, 2),
                                         (3, 18, 16, 32, 2), (19, 9, 32, 32, 1)])
 def test_direct_conv3x3_forward_and_gradients(N, H, Ci, Co, s):
+    """avsr_conv3x3 / _bwd_data_s2 / _bwd_weight launch the direct VALU kernels of csrc/conv_direct.hip (conv3x3_kernel,
+    conv3x3_bwd_data_s2_kernel, conv3x3_bwd_weight_kernel) and nothing else, so this is their kernel-level parity: forward with bias at
+    stride 1 / 2, the flipped stride-1 and the gathering stride-2 data gradient, the weight gradient with one and with two (tap, channel)
+    pairs per thread (9*Ci above 256) and every destination width 4 / 8 / 16 / 32.  (While these entry points still tried the MFMA kernels
+    first, all eight shapes were taken there and the kernels named here were never launched.)"""
     from avsr_tf1_amd import ops
     rng = np.random.default_rng(H * 100 + Ci * 10 + Co + s)
     W = H
@@ -339,3 +344,56 @@ def test_weight_gradient_with_the_batchnorm_backward_in_its_operand_fetch(N, H, 
     b64 = torch.zeros(Co, dtype=torch.float64, requires_grad=True)
     (_ref_conv(xin, w64, b64, st) * dx.double().cpu()).sum().backward()
     assert _close(dw1.cpu().numpy() - 0.5, w64.grad.numpy(), 5e-5) and _close(db1.cpu().numpy() + 0.25, b64.grad.numpy(), 5e-5)
+
+
+# ------------------------------------------------------------------------------------------------
+# the tiers below the MFMA kernels at model level: direct VALU kernels and im2col + GEMM, with the batch norm as passes of its own
+@pytest.fixture
+def mfma_off():
+    """avsr_conv_set_mfma(0) for the duration of a test: every LipCNN built meanwhile lands on the direct / im2col tiers."""
+    from avsr_tf1_amd import ops
+    ops.conv_set_mfma(0)
+    try:
+        yield
+    finally:
+        ops.conv_set_mfma(1)
+
+
+@pytest.mark.parametrize("filters,dense", [((4, 8), 8), ((8, 64), 16)])
+def test_lip_cnn_fallback_tiers(filters, dense, mfma_off):
+    """One train step of the visual-only model on 12x12x3 crops with the MFMA tier switched off, against the oracle with the bounds of
+    test_gpu_fuzz.py::test_random_lip_cnn_geometry (1e-4; 2e-4 * scale + 1e-6).  Between them the two ladders run the direct forward at
+    stride 1 and 2, the flipped stride-1 and the stride-2 direct data gradients, the direct weight gradient, im2col + GEMM + col2im for
+    3x3/1, 3x3/2 and 1x1/2, and the batch norm outside the convolutions (avsr_batchnorm_fwd_ex / avsr_batchnorm_bwd).  No ReLU-kink
+    escape: the fixtures' smallest ReLU input is 1.1e-4 and 3.1e-5 in the oracle, asserted below."""
+    from test_gpu_model import make
+    from avsr_tf1_amd.model import Batch, Seq2SeqModel
+    O, ocfg, mcfg, W, batch = make("c3_video_cnn_bi", B=3, Ta=16, Tv=4, L=5, video_hw=(12, 12, 3), use_dropout=False, cnn_filters=filters,
+                                   cnn_dense_units=dense, video_feat=dense)
+    ref = O.train_step(W, None, ocfg, batch)
+    assert ref["relu_margin"] >= 1e-5, ref["relu_margin"]
+    model = Seq2SeqModel(mcfg, weights=W)
+    db = Batch.from_numpy(batch)
+    logits = model.forward_train(db)
+    model.backward()
+    model.apply_update()
+    torch.cuda.synchronize()
+    cnn = model._cur[0]["enc"]["video"]["cnn"]
+    convs = {op[1]: (op[4], op[5]) for op in cnn.ops if op[0] == "conv"}          # name -> (k, stride)
+    assert not cnn.mfma
+    assert cnn.direct | set(cnn.col) == set(convs) and not cnn.direct & set(cnn.col)
+    if filters == (4, 8):
+        assert set(cnn.col) == {"res_block_1_shortcut"} and convs["res_block_1_shortcut"] == (1, 2)
+        assert cnn.direct == {n for n, (k, _) in convs.items() if k == 3} and len(cnn.direct) == 5
+    else:
+        assert set(cnn.col) == {"res_block_1_shortcut", "res_block_1_conv1", "res_block_1_conv2"}
+        assert sorted(convs[n] for n in cnn.col) == [(1, 2), (3, 1), (3, 2)]
+        assert cnn.direct == {"layer0", "res_block_0_conv1", "res_block_0_conv2"}
+    tag = (filters, dense)
+    assert np.abs(logits.cpu().numpy() - ref["logits"]).max() < 1e-4, tag
+    assert abs(float(model.loss.item()) - ref["loss"]) < 1e-4, tag
+    assert abs(float(model.gnorm.item()) - ref["global_norm"]) < 1e-4 * max(1.0, ref["global_norm"]), tag
+    grads = model.export_tf_weights("grads")
+    for k, g in ref["grads"].items():
+        scale = max(1e-3, np.abs(g).max())
+        assert np.abs(grads[k] - g).max() < 2e-4 * scale + 1e-6, (tag, k, np.abs(grads[k] - g).max(), scale)
