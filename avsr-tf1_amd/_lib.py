@@ -132,6 +132,12 @@ class LogmelArgs(C.Structure):
                [(n, C.c_void_p) for n in ("wav", "wav_len", "hann", "twiddle", "mel_lo", "mel_cnt", "mel_ptr", "mel_w", "out", "out_len")]
 
 
+class CtcArgs(C.Structure):
+    _fields_ = [("B", C.c_int32), ("T", C.c_int32), ("L", C.c_int32), ("C", C.c_int32), ("ld", C.c_int64)] + \
+               [(n, C.c_void_p) for n in ("z", "labels", "labels_len", "in_len", "denom")] + [("weight", C.c_float), ("pad_", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("nll", "status", "utt_loss", "dz", "ws")] + [("ws_floats", C.c_int64)]
+
+
 class ColsumJob(C.Structure):
     _fields_ = [("a", Mat), ("b", Mat), ("out", C.c_void_p), ("rows", C.c_int32), ("F", C.c_int32), ("alpha", C.c_float), ("beta", C.c_float)]
 
@@ -141,7 +147,7 @@ class TransposeJob(C.Structure):
 
 
 _STRUCTS = {"avsr_dec_layer": DecLayer, "avsr_mat": Mat, "avsr_gemm_desc": GemmDesc, "avsr_rnn_layer": RnnLayer, "avsr_rnn_stack": RnnStack,
-            "avsr_conv_desc": ConvDesc, "avsr_conv3d_desc": Conv3dDesc, "avsr_logmel_args": LogmelArgs, "avsr_attn_mech": AttnMech, "avsr_attn_rnn": AttnRnn, "avsr_transpose_job": TransposeJob,
+            "avsr_conv_desc": ConvDesc, "avsr_conv3d_desc": Conv3dDesc, "avsr_logmel_args": LogmelArgs, "avsr_ctc_args": CtcArgs, "avsr_attn_mech": AttnMech, "avsr_attn_rnn": AttnRnn, "avsr_transpose_job": TransposeJob,
             "avsr_colsum_job": ColsumJob, "avsr_beam_lm": BeamLm}
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -183,6 +189,8 @@ _SIGS = {
     "avsr_conv3d_bn_finalize": [_vp, _i32, _i32, _i64, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "avsr_logmel_supported": [_i32, _i32, _i32, _i32, _i32],
     "avsr_logmel_fwd": [C.POINTER(LogmelArgs), _vp],
+    "avsr_ctc_loss": [C.POINTER(CtcArgs), _vp],
+    "avsr_ctc_best_path": [_vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp],
     "avsr_batchnorm_apply": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp],
     "avsr_attn_rnn_bwd": [C.POINTER(AttnRnn), _vp],
     "avsr_beam_gather_tree": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
@@ -245,8 +253,8 @@ _SIGS = {
     "avsr_prof_begin": [_i32],
     "avsr_prof_end": [C.POINTER(_i32), C.POINTER(_f32), C.POINTER(C.c_double)],
 }
-# every symbol the library must export: the table above plus the four whose return type load() sets on its own
-EXPORTS = ["avsr_abi_version", "avsr_sizeof", "avsr_attn_rnn_fused_ws_floats", "avsr_conv3d_wgrad_scratch_floats"] + list(_SIGS)
+# every symbol the library must export: the table above plus the five whose return type load() sets on its own
+EXPORTS = ["avsr_abi_version", "avsr_sizeof", "avsr_attn_rnn_fused_ws_floats", "avsr_conv3d_wgrad_scratch_floats", "avsr_ctc_ws_floats"] + list(_SIGS)
 
 _lib = None
 
@@ -283,6 +291,8 @@ def load():
     lib.avsr_attn_rnn_fused_ws_floats.restype = C.c_int64
     lib.avsr_conv3d_wgrad_scratch_floats.argtypes = [C.POINTER(Conv3dDesc)]
     lib.avsr_conv3d_wgrad_scratch_floats.restype = C.c_int64
+    lib.avsr_ctc_ws_floats.argtypes = [_i32, _i32, _i32]
+    lib.avsr_ctc_ws_floats.restype = C.c_int64
     for name, st in _STRUCTS.items():
         n = lib.avsr_sizeof(name.encode())
         if n != C.sizeof(st):

@@ -24,6 +24,10 @@ Shallow fusion of a language model into beam search (not in the reference, which
 `lm_checkpoint` (a checkpoint written by `LM.train`), `lm_weight` (0.3: a conventional value, not a tuned one),
 `lm_units_per_layer` ((256,)), `lm_embedding_size` (128), `lm_cell_type` ('lstm') arrive through **kwargs; `evaluate` then scores an
 unfinished beam's continuation with log p_model + lm_weight * log p_lm (csrc/beam_lm.hip).
+Hybrid CTC / attention training (not in the reference, which only reserves `use_ctc` in its hyper-parameters): `use_ctc` (False),
+`ctc_weight` (0.3: a conventional value, not a tuned one) arrive through **kwargs; a CTC head on the audio (else video) encoder adds
+ctc_weight * CTC loss per label token to the step's loss, and `evaluate` also reports that head's best-path error rate under the key
+'ctc_' + unit (csrc/ctc.hip).
 """
 import glob
 import os
@@ -178,6 +182,7 @@ class AVSR(object):
             video_feat=feats.get('video', 128), audio_feat=feats.get('audio', 80),
             batch_normalisation=batch_normalisation, regress_aus=regress_aus,
             au_loss_weight=kwargs.get('au_loss_weight', 10.0),
+            use_ctc=bool(kwargs.get('use_ctc', False)), ctc_weight=float(kwargs.get('ctc_weight', 0.3)),
             recurrent_l2=None if optimiser == 'AdamW' else recurrent_l2_regularisation,     # avsr.py:168
             optimiser=optimiser, weight_decay=weight_decay, clip_gradients=clip_gradients, max_gradient_norm=max_gradient_norm,
             learning_rate=learning_rate, warmup_steps=kwargs.get('warmup_steps', 750), lr_decay_steps=lr_decay_steps, loss_fun=loss_fun, label_smoothing=float(label_smoothing),
@@ -434,7 +439,7 @@ class AVSR(object):
 
     def evaluate(self, checkpoint_path, epoch=None, alignments_outdir='./alignments/tmp/', beam_graphs_outdir='./beam_graphs/tmp/'):
         self.restore(checkpoint_path)                         # the path argument is honoured, as in avsr.py:328-331
-        predictions_dict, labels_dict = {}, {}
+        predictions_dict, labels_dict, ctc_dict = {}, {}, {}
         it = self._iterator('evaluate')
         if hasattr(it, "reuse_buffers") and os.environ.get("AVSR_IO_PREFETCH", "1") != "0":
             it.reuse_buffers = True                       # a batch is decoded (host-synchronised) before the next one is asked for
@@ -453,11 +458,16 @@ class AVSR(object):
                 file = names[idx].decode('utf-8')
                 predictions_dict[file] = [self._unit_dict[int(s)] for s in ids[idx]]
                 labels_dict[file] = [self._unit_dict[int(s)] for s in bd.labels[idx]]
+            if self._cfg.use_ctc:                             # the CTC head's best path, scored like the decoder's output
+                for idx, seq in enumerate(self._model.ctc_best_path(batch)):
+                    ctc_dict[names[idx].decode('utf-8')] = [self._unit_dict[s] for s in seq]
         uer, uer_dict = compute_wer(predictions_dict, labels_dict)
         error_rate = {self._unit: uer}
         if self._unit == 'character':
             wer, _wer_dict = compute_wer(predictions_dict, labels_dict, split_words=True)
             error_rate['word'] = wer
+        if self._cfg.use_ctc:
+            error_rate['ctc_' + self._unit], _ctc_uer_dict = compute_wer(ctc_dict, labels_dict)
         if self._rank == 0:
             outdir = path.join('predictions', path.split(path.split(checkpoint_path)[0])[-1])
             makedirs(outdir, exist_ok=True)

@@ -36,6 +36,11 @@ class ModelConfig:
     batch_normalisation: bool = True
     regress_aus: bool = False
     au_loss_weight: float = 10.0
+    # CTC auxiliary loss on the encoder outputs (not in the reference, whose hyper-parameter bag only reserves the switch): a Dense head
+    # over vocab_size + 1 classes (the blank is the last) on the audio encoder if there is one, else the video encoder; its loss, per
+    # label token like the sequence loss, is added with weight ctc_weight (0.3: a conventional value, not a tuned one)
+    use_ctc: bool = False
+    ctc_weight: float = 0.3
     recurrent_l2: Optional[float] = 1e-4
     clip_gradients: bool = True
     max_gradient_norm: float = 1.0
@@ -109,6 +114,12 @@ class ModelConfig:
     def directions(self) -> List[str]:
         return ["fw", "bw"] if self.encoder_type == "bidirectional" else ["fw"]
 
+    def ctc_stream(self) -> Optional[str]:
+        """The stream whose encoder carries the CTC head; None when use_ctc is off."""
+        if not self.use_ctc:
+            return None
+        return "audio" if self.audio_units is not None else "video"
+
     def units(self, stream):
         return self.video_units if stream == "video" else self.audio_units
 
@@ -181,6 +192,16 @@ class ModelConfig:
             if self.video_units is None or self.audio_units is None:
                 raise ValueError("av_align needs both a video and an audio stream")
         self.loss_code()
+        if self.use_ctc:
+            if self.architecture == "lm":
+                raise ValueError("use_ctc: the language model has no encoder to put the CTC head on")
+            if self.label_smoothing > 0.0:
+                raise ValueError("use_ctc with label_smoothing > 0: the sequence loss is then normalised by label rows, not label "
+                                 "tokens, and the CTC term shares its normaliser")
+            if self.ctc_weight < 0.0:
+                raise ValueError("ctc_weight must not be negative")
+            if not self.enable_attention:
+                raise NotImplementedError("use_ctc with enable_attention=False is not built")
         if self.optimiser not in ("Adam", "Nadam", "AdamW", "Momentum"):
             raise Exception('Unsupported optimiser, try Adam')                            # seq2seq.py:218
         for st in self.streams():                 # the wrapper flags only where the reference applies them (see `wrapped`)

@@ -100,7 +100,7 @@ class Seq2SeqModel(EncoderMixin, DecoderMixin):
         tn = 0
         for name in self._train_off:
             if name.endswith(("/kernel", "/query_kernel", "/layer_kernel", "/gates_kernel", "/cand_kernel")) and \
-                    not name.startswith(("video/au", "audio/au", "video/cnn/")):
+                    not name.startswith(("video/au", "audio/au", "video/ctc", "audio/ctc", "video/cnn/")):   # (heads: trans_b GEMMs)
                 if name.endswith("memory_kernel"):
                     continue
                 r, c = self._eshape(name)
@@ -151,6 +151,8 @@ class Seq2SeqModel(EncoderMixin, DecoderMixin):
     def load_tf_weights(self, W: Dict[str, np.ndarray]):
         """Import a {name: array} dict in TF layout (same names as oracle / export_tf_weights)."""
         for name, (shape, kind, _i) in self.inv_tf.items():
+            if name not in W and "/ctc/" in name:
+                raise ValueError("the weights hold no %s: a use_ctc model needs the CTC head's variables" % name)
             e = torch.from_numpy(self._to_engine(name, W[name])).to(self.dev)
             ref = self.S[name] if name in self.S else self.P[name]
             ref.t[ref.off:ref.off + e.numel()].copy_(e)
@@ -275,6 +277,13 @@ class Seq2SeqModel(EncoderMixin, DecoderMixin):
             E["c_dec"], E["h_dec"], E["dc_dec"], E["dh_dec"] = z(B, H), z(B, H), z(B, H), z(B, H)
             if s == "video" and cfg.regress_aus:
                 E["au_z"], E["au_dz"], E["au_row"] = z(B * T, 2), z(B * T, 2), z(B * T)
+            if s == cfg.ctc_stream():
+                Cc = cfg.vocab_size + 1
+                E["ctc_z"], E["ctc_ids"] = z(B * T, Cc), torch.zeros(B * T, dtype=torch.int32, device=dev)
+                if not greedy:
+                    E["ctc_dz"], E["ctc_nll"], E["ctc_utt"] = z(B * T, Cc), z(B), z(B)
+                    E["ctc_status"] = torch.zeros(B, dtype=torch.int32, device=dev)
+                    E["ctc_ws"] = z(ops.ctc_ws_floats(B, T, L))
             ws["enc"][s] = E
         if cfg.architecture == "av_align":
             A = ws["enc"]["audio"]
@@ -464,6 +473,8 @@ class Seq2SeqModel(EncoderMixin, DecoderMixin):
         if cfg.regress_aus and "video" in ws["enc"]:
             Ev = ws["enc"]["video"]
             ops.reduce_scalar(Ev["au_row"], B * Ev["T"], self.loss, accumulate=True)
+        if cfg.use_ctc:                          # after seq_loss: the term shares its normaliser, final here on every trainer path
+            self._ctc_forward(ws, batch)
         return D["logits"]
 
     def local_loss_denominator(self, batch: Batch):

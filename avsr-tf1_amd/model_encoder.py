@@ -436,6 +436,58 @@ class EncoderMixin:
                 ops.au_loss(E["au_z"], batch.aus, E["len"], E["au_row"], E["au_dz"], B, E["T"], cfg.au_loss_weight * self.au_scale,
                             total_count=self.au_total if self.au_external else None)
 
+    def _ctc_head(self, ws):
+        """z = memory @ kernel + bias over V + 1 classes, on the memory attention sees (_mem_desc)."""
+        cfg, B = self.cfg, ws["B"]
+        s = cfg.ctc_stream()
+        E, Cc = ws["enc"][s], cfg.vocab_size + 1
+        ops.gemm(self._mem_desc(ws, s)["vmat"], self.P[f"{s}/ctc/kernel"].mat(Cc), ops.mat(E["ctc_z"], Cc), B * E["T"], Cc,
+                 cfg.memory_depth(s), bias=self._pp(f"{s}/ctc/bias"))
+        return E, Cc
+
+    def _ctc_forward(self, ws, batch):
+        """use_ctc: the head, then avsr_ctc_loss (csrc/ctc.hip): per-utterance ctc_weight * nll / denom added to the step's loss, d logits
+        kept for _encode_backward.  The target is the label row without its EOS; the blank is class V."""
+        cfg, B = self.cfg, ws["B"]
+        E, Cc = self._ctc_head(ws)
+        ops.ctc_loss(E["ctc_z"], Cc, batch.labels, batch.labels_len, E["len"], self.denom, cfg.ctc_weight, E["ctc_nll"], E["ctc_status"],
+                     E["ctc_utt"], E["ctc_dz"], E["ctc_ws"], B, E["T"], ws["L"], Cc)
+        ops.reduce_scalar(E["ctc_utt"], B, self.loss, accumulate=True)
+
+    def ctc_best_path(self, batch):
+        """use_ctc: the CTC head's best path -- encoders in evaluation mode, per-frame argmax on the device (frames past an utterance's
+        length ignored), repeats collapsed and blanks dropped on the host.  One id list per utterance."""
+        out = self._ctc_best_path(batch)
+        if self.check_persistent():
+            out = self._ctc_best_path(batch)
+        return out
+
+    def _ctc_best_path(self, batch):
+        cfg = self.cfg
+        if not cfg.use_ctc:
+            raise ValueError("ctc_best_path needs a model built with use_ctc=True")
+        B = (batch.audio if batch.audio is not None else batch.video).shape[0]
+        Ta = self._audio_rows(batch)
+        Tv = batch.video.shape[1] if batch.video is not None else 0
+        ws = self._get_ws(B, Ta, Tv, 1, True)
+        self._refresh_derived()
+        self._encode(ws, batch, False)
+        E, Cc = self._ctc_head(ws)
+        ops.ctc_best_path(E["ctc_z"], Cc, E["len"], B, E["T"], Cc, E["ctc_ids"])
+        ids = E["ctc_ids"].view(B, E["T"]).cpu().numpy()
+        out = []
+        for row in ids:
+            seq, prev = [], -1
+            for k in row:
+                k = int(k)
+                if k < 0:
+                    break
+                if k != prev and k != Cc - 1:
+                    seq.append(k)
+                prev = k
+            out.append(seq)
+        return out
+
     def persistent_flagged(self):
         """Read-only form of check_persistent(): did a persistent kernel flag the last pass on THIS rank?"""
         return bool(self.persistent_rnn and ops.rnn_persistent_error())
@@ -551,6 +603,14 @@ class EncoderMixin:
             ops.gemm(ops.mat(E["au_dz"], 2), self.P["video/au/kernel"].mat(2), E["dmem"].mat(), B * T, D, 2, trans_b=1, beta=1.0)
             self._gemm_tn(E["mem"].mat(), ops.mat(E["au_dz"], 2), self.Gr["video/au/kernel"].mat(2), D, 2, B * T)
             ops.colsum(ops.mat(E["au_dz"], 2), B * T, 2, self.grads, self.scratch, beta=1.0, out_offset=self.Gr["video/au/bias"].off)
+        if cfg.use_ctc:                              # CTC head: d logits into the memory gradient, the head's own gradients
+            s = cfg.ctc_stream()
+            E, md = ws["enc"][s], self._mem_desc(ws, s)
+            T, D, Cc = E["T"], cfg.memory_depth(s), cfg.vocab_size + 1
+            dzm = ops.mat(E["ctc_dz"], Cc)
+            ops.gemm(dzm, self.P[f"{s}/ctc/kernel"].mat(Cc), md["gmat"], B * T, D, Cc, trans_b=1, beta=1.0)
+            self._gemm_tn(md["vmat"], dzm, self.Gr[f"{s}/ctc/kernel"].mat(Cc), D, Cc, B * T)
+            ops.colsum(dzm, B * T, Cc, self.grads, self.scratch, beta=1.0, out_offset=self.Gr[f"{s}/ctc/bias"].off)
         if cfg.architecture == "av_align":
             self._av_align_backward(ws, batch)       # needs the complete gradient of the audio memory; fills video dmem
         stacks = []

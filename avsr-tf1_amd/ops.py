@@ -337,6 +337,25 @@ def au_loss(z, aus, lens, row_loss, dz, B, T, weight, total_count=None):
           "avsr_au_loss_dp")
 
 
+def ctc_ws_floats(B, T, L):
+    return int(_L().avsr_ctc_ws_floats(int(B), int(T), int(L)))
+
+
+def ctc_loss(z, ld, labels, labels_len, in_len, denom, weight, nll, status, utt_loss, dz, ws, B, T, L, n_classes):
+    """avsr_ctc_loss: z / dz [B*T, C] with row stride ld, blank = class n_classes - 1; denom is the sequence loss's device scalar."""
+    from ._lib import CtcArgs
+    a = CtcArgs()
+    a.B, a.T, a.L, a.C, a.ld = int(B), int(T), int(L), int(n_classes), int(ld)
+    a.z, a.labels, a.labels_len, a.in_len, a.denom = fptr(z), fptr(labels), fptr(labels_len), fptr(in_len), fptr(denom)
+    a.weight = float(weight)
+    a.nll, a.status, a.utt_loss, a.dz, a.ws, a.ws_floats = fptr(nll), fptr(status), fptr(utt_loss), fptr(dz), fptr(ws), int(ws.numel())
+    check(_L().avsr_ctc_loss(C.byref(a), _s()), "avsr_ctc_loss")
+
+
+def ctc_best_path(z, ld, in_len, B, T, n_classes, ids):
+    check(_L().avsr_ctc_best_path(fptr(z), int(ld), fptr(in_len), int(B), int(T), int(n_classes), fptr(ids), _s()), "avsr_ctc_best_path")
+
+
 def normed_v(v, g, vn, H):
     check(_L().avsr_normed_v(fptr(v), fptr(g), fptr(vn), H, _s()), "avsr_normed_v")
 

@@ -108,6 +108,9 @@ def _layout(cfg: ModelConfig):
         if stream == "video" and cfg.regress_aus:
             inv["video/au/kernel"] = ([depth("video"), [2]], "plain", "glorot")
             inv["video/au/bias"] = ([[2]], "plain", "zeros")
+        if stream == cfg.ctc_stream():                        # use_ctc: Dense(V + 1) on the memory attention sees; blank = class V
+            inv[f"{stream}/ctc/kernel"] = ([depth(stream), [cfg.vocab_size + 1]], "plain", "glorot")
+            inv[f"{stream}/ctc/bias"] = ([[cfg.vocab_size + 1]], "plain", "zeros")
     if cfg.video_units is not None and cfg.video_processing in ("resnet_cnn", "3dconv_cnn"):
         if cfg.video_processing == "3dconv_cnn":                 # no biases; [kt, kh, kw, cin, cout] kernels (cnn3d.tf_names: TF's names)
             from .cnn3d import param_shapes

@@ -671,6 +671,40 @@ typedef struct avsr_logmel_args {
 } avsr_logmel_args;
 int avsr_logmel_supported(int32_t frame_length, int32_t fft_length, int32_t num_mel_bins, int32_t window, int32_t stride);
 int avsr_logmel_fwd(const avsr_logmel_args* a, void* stream);
+/* ---- CTC auxiliary loss on an encoder's outputs (use_ctc; not in the reference; csrc/ctc.hip).  z [B*T, C] with row stride ld are the
+ * head's logits, C = vocab_size + 1 and the BLANK IS CLASS C - 1 (tf.nn.ctc_loss's convention); columns >= C of a wider row are never
+ * read or written.  Utterance b: target labels[b, :U_b] with U_b = max(min(labels_len[b], L) - 1, 0) (the label row without its EOS),
+ * T_b = min(max(in_len[b], 0), T) frames.
+ *   nll[b]      = -log p(target_b | log_softmax(z[b, :T_b])), the standard CTC forward-backward recursion
+ *   status[b]   = 1, or 0 when the utterance has no valid alignment (T_b < U_b + adjacent equal label pairs, T_b == 0, or a label
+ *                 outside [0, C - 1)): then nll[b] = 0 and its rows of dz are zero (torch's zero_infinity=True)
+ *   utt_loss[b] = weight * nll[b] / (denom[0] + 1e-12)          denom: DEVICE scalar, the sequence loss's own normaliser
+ *   dz[b, t, k] = weight / denom * (softmax(z)[b, t, k] - occupancy[b, t, k]) for t < T_b, exactly 0 for t >= T_b; layout of z; dz != z
+ * ws: avsr_ctc_ws_floats(B, T, L) floats of scratch (alpha over all T frames lives there, so T is not bounded by on-chip memory).
+ * One launch, one workgroup per utterance, no atomics (two launches on the same inputs are bit-identical), no host read, no
+ * memset / memcpy: safe under stream capture.  L and C up to 1024, otherwise AVSR_ERR_UNSUPPORTED (-3). */
+typedef struct avsr_ctc_args {
+  int32_t B, T, L, C;
+  int64_t ld;
+  const float* z;
+  const int32_t* labels;
+  const int32_t* labels_len;
+  const int32_t* in_len;
+  const float* denom;
+  float weight;
+  int32_t pad_;
+  float* nll;
+  int32_t* status;
+  float* utt_loss;
+  float* dz;
+  float* ws;
+  int64_t ws_floats;
+} avsr_ctc_args;
+int avsr_ctc_loss(const avsr_ctc_args* a, void* stream);
+int64_t avsr_ctc_ws_floats(int32_t B, int32_t T, int32_t L);
+/* ids[b*T + t] = argmax_k z[b, t, k] over the C classes (the lowest index wins a tie) for t < T_b, -1 for t >= T_b: the CTC best path
+ * before the host collapses repeats and drops blanks. */
+int avsr_ctc_best_path(const float* z, int64_t ld, const int32_t* in_len, int32_t B, int32_t T, int32_t C, int32_t* ids, void* stream);
 /* y = max(x, 0);  dx = dy * [y > 0];  out = a + b (tf.nn.relu / residual tf.add of video.py) */
 int avsr_relu(const float* x, float* y, int64_t n, void* stream);
 int avsr_relu_bwd(const float* y, const float* dy, float* dx, int64_t n, void* stream);
