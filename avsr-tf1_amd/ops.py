@@ -112,6 +112,8 @@ def gemm(A, B, Cm, M, N, K, trans_a=False, trans_b=False, alpha=1.0, beta=0.0, b
             splitk //= 2
     d.splitk = int(splitk)
     grp = _gemm_group
+    if grp is not None and len(grp["descs"]) >= 48:
+        _flush_group(grp)          # before this entry's slab is carved: the flush hands the whole workspace back
     if splitk > 1:
         need = batch * splitk * (M * N + cs_extra)
         assert workspace is not None and workspace.numel() >= need, "split-K workspace too small"
@@ -128,8 +130,6 @@ def gemm(A, B, Cm, M, N, K, trans_a=False, trans_b=False, alpha=1.0, beta=0.0, b
             d.workspace = fptr(workspace)
             d.workspace_floats = workspace.numel()
     if grp is not None:
-        if len(grp["descs"]) >= 48:
-            _flush_group(grp)
         grp["descs"].append(d)
         grp["keep"] += [A, B, Cm]
         return
