@@ -121,6 +121,12 @@ class ConvDesc(C.Structure):
                [("bn_scale", C.c_void_p), ("bn_shift", C.c_void_p)]
 
 
+class ConvLaunch(C.Structure):
+    """avsr_conv_launch: one record of avsr_conv_plan."""
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "m", "ntc", "ch4", "rs", "fold", "ep", "nsp", "ntap", "t0", "F", "grid", "CsP", "lds_bytes",
+                                         "slab", "pad_")]
+
+
 class Conv3dDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("B", "T", "H", "W", "Ci", "Co", "kt", "kh", "kw", "stride", "pad_f", "pad_t", "pad_l", "Ho", "Wo",
                                          "relu")] + [("scale", C.c_void_p), ("shift", C.c_void_p)]
@@ -147,7 +153,7 @@ class TransposeJob(C.Structure):
 
 
 _STRUCTS = {"avsr_dec_layer": DecLayer, "avsr_mat": Mat, "avsr_gemm_desc": GemmDesc, "avsr_rnn_layer": RnnLayer, "avsr_rnn_stack": RnnStack,
-            "avsr_conv_desc": ConvDesc, "avsr_conv3d_desc": Conv3dDesc, "avsr_logmel_args": LogmelArgs, "avsr_ctc_args": CtcArgs, "avsr_attn_mech": AttnMech, "avsr_attn_rnn": AttnRnn, "avsr_transpose_job": TransposeJob,
+            "avsr_conv_desc": ConvDesc, "avsr_conv_launch": ConvLaunch, "avsr_conv3d_desc": Conv3dDesc, "avsr_logmel_args": LogmelArgs, "avsr_ctc_args": CtcArgs, "avsr_attn_mech": AttnMech, "avsr_attn_rnn": AttnRnn, "avsr_transpose_job": TransposeJob,
             "avsr_colsum_job": ColsumJob, "avsr_beam_lm": BeamLm}
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -174,6 +180,7 @@ _SIGS = {
     "avsr_conv_bwd_data_bn_supported": [C.POINTER(ConvDesc)],
     "avsr_conv_bwd_weight_bn": [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _i64, _vp],
     "avsr_conv_bwd_weight_bn_supported": [C.POINTER(ConvDesc)],
+    "avsr_conv_plan": [C.POINTER(ConvDesc), _i32, _i32, _i64, C.POINTER(ConvLaunch), _i32],
     "avsr_bn_bwd_finalize": [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp],
     "avsr_bn_bwd_apply": [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _vp],
     "avsr_bn_bwd_stage1": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, C.POINTER(_i32), _vp],

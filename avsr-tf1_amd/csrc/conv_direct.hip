@@ -170,11 +170,16 @@ __global__ __launch_bounds__(256) void conv3x3_bwd_weight_kernel(const float* __
   const int n0 = blockIdx.x * frames_per_blk, n1 = min(N, n0 + frames_per_blk);
   const int nx = Hp * Wp * Ci, nd = Ho * Wo * CO;
   for (int idx = threadIdx.x; idx < nx; idx += 256) xs[idx] = 0.f;       // the halo stays zero; frames only overwrite the interior
-  const int rowf = W * Ci, rowq = rowf >> 2;                              // floats / 16-byte pieces per map row (W*Ci % 4 == 0)
+  const int rowf = W * Ci, rowq = rowf >> 2;                              // floats / 16-byte pieces per map row
   for (int n = n0; n < n1; ++n) {
     __syncthreads();
     const float* xn = x + (long)n * H * rowf;
-    for (int idx = threadIdx.x; idx < H * rowq; idx += 256) {
+    if (rowf & 3) {                                                         // 1 .. 3 channels on a width that leaves no whole pieces: by the float
+      for (int idx = threadIdx.x; idx < H * rowf; idx += 256) {
+        const int h = idx / rowf;
+        xs[((h + 1) * Wp + 1) * Ci + (idx - h * rowf)] = xn[idx];
+      }
+    } else for (int idx = threadIdx.x; idx < H * rowq; idx += 256) {
       const int h = idx / rowq, p4 = idx % rowq;
       const f32x4 v = ld4(xn + (long)h * rowf + p4 * 4);
       float* d = xs + ((h + 1) * Wp + 1) * Ci + p4 * 4;

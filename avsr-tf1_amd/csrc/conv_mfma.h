@@ -120,6 +120,17 @@ struct WGArgs {
 
 extern int g_conv_mfma;                 // avsr_conv_set_mfma: 0 sends every layer to the direct / im2col paths (tests)
 
+// avsr_conv_plan: while this thread's recorder is set, the dry paths of cg_launch / cg_launch_q4 / conv_bwd_weight_impl note the launch they
+// decided on (nothing else reads it: the *_supported queries and every real call run with it NULL)
+struct ConvPlanRec { avsr_conv_launch* out; int cap, n; };
+extern thread_local ConvPlanRec* g_conv_plan;
+static inline void conv_plan_note(const avsr_conv_launch& L) {
+  ConvPlanRec* R = g_conv_plan;
+  if (!R) return;
+  if (R->n < R->cap) R->out[R->n] = L;
+  ++R->n;
+}
+
 }  // namespace avsr
 
 #define S_(x) ((hipStream_t)(x))

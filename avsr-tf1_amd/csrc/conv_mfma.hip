@@ -661,6 +661,7 @@ __global__ __launch_bounds__(256, 2) void conv_q4_kernel(const CGArgs A) {
 }
 
 int g_conv_mfma = 1;
+thread_local ConvPlanRec* g_conv_plan = nullptr;
 
 }  // namespace avsr
 
@@ -677,6 +678,19 @@ static bool cg_q4_taps_ok(const CGArgs& A) {
   for (int t = 0; t < 9; ++t)
     if (A.tap[t].db != (A.wmode ? 1 - t % 3 : t % 3 - 1)) return false;
   return true;
+}
+// The dry path's answer: the grid.  Under avsr_conv_plan it also notes the launch -- kernel, instantiation, geometry -- and answers with
+// the refusal the launch itself would meet below, where there is one.
+static int cg_dry(const CGArgs& A, int kernel, int m, int c4t, int grid, size_t lds) {
+  if (!g_conv_plan) return grid;
+  if (A.res && A.bnb_x) return AVSR_ERR_ARG;
+  const int ep = ((A.res || A.bnb_x) ? 1 : 0) | (A.beta != 0.f ? 2 : 0);
+  if (A.Cs % 4 && ep) return AVSR_ERR_UNSUPPORTED;
+  avsr_conv_launch L = {};
+  L.kernel = kernel; L.m = m; L.ntc = c4t; L.ch4 = A.Cs % 4 == 0; L.ep = ep; L.nsp = A.nsp; L.ntap = A.ntap; L.F = A.F; L.grid = grid;
+  L.CsP = kernel == 0 ? A.CsP : A.CsL; L.lds_bytes = (int32_t)lds;
+  conv_plan_note(L);
+  return grid;
 }
 static int cg_launch_q4(CGArgs& A, hipStream_t s, int kind, double flops, bool dry) {
   int Fcap = 16;
@@ -714,7 +728,7 @@ static int cg_launch_q4(CGArgs& A, hipStream_t s, int kind, double flops, bool d
   if (lds < 256) lds = 256;
   int grid = (A.N + A.F - 1) / A.F;
   if (grid > CONV_MAX_PARTS) grid = CONV_MAX_PARTS;
-  if (dry) return grid;
+  if (dry) return cg_dry(A, 1, 9, A.Cs == 3 ? 1 : 2, grid, lds);
   ProfScope ps(kind, s, flops);
   const bool emap = A.res != nullptr || A.bnb_x != nullptr;
   if (A.res && A.bnb_x) return AVSR_ERR_ARG;
@@ -803,7 +817,7 @@ static int cg_launch(CGArgs& A, hipStream_t s, int kind, double flops, bool dry 
   if (lds < sizeof(float) * 4 * 4 * 2 * 4) lds = sizeof(float) * 4 * 4 * 2 * 4;      // the statistics reduction's staging area
   int grid = (A.N + A.F - 1) / A.F;
   if (grid > CONV_MAX_PARTS) grid = CONV_MAX_PARTS;
-  if (dry) return grid;
+  if (dry) return cg_dry(A, 0, A.Cs % 4 ? 5 : (nch <= 2 ? 2 : (nch <= 6 ? 6 : (nch <= 9 ? 9 : (nch <= 18 ? 18 : 20)))), 0, grid, lds);
   ProfScope ps(kind, s, flops);
   const bool emap = A.res != nullptr || A.bnb_x != nullptr;
   if (A.res && A.bnb_x) return AVSR_ERR_ARG;            // one extra epilogue map at a time
@@ -898,6 +912,7 @@ static int cg_run_paired(CGArgs& A, const CGTap* taps, int nt, hipStream_t s, in
 
 int conv_fwd_impl(const avsr_conv_desc* c, const float* x, const float* w, const float* bias, const float* res, const float* res_sc,
                          const float* res_sh, float* y, float* stats, int32_t* nparts, void* stream, bool dry) {
+  if (c->Ci % 4 && c->bn_scale) return AVSR_ERR_UNSUPPORTED;      // the BN-ReLU loader is part of the row-structured staging only (as the weight gradient)
   CGArgs A = {};
   A.src = x; A.w = w; A.bias = bias; A.dst = y; A.stats = stats; A.res = res; A.bn_sc = c->bn_scale; A.bn_sh = c->bn_shift;
   A.res_sc = res ? res_sc : nullptr; A.res_sh = res ? res_sh : nullptr;
@@ -981,7 +996,13 @@ int conv_bwd_data_impl(const avsr_conv_desc* c, const float* dy, const float* w,
   // have to be applied class by class -- the fused forms are only offered on the single-launch paths above
   if (acc || bnb_x) return AVSR_ERR_UNSUPPORTED;
   // stride 2: one launch per parity class (ph, pw) of the input pixels; a class no tap reaches receives no gradient from this
-  // convolution (beta == 0 is then refused: the caller orders its contributions so that this one accumulates)
+  // convolution (any beta but 1 is then refused: the caller orders its contributions so that this one accumulates)
+  if (beta != 1.f) {                                      // a class no tap reaches keeps what it holds, which is beta*dx only for beta == 1
+    CGTap taps[9];                                        // (decided before the first class is launched: a refusal writes nothing)
+    for (int ph = 0; ph < 2; ++ph)
+      for (int pw = 0; pw < 2; ++pw)
+        if ((c->H - ph + 1) / 2 > 0 && (c->W - pw + 1) / 2 > 0 && cg_class_taps(c, ph, pw, taps) == 0) return AVSR_ERR_UNSUPPORTED;
+  }
   for (int ph = 0; ph < 2; ++ph)
     for (int pw = 0; pw < 2; ++pw) {
       const int OA = (c->H - ph + 1) / 2, OB = (c->W - pw + 1) / 2;
@@ -989,10 +1010,7 @@ int conv_bwd_data_impl(const avsr_conv_desc* c, const float* dy, const float* w,
       CGArgs A = args(OA, OB, 2, ph, pw);
       CGTap taps[9];
       const int nt = cg_class_taps(c, ph, pw, taps);
-      if (nt == 0) {
-        if (beta == 0.f) return AVSR_ERR_UNSUPPORTED;
-        continue;
-      }
+      if (nt == 0) continue;                              // (beta == 1, see above)
       const int rc = cg_run(A, taps, nt, S_(stream), PROF_CONV_BWD_DATA, 2.0 * c->N * A.OA * A.OB * (double)c->Ci * c->Co, dry, nullptr);
       if (rc < 0) return rc;
     }
@@ -1005,6 +1023,36 @@ extern "C" int avsr_conv_supported(const avsr_conv_desc* c) {
   if (c->Ci >= 4 && conv_bwd_data_impl(c, nullptr, nullptr, nullptr, 1.f, nullptr, true) != AVSR_OK) return 0;
   if (conv_bwd_weight_impl(c, nullptr, nullptr, nullptr, nullptr, 1.f, nullptr, 1L << 40, nullptr, true) != AVSR_OK) return 0;
   return 1;
+}
+
+// The launches one call would make (avsr_hip.h): the entry points' own argument checks, then the implementations' dry paths with this
+// thread's recorder set.  The operands are one dummy address that nothing dereferences.
+extern "C" int avsr_conv_plan(const avsr_conv_desc* c, int32_t op, int32_t flags, int64_t scratch_floats, avsr_conv_launch* out, int32_t cap) {
+  if (!cd_ok(c) || op < 0 || op > 2 || cap < 0 || (cap > 0 && !out)) return AVSR_ERR_ARG;
+  const int allowed = op == 0 ? (AVSR_CONV_PLAN_BIAS | AVSR_CONV_PLAN_RES | AVSR_CONV_PLAN_STATS)
+                    : op == 1 ? (AVSR_CONV_PLAN_BETA | AVSR_CONV_PLAN_ACC | AVSR_CONV_PLAN_BNB)
+                              : (AVSR_CONV_PLAN_BETA | AVSR_CONV_PLAN_DBIAS | AVSR_CONV_PLAN_FOLD | AVSR_CONV_PLAN_FOLD_DX);
+  if (flags & ~allowed) return AVSR_ERR_ARG;
+  if ((flags & AVSR_CONV_PLAN_FOLD_DX) && !(flags & AVSR_CONV_PLAN_FOLD)) return AVSR_ERR_ARG;
+  if (!g_conv_mfma) return AVSR_ERR_UNSUPPORTED;
+  static float dummy;
+  auto opt = [&](int bit) -> float* { return (flags & bit) ? &dummy : nullptr; };
+  const float beta = (flags & AVSR_CONV_PLAN_BETA) ? 1.f : 0.f;
+  ConvPlanRec R = {out, cap, 0};
+  int32_t n = 0;
+  g_conv_plan = &R;
+  int rc;
+  if (op == 0)
+    rc = conv_fwd_impl(c, &dummy, &dummy, opt(AVSR_CONV_PLAN_BIAS), opt(AVSR_CONV_PLAN_RES), nullptr, nullptr, &dummy, opt(AVSR_CONV_PLAN_STATS), &n,
+                       nullptr, true);
+  else if (op == 1)
+    rc = conv_bwd_data_impl(c, &dummy, &dummy, &dummy, beta, nullptr, true, opt(AVSR_CONV_PLAN_ACC), opt(AVSR_CONV_PLAN_BNB), opt(AVSR_CONV_PLAN_BNB),
+                            opt(AVSR_CONV_PLAN_BNB), opt(AVSR_CONV_PLAN_BNB), &n);
+  else
+    rc = conv_bwd_weight_impl(c, &dummy, &dummy, &dummy, opt(AVSR_CONV_PLAN_DBIAS), beta, &dummy, scratch_floats, nullptr, true,
+                              opt(AVSR_CONV_PLAN_FOLD), opt(AVSR_CONV_PLAN_FOLD), opt(AVSR_CONV_PLAN_FOLD_DX));
+  g_conv_plan = nullptr;
+  return rc < 0 ? rc : R.n;
 }
 
 extern "C" int avsr_conv_fwd(const avsr_conv_desc* c, const float* x, const float* w, const float* bias, const float* res, const float* res_scale,

@@ -344,6 +344,15 @@ static int wg_grid(int N, int F, int slab, int wpc, long scratch_floats) {
   return grid;
 }
 
+// avsr_conv_plan's record of one weight-gradient launch (dry path only)
+static void wg_note(const WGArgs& A, int m, int ntc, bool rs, int fold, int nsp, int grid, size_t lds) {
+  if (!g_conv_plan) return;
+  avsr_conv_launch L = {};
+  L.kernel = 2; L.m = m; L.ntc = ntc; L.ch4 = A.Ci % 4 == 0; L.rs = rs; L.fold = fold; L.nsp = nsp; L.ntap = A.nt; L.t0 = A.t0; L.F = A.F;
+  L.grid = grid; L.CsP = A.CiL + A.pad; L.lds_bytes = (int32_t)lds; L.slab = A.slab;
+  conv_plan_note(L);
+}
+
 int conv_bwd_weight_impl(const avsr_conv_desc* c, const float* x, const float* dy, float* dw, float* dbias, float beta, float* scratch,
                                 long scratch_floats, void* stream, bool dry, const float* fold_y, const float* fold_k,
                                 float* fold_dx) {
@@ -367,7 +376,7 @@ int conv_bwd_weight_impl(const avsr_conv_desc* c, const float* x, const float* d
     if ((Ci % 4 == 0 ? MT <= 6 : MT <= 3) && wg_plan(A, MT, A.slab, false, &P)) {
       const int grid = wg_grid(N, A.F, A.slab, P.wpc, scratch_floats);
       if (grid < 1) return AVSR_ERR_ARG;
-      if (dry) return AVSR_OK;
+      if (dry) { wg_note(A, Ci % 4 ? 3 : 6, 1, false, fold ? (fold_dx ? 2 : 1) : 0, 2, grid, P.lds); return AVSR_OK; }
       hipStream_t s = S_(stream);
       {
         ProfScope ps(PROF_CONV_BWD_WEIGHT, s, 2.0 * N * Ho * Wo * 9.0 * Ci * Co);
@@ -421,7 +430,13 @@ int conv_bwd_weight_impl(const avsr_conv_desc* c, const float* x, const float* d
     if (Ci % 4 && (MT > 3 || NTC != 1)) return AVSR_ERR_UNSUPPORTED;
     const int grid = wg_grid(N, A.F, A.slab, P.wpc, scratch_floats);
     if (grid < 1) return AVSR_ERR_ARG;
-    if (dry) continue;
+    if (dry) {
+      // (the form chosen below; the next tap group of a real call does not ask for the bias columns again)
+      const int m = fold ? (rs || NTC == 1 ? 5 : 9) : (Ci % 4 ? 3 : (MT <= 5 ? 5 : (MT <= 9 || NTC == 4 ? 9 : 18)));
+      wg_note(A, m, Ci % 4 ? 1 : NTC, rs, fold ? (fold_dx ? 2 : 1) : 0, 1, grid, lds);
+      bias_done = true;
+      continue;
+    }
     {
       ProfScope ps(PROF_CONV_BWD_WEIGHT, s, 2.0 * N * Ho * Wo * (double)A.nt * Ci * Co);
 #define WG_GO(M_, N_, C_) hipLaunchKernelGGL((conv_wgrad_kernel<M_, N_, C_>), dim3(grid), dim3(256), lds, s, A)

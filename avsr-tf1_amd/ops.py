@@ -659,6 +659,24 @@ def conv_bwd_weight_bn_supported(d):
     return bool(_L().avsr_conv_bwd_weight_bn_supported(C.byref(d)))
 
 
+CONV_PLAN_OPS = {"fwd": 0, "bwd_data": 1, "bwd_weight": 2}
+CONV_PLAN_FLAGS = {"bias": 1, "res": 2, "stats": 4, "beta": 8, "acc": 16, "bnb": 32, "fold": 64, "fold_dx": 128, "dbias": 256}
+
+
+def conv_plan(d, op, flags=(), scratch_floats=1 << 40, cap=16):
+    """avsr_conv_plan: the launches one descriptor call would make, as a list of dicts (the fields of avsr_conv_launch), decided by the
+    library's host code without touching HIP (no GPU needed).  op: "fwd" / "bwd_data" / "bwd_weight"; flags: names of CONV_PLAN_FLAGS (or
+    their OR-ed bits).  A call the library would refuse raises AvsrError with its code."""
+    from ._lib import ConvLaunch
+    bits = flags if isinstance(flags, int) else sum(CONV_PLAN_FLAGS[f] for f in set(flags))
+    out = (ConvLaunch * cap)()
+    n = _L().avsr_conv_plan(C.byref(d), CONV_PLAN_OPS[op] if isinstance(op, str) else int(op), bits, int(scratch_floats), out, cap)
+    if n < 0:
+        check(n, "avsr_conv_plan")
+    assert n <= cap
+    return [{f: getattr(out[i], f) for f, _ in ConvLaunch._fields_ if f != "pad_"} for i in range(n)]
+
+
 def slab_defer_begin():
     """From here to slab_defer_end() the conv_bwd_weight calls of this thread record their final slab reductions instead of launching
     them: one launch at the end (every call needs its own scratch region)."""

@@ -542,7 +542,8 @@ int avsr_conv_set_mfma(int32_t on);
  *     itself a lazily normalised map); stats != NULL (>= 512*2*Co floats): per-workgroup partial sums / sums of squares of y
  *     [*nparts][2*Co] for the batch norm that consumes y; avsr_bn_finalize merges them in fp64 into mean / inverse std (+ the
  *     moving averages with the Bessel-corrected variance of the fused rank-4 TF kernel) and the scale / shift vectors above.
- *   avsr_conv_bwd_data: dx = beta*dx + conv_transpose(dy); a stride-2 1x1 kernel reaches only the even pixels, so beta must be 1.
+ *   avsr_conv_bwd_data: dx = beta*dx + conv_transpose(dy); a stride-2 1x1 kernel reaches only the even pixels, so beta must be 1
+ *     (any other beta: AVSR_ERR_UNSUPPORTED before anything is launched).
  *   avsr_conv_bwd_weight: dw = beta*dw + sum x (x) dy, dbias (may be NULL) = beta*dbias + column sums of dy (same pass over dy);
  *     scratch >= 256 * (k*k*Ci*Co + Co) floats.
  * AVSR_ERR_UNSUPPORTED (-3) for shapes outside the kernels' register / LDS budget (avsr_conv_supported == 0): the caller then uses
@@ -579,6 +580,30 @@ int avsr_conv_bwd_data_bn_supported(const avsr_conv_desc* c);
 int avsr_conv_bwd_weight_bn(const avsr_conv_desc* c, const float* x, const float* dz, const float* y, const float* k, float* dx_out,
                             float* dw, float* dbias, float beta, float* scratch, int64_t scratch_floats, void* stream);
 int avsr_conv_bwd_weight_bn_supported(const avsr_conv_desc* c);
+/* Read-only plan query: the kernel launches one call of the descriptor API WOULD make, decided by the same host code on its dry path --
+ * no pointer is dereferenced, nothing is launched, no HIP call is made (runs without a GPU).  op: 0 avsr_conv_fwd, 1 avsr_conv_bwd_data
+ * (+ _bn), 2 avsr_conv_bwd_weight (+ _bn).  flags: the optional operands the real call would pass (AVSR_CONV_PLAN_*; c->bn_scale != NULL
+ * stands for the BN-ReLU loader); scratch_floats: the weight gradient's scratch.  Writes up to `cap` records, one per launch in launch
+ * order, and returns the number of launches (which may exceed cap), or the AVSR_ERR_* code the real call would return.
+ *   kernel 0: conv_gen_kernel<m = MAXCH, ch4, ep>      1: conv_q4_kernel<m = NTAP, ntc = C4T, ch4, ep>
+ *   kernel 2: conv_wgrad_kernel<m = MT, ntc = NTC, ch4, rs, fold>
+ *   nsp: destination pixels per product row (data path; the pixel-pair weight gradient reports 2), ntap: taps of this launch, t0: its first
+ *   tap, F: frames per pass, grid: workgroups, CsP: floats per staged pixel in LDS, lds_bytes: dynamic LDS, slab: floats per workgroup
+ *   partial (weight gradient; includes the bias columns where this launch computes them). */
+#define AVSR_CONV_PLAN_BIAS 1
+#define AVSR_CONV_PLAN_RES 2
+#define AVSR_CONV_PLAN_STATS 4
+#define AVSR_CONV_PLAN_BETA 8
+#define AVSR_CONV_PLAN_ACC 16
+#define AVSR_CONV_PLAN_BNB 32
+#define AVSR_CONV_PLAN_FOLD 64
+#define AVSR_CONV_PLAN_FOLD_DX 128
+#define AVSR_CONV_PLAN_DBIAS 256
+typedef struct avsr_conv_launch {
+  int32_t kernel, m, ntc, ch4, rs, fold, ep, nsp;
+  int32_t ntap, t0, F, grid, CsP, lds_bytes, slab, pad_;
+} avsr_conv_launch;
+int avsr_conv_plan(const avsr_conv_desc* c, int32_t op, int32_t flags, int64_t scratch_floats, avsr_conv_launch* out, int32_t cap);
 int avsr_bn_bwd_finalize(const float* part, int32_t nparts, int32_t C, int64_t count, const float* mean, const float* invstd,
                          const float* gamma, float* dgamma, float* dbeta, float grad_beta, float* k, void* stream);
 int avsr_bn_bwd_apply(const float* dz, const float* x, const float* k, float* dx, int64_t rows, int32_t C, float beta, void* stream);
