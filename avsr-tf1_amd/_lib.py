@@ -116,6 +116,16 @@ class BeamLm(C.Structure):
                 ("wout_t", C.c_void_p), ("bout", C.c_void_p), ("state_c", C.c_void_p), ("state_h", C.c_void_p), ("lm_logp", C.c_void_p)]
 
 
+BEAM_CTC_MAX_T, BEAM_CTC_MAX_V = 2048, 256          # AVSR_BEAM_CTC_MAX_T / _V of include/avsr_hip.h
+
+
+class BeamCtc(C.Structure):
+    _fields_ = [("n_utt", C.c_int32), ("beam_width", C.c_int32), ("T", C.c_int32), ("V", C.c_int32), ("eos_id", C.c_int32),
+                ("weight", C.c_float), ("ld", C.c_int64)] + \
+               [(n, C.c_void_p) for n in ("z", "in_len", "y", "state", "psi", "last", "term", "extra", "lm_logp")] + \
+               [("lm_weight", C.c_float), ("pad_", C.c_int32)]
+
+
 class ConvDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("N", "H", "W", "Ci", "Co", "k", "stride", "pad_t", "pad_l", "Ho", "Wo", "pad_")] + \
                [("bn_scale", C.c_void_p), ("bn_shift", C.c_void_p)]
@@ -154,7 +164,7 @@ class TransposeJob(C.Structure):
 
 _STRUCTS = {"avsr_dec_layer": DecLayer, "avsr_mat": Mat, "avsr_gemm_desc": GemmDesc, "avsr_rnn_layer": RnnLayer, "avsr_rnn_stack": RnnStack,
             "avsr_conv_desc": ConvDesc, "avsr_conv_launch": ConvLaunch, "avsr_conv3d_desc": Conv3dDesc, "avsr_logmel_args": LogmelArgs, "avsr_ctc_args": CtcArgs, "avsr_attn_mech": AttnMech, "avsr_attn_rnn": AttnRnn, "avsr_transpose_job": TransposeJob,
-            "avsr_colsum_job": ColsumJob, "avsr_beam_lm": BeamLm}
+            "avsr_colsum_job": ColsumJob, "avsr_beam_lm": BeamLm, "avsr_beam_ctc": BeamCtc}
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 # argument types of every entry point that returns an int status (include/avsr_hip.h)
@@ -207,6 +217,12 @@ _SIGS = {
     "avsr_beam_search_step_lm": [_vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp,
                                  _vp, _f32, _vp],
     "avsr_attn_rnn_fwd_lm": [C.POINTER(AttnRnn), C.POINTER(BeamLm), _i32, _i32, _vp],
+    "avsr_beam_ctc_supported": [C.POINTER(BeamCtc)],
+    "avsr_beam_ctc_begin": [C.POINTER(BeamCtc), _vp],
+    "avsr_beam_ctc_step": [C.POINTER(BeamCtc), _vp, _vp, _vp, _i32, _vp],
+    "avsr_beam_search_step_ctc": [_vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp,
+                                  _vp, _f32, _vp, _f32, _vp, _vp],
+    "avsr_attn_rnn_fwd_ctc": [C.POINTER(AttnRnn), C.POINTER(BeamLm), C.POINTER(BeamCtc), _i32, _i32, _vp],
     "avsr_attn_alpha_rows": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp],
     "avsr_bahdanau_dkeys": [_vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
     "avsr_transpose": [C.POINTER(TransposeJob), _i32, _vp],

@@ -27,7 +27,9 @@ unfinished beam's continuation with log p_model + lm_weight * log p_lm (INTEGRAT
 Hybrid CTC / attention training (not in the reference, which only reserves `use_ctc` in its hyper-parameters): `use_ctc` (False),
 `ctc_weight` (0.3: a conventional value, not a tuned one) arrive through **kwargs; a CTC head on the audio (else video) encoder adds
 ctc_weight * CTC loss per label token to the step's loss, and `evaluate` also reports that head's best-path error rate under the key
-'ctc_' + unit (csrc/ctc.hip).
+'ctc_' + unit (csrc/ctc.hip).  `ctc_decode_weight` (0.0 = off) is an evaluate-time option of a `use_ctc` model:
+beam search then adds ctc_decode_weight * (CTC prefix score of the continuation - that of the beam) to an unfinished beam's step score
+(joint CTC / attention decoding, csrc/beam_ctc.hip); it works together with `lm_checkpoint`.
 """
 import glob
 import os
@@ -152,6 +154,20 @@ class AVSR(object):
             lm_cfg = _lm.fusion_config(self._unit_dict, kwargs.get('lm_units_per_layer', (256,)), kwargs.get('lm_embedding_size', 128),
                                        kwargs.get('lm_cell_type', 'lstm'))
             lm_weights = _lm.checkpoint_weights(lm_cfg, lm_checkpoint)
+
+        # joint CTC / attention scoring in beam search: an evaluate-time weight, held like _lm_weight; 0 = off, nothing new is launched
+        self._ctc_decode_weight = float(kwargs.get('ctc_decode_weight', 0.0))
+        if not self._ctc_decode_weight >= 0.0 or self._ctc_decode_weight == float('inf'):
+            raise ValueError("ctc_decode_weight must be a finite number >= 0 (got %r)" % (kwargs.get('ctc_decode_weight'),))
+        if self._ctc_decode_weight != 0.0:
+            from ._lib import BEAM_CTC_MAX_V
+            if not kwargs.get('use_ctc', False):
+                raise ValueError("ctc_decode_weight needs use_ctc=True: the term is the CTC head's prefix score")
+            if decoding_algorithm != 'beam_search':
+                raise ValueError("ctc_decode_weight needs decoding_algorithm='beam_search': the joint scoring is defined on the beam")
+            if len(self._unit_dict) - 1 > BEAM_CTC_MAX_V or beam_width > 64:
+                raise ValueError("ctc_decode_weight: avsr_beam_ctc_supported covers vocabularies of up to %d symbols and beam widths "
+                                 "of up to 64 (got %d, %d)" % (BEAM_CTC_MAX_V, len(self._unit_dict) - 1, beam_width))
 
         reverse = {v: k for k, v in self._unit_dict.items()}
         feats, video_hw = {}, (36, 36, 3)
@@ -448,7 +464,8 @@ class AVSR(object):
             batch, names = self._to_batch(bd)
             if self._decoding_algorithm == 'beam_search':     # avsr.py:58-59 default: width 10, first beam returned
                 ids = self._model.beam_search_decode(batch, beam_width=self._beam_width, max_steps=self._cfg.max_label_length,
-                                                     lm=self._lm, lm_weight=self._lm_weight if self._lm is not None else 0.0)
+                                                     lm=self._lm, lm_weight=self._lm_weight if self._lm is not None else 0.0,
+                                                     ctc_weight=self._ctc_decode_weight)
             else:
                 ids = self._model.greedy_decode(batch, max_steps=self._cfg.max_label_length)
             ids = ids.cpu().numpy()

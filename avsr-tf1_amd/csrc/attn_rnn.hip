@@ -18,6 +18,9 @@ int beam_cell_launch(const avsr_attn_rnn& d, int l, hipStream_t s);
 int beam_attention_layer_launch(const avsr_attn_rnn& d, int l, hipStream_t s);
 int beam_lm_check(const avsr_beam_lm* m);                                                                  // beam_lm.hip
 int beam_lm_step_launch(const avsr_beam_lm& m, const int32_t* tok, const int32_t* parent_rows, int step, hipStream_t s);
+int beam_ctc_check(const avsr_beam_ctc* c);                                                               // beam_ctc.hip
+int beam_ctc_step_launch(const avsr_beam_ctc& c, const int32_t* tok, const int32_t* parent_rows, const int32_t* fin, int step, hipStream_t s);
+int beam_ctc_combine_launch(const float* term, float weight, const float* lm_logp, float lm_weight, float* extra, long n, hipStream_t s);
 }
 int avsr_dec_persist_fwd(const avsr_attn_rnn* d, int32_t l_begin, int32_t l_end, void* stream);   // dec_persist.hip
 int avsr_dec_persist_bwd(const avsr_attn_rnn* d, void* stream);                                      // dec_persist_bwd.hip
@@ -478,8 +481,11 @@ static void fill_attn_launch(const avsr_attn_rnn& d, int l, AttnLaunch& AL) {
 
 }  // namespace avsr
 
-// lm != NULL (mode 3 only, checked by the caller): the language-model step runs ahead of every step's selection
-static int attn_rnn_fwd_impl(const avsr_attn_rnn* dp, const avsr_beam_lm* lm, int32_t l_begin, int32_t l_end, void* stream) {
+// lm != NULL (mode 3 only, checked by the caller): the language-model step runs ahead of every step's selection.
+// ctc != NULL (mode 3, weight > 0): the CTC prefix-score step runs after it, and the selection reads ctc->extra -- the two terms
+// combined by that step -- as its one additive term with weight 1 (beam_ctc.hip).
+static int attn_rnn_fwd_impl(const avsr_attn_rnn* dp, const avsr_beam_lm* lm, const avsr_beam_ctc* ctc, int32_t l_begin, int32_t l_end,
+                             void* stream) {
   using namespace avsr;
   int rc = validate(dp);
   if (rc) return rc;
@@ -544,6 +550,7 @@ static int attn_rnn_fwd_impl(const avsr_attn_rnn* dp, const avsr_beam_lm* lm, in
   for (int l = l_first; l < l_end; ++l) {
     // ---- K0: language-model step on the symbols and parents the previous selection left (independent of the decoder's chain) ----
     if (lm && (rc = beam_lm_step_launch(*lm, d.tok, d.parent_rows, l, s))) return rc;
+    if (ctc && (rc = beam_ctc_step_launch(*ctc, d.tok, d.parent_rows, d.beam_fin + (long)(l & 1) * B, l, s))) return rc;
     // ---- K1: LSTM step -------------------------------------------------------------------
     bool cell_done = false;
     if (beam_dense) {
@@ -724,8 +731,9 @@ static int attn_rnn_fwd_impl(const avsr_attn_rnn* dp, const avsr_beam_lm* lm, in
                      d.logits + (long)l * d.V, (long)L * d.V, d.V, K, l, d.eos_id, d.length_penalty, d.beam_logp + (long)pin * B,           \
                      d.beam_fin + (long)pin * B, d.beam_len + (long)pin * B, d.beam_logp + (long)pout * B, d.beam_fin + (long)pout * B,    \
                      d.beam_len + (long)pout * B, d.tok, d.parent_rows, d.step_ids + (long)l * B, d.parent_ids + (long)l * B,              \
-                     d.n_unfinished + l, xa, xsb, O, d.wout_t, d.bout, lm ? lm->lm_logp : nullptr, lm ? lm->lm_weight : 0.f)
-        if (lm) { if (bs_nct == 2) BS_GO(2, true); else if (bs_nct == 4) BS_GO(4, true); else BS_GO(0, true); }
+                     d.n_unfinished + l, xa, xsb, O, d.wout_t, d.bout, ctc ? ctc->extra : lm ? lm->lm_logp : nullptr,                       \
+                     ctc ? 1.f : lm ? lm->lm_weight : 0.f)
+        if (lm || ctc) { if (bs_nct == 2) BS_GO(2, true); else if (bs_nct == 4) BS_GO(4, true); else BS_GO(0, true); }
         else { if (bs_nct == 2) BS_GO(2, false); else if (bs_nct == 4) BS_GO(4, false); else BS_GO(0, false); }
 #undef BS_GO
       } else {
@@ -745,7 +753,7 @@ static int attn_rnn_fwd_impl(const avsr_attn_rnn* dp, const avsr_beam_lm* lm, in
 }
 
 extern "C" int avsr_attn_rnn_fwd(const avsr_attn_rnn* dp, int32_t l_begin, int32_t l_end, void* stream) {
-  return attn_rnn_fwd_impl(dp, nullptr, l_begin, l_end, stream);
+  return attn_rnn_fwd_impl(dp, nullptr, nullptr, l_begin, l_end, stream);
 }
 
 extern "C" int avsr_attn_rnn_fwd_lm(const avsr_attn_rnn* dp, const avsr_beam_lm* lm, int32_t l_begin, int32_t l_end, void* stream) {
@@ -754,7 +762,24 @@ extern "C" int avsr_attn_rnn_fwd_lm(const avsr_attn_rnn* dp, const avsr_beam_lm*
   const int rc = avsr::beam_lm_check(lm);
   if (rc) return rc;
   if (lm->V != dp->V || lm->n_rows != dp->B) return AVSR_ERR_ARG;
-  return attn_rnn_fwd_impl(dp, lm, l_begin, l_end, stream);
+  return attn_rnn_fwd_impl(dp, lm, nullptr, l_begin, l_end, stream);
+}
+
+extern "C" int avsr_attn_rnn_fwd_ctc(const avsr_attn_rnn* dp, const avsr_beam_lm* lm, const avsr_beam_ctc* ctc, int32_t l_begin,
+                                     int32_t l_end, void* stream) {
+  if (!dp || !ctc) return AVSR_ERR_ARG;
+  if (dp->mode != 3) return AVSR_ERR_ARG;                      // joint scoring is defined on the beam
+  int rc = avsr::beam_ctc_check(ctc);
+  if (rc) return rc;
+  if (ctc->V != dp->V || (long)ctc->n_utt * ctc->beam_width != dp->B || ctc->beam_width != dp->beam_width || ctc->eos_id != dp->eos_id)
+    return AVSR_ERR_ARG;
+  if (lm) {
+    if ((rc = avsr::beam_lm_check(lm))) return rc;
+    if (lm->V != dp->V || lm->n_rows != dp->B || ctc->lm_logp != lm->lm_logp) return AVSR_ERR_ARG;
+  } else if (ctc->lm_logp) {
+    return AVSR_ERR_ARG;
+  }
+  return attn_rnn_fwd_impl(dp, lm, ctc->weight == 0.f ? nullptr : ctc, l_begin, l_end, stream);
 }
 
 extern "C" int avsr_attn_rnn_bwd(const avsr_attn_rnn* dp, void* stream) {
@@ -1035,6 +1060,25 @@ extern "C" int avsr_beam_search_step_lm(float* logits, int32_t n_utt, int32_t be
 #undef BS_GO
   AVSR_CHECK_LAUNCH();
   return AVSR_OK;
+}
+
+extern "C" int avsr_beam_search_step_ctc(float* logits, int32_t n_utt, int32_t beam_width, int32_t V, int32_t step, int32_t eos_id,
+                                         float length_penalty_weight, const float* logp_in, const int32_t* fin_in, const int32_t* len_in,
+                                         float* logp_out, int32_t* fin_out, int32_t* len_out, int32_t* tok, int32_t* parent_rows,
+                                         int32_t* step_ids, int32_t* parent_ids, int32_t* n_unfinished, const float* x, int64_t x_stride,
+                                         int32_t O, const float* wout_t, const float* bout, const float* lm_logp, float lm_weight,
+                                         const float* ctc_term, float ctc_weight, float* extra, void* stream) {
+  if (ctc_term && ctc_weight != 0.f) {
+    if (!extra || !(ctc_weight > 0.f) || n_utt <= 0 || beam_width <= 0 || V <= 0) return AVSR_ERR_ARG;
+    const int rc = avsr::beam_ctc_combine_launch(ctc_term, ctc_weight, lm_weight != 0.f ? lm_logp : nullptr, lm_weight, extra,
+                                                 (long)n_utt * beam_width * V, (hipStream_t)stream);
+    if (rc) return rc;
+    lm_logp = extra;
+    lm_weight = 1.f;
+  }
+  return avsr_beam_search_step_lm(logits, n_utt, beam_width, V, step, eos_id, length_penalty_weight, logp_in, fin_in, len_in, logp_out, fin_out,
+                                  len_out, tok, parent_rows, step_ids, parent_ids, n_unfinished, x, x_stride, O, wout_t, bout, lm_logp, lm_weight,
+                                  stream);
 }
 
 extern "C" int avsr_beam_search_step(float* logits, int32_t n_utt, int32_t beam_width, int32_t V, int32_t step, int32_t eos_id,

@@ -8,7 +8,7 @@ import os
 import numpy as np
 import torch
 from . import ops, params as PR
-from ._lib import AttnRnn, BeamLm, MAX_LM_LAYERS, RnnStack
+from ._lib import AttnRnn, BEAM_CTC_MAX_T, BEAM_CTC_MAX_V, BeamCtc, BeamLm, MAX_LM_LAYERS, RnnStack
 from .config import ATT_CODE, BAHDANAU_TYPES, CELL_ID_DECODER, LUONG_TYPES, ModelConfig, encoder_cell_id
 from .model_base import Batch, Ref, SeqBuf, _FlagReader, _PtrView, _splitk, desc_steplen  # noqa: F401
 
@@ -372,16 +372,19 @@ class DecoderMixin:
     def beam_search_decode(self, *args, **kw):
         """See _beam_search_decode.  If a persistent kernel's bounded wait expired during the pass (workgroups not co-resident) the
         results are invalid: check_persistent() has then switched the one-launch paths off and the pass is redone with one launch
-        per step (the ids written to .mlf files and error rates never come from a flagged pass); the redo carries `lm` along."""
+        per step (the ids written to .mlf files and error rates never come from a flagged pass); the redo carries `lm` and `ctc_weight`
+        along."""
         out = self._beam_search_decode(*args, **kw)
         if self.check_persistent():
             out = self._beam_search_decode(*args, **kw)
         return out
 
-    def greedy_decode(self, *args, lm=None, **kw):
+    def greedy_decode(self, *args, lm=None, ctc_weight=0.0, **kw):
         """See _greedy_decode; redone through the per-step launches if a persistent kernel flagged its pass (as above)."""
         if lm is not None:
             raise ValueError("greedy_decode: language-model fusion is defined on the beam (beam_search_decode(lm=...))")
+        if ctc_weight != 0.0:
+            raise ValueError("greedy_decode: joint CTC / attention scoring is defined on the beam (beam_search_decode(ctc_weight=...))")
         out = self._greedy_decode(*args, **kw)
         if self.check_persistent():
             out = self._greedy_decode(*args, **kw)
@@ -389,13 +392,20 @@ class DecoderMixin:
 
     def _beam_search_decode(self, batch: Batch, beam_width: int = 10, length_penalty_weight: Optional[float] = None,
                             max_steps: Optional[int] = None, check_every: int = 8, return_all: bool = False, lm=None,
-                            lm_weight: float = 0.0):
+                            lm_weight: float = 0.0, ctc_weight: float = 0.0):
         """Eval graph with BeamSearchDecoder (decoder_unimodal.py:222-271, decoder_bimodal.py:328-381): ids of beam 0,
         int32 [B, T_out]; positions after the first EOS hold EOS (gather_tree).  length_penalty_weight defaults to the
         reference's 0.6 (unimodal / av_align) or 0.5 (bimodal).
         lm: a Seq2SeqModel with architecture='lm' (LSTM) over the same vocabulary -- shallow fusion: an unfinished beam's step score is
-        log_softmax(logits)[v] + lm_weight * log_softmax(lm logits)[v] (include/avsr_hip.h avsr_beam_lm; csrc/beam_lm.hip)."""
+        log_softmax(logits)[v] + lm_weight * log_softmax(lm logits)[v] (include/avsr_hip.h avsr_beam_lm; csrc/beam_lm.hip).
+        ctc_weight > 0 (a use_ctc model): joint CTC / attention scoring -- the step score also gets ctc_weight * (psi(g . v) - psi(g)),
+        the CTC head's prefix score of the continuation against the beam's (avsr_beam_ctc; csrc/beam_ctc.hip).  0 launches nothing new."""
         cfg, K = self.cfg, int(beam_width)
+        ctc_weight = float(ctc_weight)
+        if not ctc_weight >= 0.0 or ctc_weight == float("inf"):
+            raise ValueError("beam search: ctc_weight must be a finite number >= 0 (got %r)" % (ctc_weight,))
+        if ctc_weight != 0.0 and not cfg.use_ctc:
+            raise ValueError("beam search: ctc_weight needs a model built with use_ctc=True")
         if lm is not None:
             self._check_lm(lm)
         if K < 1 or K > 64 or K * cfg.vocab_size > 1024:
@@ -454,6 +464,7 @@ class DecoderMixin:
         prow.copy_(X["prow0"])
         ops.zero_multi([fin, ln])
         lmd = self._beam_lm_desc(lm, lm_weight, X, R) if lm is not None else None
+        cd = self._beam_ctc_desc(ws, ctc_weight, X, B, K, lmd) if ctc_weight != 0.0 else None
         self._decoder_init_state(wsb)
         self._block_prepare(wsb, D)
         d = self._block_desc(wsb, D, D["steplen"], 3, D["h0"], D["c0"], with_bwd=False)
@@ -473,7 +484,9 @@ class DecoderMixin:
         l, pending = 0, False
         while l < L:
             l1 = min(L, l + check_every)
-            if lmd is None:
+            if cd is not None:
+                ops.attn_rnn_fwd_ctc(d, lmd, cd, l, l1)
+            elif lmd is None:
                 ops.attn_rnn_fwd(d, l, l1)
             else:
                 ops.attn_rnn_fwd_lm(d, lmd, l, l1)
@@ -528,6 +541,34 @@ class DecoderMixin:
         if not ops.beam_lm_supported(m):
             raise ValueError("beam search: the language model's shape is outside avsr_beam_lm_supported")
         return m
+
+    def _beam_ctc_desc(self, ws, weight, X, B, K, lmd):
+        """avsr_beam_ctc over the head's logits of this batch (_ctc_head, encoders in evaluation mode); log-probabilities, the state
+        ping-pong, term and the pre-combined buffer live in the cached beam workspace X.  Queues avsr_beam_ctc_begin."""
+        cfg, dev = self.cfg, self.dev
+        E, Cc = self._ctc_head(ws)
+        T, V, R = E["T"], cfg.vocab_size, B * K
+        if T > BEAM_CTC_MAX_T or V > BEAM_CTC_MAX_V:
+            raise ValueError("beam search: ctc_weight covers encoder memories of up to %d frames and vocabularies of up to %d symbols "
+                             "(avsr_beam_ctc_supported; got %d, %d)" % (BEAM_CTC_MAX_T, BEAM_CTC_MAX_V, T, V))
+        key = ("ctc", T)
+        if key not in X:
+            X[key] = dict(y=torch.zeros(B, T, Cc, device=dev), state=torch.zeros(2, R, T, 2, device=dev), psi=torch.zeros(2, R, device=dev),
+                          last=torch.zeros(2, R, dtype=torch.int32, device=dev), term=torch.zeros(R, V, device=dev),
+                          extra=torch.zeros(R, V, device=dev))
+        buf = X[key]
+        c = BeamCtc()
+        c.n_utt, c.beam_width, c.T, c.V, c.eos_id, c.weight, c.ld = B, K, T, V, cfg.eos_id, float(weight), Cc
+        c.z, c.in_len = ops.fptr(E["ctc_z"]), ops.fptr(E["len"])
+        c.y, c.state, c.psi, c.last = ops.fptr(buf["y"]), ops.fptr(buf["state"]), ops.fptr(buf["psi"]), ops.fptr(buf["last"])
+        c.term, c.extra = ops.fptr(buf["term"]), ops.fptr(buf["extra"])
+        if lmd is not None:
+            c.lm_logp, c.lm_weight = lmd.lm_logp, lmd.lm_weight
+        if not ops.beam_ctc_supported(c):
+            raise ValueError("beam search: the shape (%d utterances x %d beams, %d frames, %d symbols) is outside avsr_beam_ctc_supported"
+                             % (B, K, T, V))
+        ops.beam_ctc_begin(c)
+        return c
 
     def _flag_reader(self):
         if getattr(self, "_fr", None) is None:

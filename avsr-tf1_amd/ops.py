@@ -189,6 +189,36 @@ def beam_lm_step(desc, tok, parent_rows, n_rows, step):
     check(_L().avsr_beam_lm_step(C.byref(desc), fptr(tok), fptr(parent_rows), int(n_rows), int(step), _s()), "avsr_beam_lm_step")
 
 
+def beam_ctc_supported(desc):
+    return bool(_L().avsr_beam_ctc_supported(C.byref(desc)))
+
+
+def beam_ctc_begin(desc):
+    """Once per decode (include/avsr_hip.h avsr_beam_ctc): log_softmax of the head's rows into desc.y, the empty prefix into half 0."""
+    check(_L().avsr_beam_ctc_begin(C.byref(desc), _s()), "avsr_beam_ctc_begin")
+
+
+def beam_ctc_step(desc, tok, parent_rows, fin, step):
+    """One CTC prefix-score step over the hypothesis rows: the state's other half, desc.term and desc.extra."""
+    check(_L().avsr_beam_ctc_step(C.byref(desc), fptr(tok), fptr(parent_rows), fptr(fin), int(step), _s()), "avsr_beam_ctc_step")
+
+
+def beam_search_step_ctc(logits, n_utt, beam_width, V, step, eos_id, length_penalty_weight, logp_in, fin_in, len_in, logp_out, fin_out, len_out,
+                         tok, parent_rows, step_ids, parent_ids, n_unfinished, lm_logp, lm_weight, ctc_term, ctc_weight, extra,
+                         x=None, x_stride=0, O=0, wout_t=None, bout=None):
+    """beam_search_step_lm with + ctc_weight * ctc_term on unfinished beams (ctc_term None or weight 0: beam_search_step_lm exactly)."""
+    check(_L().avsr_beam_search_step_ctc(fptr(logits), n_utt, beam_width, V, step, eos_id, float(length_penalty_weight), fptr(logp_in),
+                                         fptr(fin_in), fptr(len_in), fptr(logp_out), fptr(fin_out), fptr(len_out), fptr(tok), fptr(parent_rows),
+                                         fptr(step_ids), fptr(parent_ids), fptr(n_unfinished), fptr(x), x_stride, O, fptr(wout_t), fptr(bout),
+                                         fptr(lm_logp), float(lm_weight), fptr(ctc_term), float(ctc_weight), fptr(extra), _s()),
+          "avsr_beam_search_step_ctc")
+
+
+def attn_rnn_fwd_ctc(desc, lm_desc, ctc_desc, l_begin, l_end):
+    check(_L().avsr_attn_rnn_fwd_ctc(C.byref(desc), C.byref(lm_desc) if lm_desc is not None else None, C.byref(ctc_desc), int(l_begin),
+                                     int(l_end), _s()), "avsr_attn_rnn_fwd_ctc")
+
+
 def attn_rnn_fwd_lm(desc, lm_desc, l_begin, l_end):
     check(_L().avsr_attn_rnn_fwd_lm(C.byref(desc), C.byref(lm_desc), int(l_begin), int(l_end), _s()), "avsr_attn_rnn_fwd_lm")
 

@@ -445,6 +445,61 @@ int avsr_beam_search_step_lm(float* logits, int32_t n_utt, int32_t beam_width, i
  * parent_rows = identity) and its output is not read. */
 int avsr_attn_rnn_fwd_lm(const avsr_attn_rnn* d, const avsr_beam_lm* lm, int32_t l_begin, int32_t l_end, void* stream);
 
+/* Joint CTC / attention scoring inside beam search (csrc/beam_ctc.hip; the rule is this project's own):
+ *   step_logp[k][v] = log_softmax(logits_am[k])[v] (+ lm_weight * log p_lm) + weight * (psi(g_k . v) - psi(g_k))      (unfinished beam k)
+ * psi(g) = log-probability, under the CTC head, of all label sequences that start with the beam's label prefix g; psi(g . EOS) =
+ * log p_ctc(g | x).  The term is 0 where psi(g_k) = -inf or the utterance has no frames, may be -inf, is never NaN; a finished beam
+ * gets none.  The terms telescope: a beam that ends with EOS has accumulated weight * log p_ctc(its labels | x).
+ * z: the head's logits [n_utt * T][ld] over V + 1 real classes, the blank is class V; in_len [n_utt], T_b = clamp(in_len, 0, T).
+ * Buffers: y [n_utt][T][V + 1] (log_softmax of the rows t < T_b); state [2][R][T][2] (r_n, r_b per frame), psi [2][R], last [2][R]
+ * with R = n_utt * beam_width: a ping-pong like avsr_beam_lm's -- avsr_beam_ctc_begin writes the empty prefix into half 0, step s reads
+ * row parent_rows[r] of half s & 1 and writes row r of half (s + 1) & 1 (step 0: tok = GO, the empty prefix is copied through and
+ * scored; a row with tok = EOS or fin != 0 copies its parent through and gets term 0).  term [R][V]; extra [R][V] = weight * term
+ * (+ lm_weight * lm_logp where lm_logp != NULL: the buffer the selection reads as its one additive term, with weight 1).
+ * 1 <= T <= AVSR_BEAM_CTC_MAX_T, 2 <= V <= AVSR_BEAM_CTC_MAX_V, beam_width <= 64, weight >= 0, ld >= V + 1. */
+#define AVSR_BEAM_CTC_MAX_T 2048
+#define AVSR_BEAM_CTC_MAX_V 256
+typedef struct avsr_beam_ctc {
+  int32_t n_utt, beam_width, T, V;
+  int32_t eos_id;
+  float weight;
+  int64_t ld;
+  const float* z;
+  const int32_t* in_len;
+  float* y;
+  float* state;
+  float* psi;
+  int32_t* last;
+  float* term;
+  float* extra;
+  const float* lm_logp;      /* NULL, or the fused language model's [R][V] (avsr_beam_lm.lm_logp) */
+  float lm_weight;
+  int32_t pad_;
+} avsr_beam_ctc;
+/* 1 if the entry points below run this descriptor, else 0 (decided on the host; nothing is dereferenced). */
+int avsr_beam_ctc_supported(const avsr_beam_ctc* ctc);
+/* Once per decode: y and the empty prefix's state (half 0).  One launch. */
+int avsr_beam_ctc_begin(const avsr_beam_ctc* ctc, void* stream);
+/* One step over the R rows: state update, then term and extra.  tok / parent_rows / fin [R] as avsr_beam_search_step leaves them
+ * (values outside [0, V) / [0, R) are clamped: nothing outside the buffers is addressed).  One launch. */
+int avsr_beam_ctc_step(const avsr_beam_ctc* ctc, const int32_t* tok, const int32_t* parent_rows, const int32_t* fin, int32_t step,
+                       void* stream);
+/* avsr_beam_search_step_lm with the CTC term next to the language model's: ctc_term [n_utt * beam_width][V] and a scratch buffer
+ * extra of the same size, into which weight * ctc_term (+ lm_weight * lm_logp) is combined first.  ctc_term == NULL or
+ * ctc_weight == 0: avsr_beam_search_step_lm exactly (extra is not touched). */
+int avsr_beam_search_step_ctc(float* logits, int32_t n_utt, int32_t beam_width, int32_t V, int32_t step, int32_t eos_id,
+                              float length_penalty_weight, const float* logp_in, const int32_t* fin_in, const int32_t* len_in,
+                              float* logp_out, int32_t* fin_out, int32_t* len_out, int32_t* tok, int32_t* parent_rows,
+                              int32_t* step_ids, int32_t* parent_ids, int32_t* n_unfinished, const float* x, int64_t x_stride,
+                              int32_t O, const float* wout_t, const float* bout, const float* lm_logp, float lm_weight,
+                              const float* ctc_term, float ctc_weight, float* extra, void* stream);
+/* avsr_attn_rnn_fwd in mode 3 with avsr_beam_ctc_step -- after avsr_beam_lm_step when lm != NULL -- ahead of every selection, under
+ * every avsr_attn_rnn_set_beam_kernel setting (ctc->n_utt * ctc->beam_width == d->B, ctc->V == d->V; with lm, ctc->lm_logp must be
+ * lm->lm_logp).  The caller has run avsr_beam_ctc_begin.  ctc->weight == 0: avsr_attn_rnn_fwd / avsr_attn_rnn_fwd_lm exactly, no CTC
+ * launch.  A step queued after the search has ended (tok = EOS, parent_rows = identity) copies state through and is not read. */
+int avsr_attn_rnn_fwd_ctc(const avsr_attn_rnn* d, const avsr_beam_lm* lm, const avsr_beam_ctc* ctc, int32_t l_begin, int32_t l_end,
+                          void* stream);
+
 /* Post-loop helpers of the attention backward (see csrc/attention.hip). */
 int avsr_attn_alpha_rows(float* scores, const float* dscores, const int32_t* len, const int32_t* steplen,
                          const float* g, float* rowdot, int32_t B, int32_t L, int32_t T, void* stream);
