@@ -154,6 +154,14 @@ class CtcArgs(C.Structure):
                [(n, C.c_void_p) for n in ("nll", "status", "utt_loss", "dz", "ws")] + [("ws_floats", C.c_int64)]
 
 
+CTC_PREFIX_MAX_V, CTC_PREFIX_MAX_W, CTC_PREFIX_MAX_L = 256, 64, 512     # AVSR_CTC_PREFIX_MAX_* of include/avsr_hip.h
+
+
+class CtcPrefixArgs(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("B", "T", "V", "beam_width", "L_max", "pad_")] + [("ld", C.c_int64)] + \
+               [(n, C.c_void_p) for n in ("z", "in_len", "ids", "lens", "score", "trace_parent", "trace_sym", "trace_pb", "trace_pnb")]
+
+
 class ColsumJob(C.Structure):
     _fields_ = [("a", Mat), ("b", Mat), ("out", C.c_void_p), ("rows", C.c_int32), ("F", C.c_int32), ("alpha", C.c_float), ("beta", C.c_float)]
 
@@ -164,7 +172,7 @@ class TransposeJob(C.Structure):
 
 _STRUCTS = {"avsr_dec_layer": DecLayer, "avsr_mat": Mat, "avsr_gemm_desc": GemmDesc, "avsr_rnn_layer": RnnLayer, "avsr_rnn_stack": RnnStack,
             "avsr_conv_desc": ConvDesc, "avsr_conv_launch": ConvLaunch, "avsr_conv3d_desc": Conv3dDesc, "avsr_logmel_args": LogmelArgs, "avsr_ctc_args": CtcArgs, "avsr_attn_mech": AttnMech, "avsr_attn_rnn": AttnRnn, "avsr_transpose_job": TransposeJob,
-            "avsr_colsum_job": ColsumJob, "avsr_beam_lm": BeamLm, "avsr_beam_ctc": BeamCtc}
+            "avsr_colsum_job": ColsumJob, "avsr_beam_lm": BeamLm, "avsr_beam_ctc": BeamCtc, "avsr_ctc_prefix_args": CtcPrefixArgs}
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 # argument types of every entry point that returns an int status (include/avsr_hip.h)
@@ -208,6 +216,8 @@ _SIGS = {
     "avsr_logmel_fwd": [C.POINTER(LogmelArgs), _vp],
     "avsr_ctc_loss": [C.POINTER(CtcArgs), _vp],
     "avsr_ctc_best_path": [_vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp],
+    "avsr_ctc_prefix_search_supported": [_i32, _i32, _i32],
+    "avsr_ctc_prefix_search": [C.POINTER(CtcPrefixArgs), _vp],
     "avsr_batchnorm_apply": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp],
     "avsr_attn_rnn_bwd": [C.POINTER(AttnRnn), _vp],
     "avsr_beam_gather_tree": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],

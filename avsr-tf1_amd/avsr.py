@@ -30,6 +30,8 @@ ctc_weight * CTC loss per label token to the step's loss, and `evaluate` also re
 'ctc_' + unit (csrc/ctc.hip).  `ctc_decode_weight` (0.0 = off) is an evaluate-time option of a `use_ctc` model:
 beam search then adds ctc_decode_weight * (CTC prefix score of the continuation - that of the beam) to an unfinished beam's step score
 (joint CTC / attention decoding, csrc/beam_ctc.hip); it works together with `lm_checkpoint`.
+`decoding_algorithm='ctc_prefix_beam_search'` (a `use_ctc` model; not in the reference) makes `evaluate` take its predictions from a CTC
+prefix beam search of width `beam_width` on that head alone -- no decoder step (csrc/ctc_prefix.hip).
 """
 import glob
 import os
@@ -136,9 +138,18 @@ class AVSR(object):
             from .audio_frontend import LogmelSpec
             self._audio_frontend = LogmelSpec(kwargs.get('audio_transformation', 'logmel_stack_w8s3'), kwargs.get('num_mel_bins', 30),
                                               kwargs.get('sample_rate', 16000))
-        if decoding_algorithm not in ('greedy', 'beam_search'):
-            raise Exception('The only supported algorithms are `greedy` and `beam_search`')     # decoder_unimodal.py:124
+        if decoding_algorithm not in ('greedy', 'beam_search', 'ctc_prefix_beam_search'):
+            raise Exception('The only supported algorithms are `greedy`, `beam_search` and (not in the reference) '
+                            '`ctc_prefix_beam_search`')                                          # decoder_unimodal.py:124
         self._decoding_algorithm, self._beam_width = decoding_algorithm, beam_width
+        if decoding_algorithm == 'ctc_prefix_beam_search':    # the CTC head's own search (csrc/ctc_prefix.hip): no decoder step at evaluate
+            from ._lib import CTC_PREFIX_MAX_L, CTC_PREFIX_MAX_V, CTC_PREFIX_MAX_W
+            if not kwargs.get('use_ctc', False):
+                raise ValueError("decoding_algorithm='ctc_prefix_beam_search' needs use_ctc=True: the search runs on the CTC head")
+            if len(self._unit_dict) - 1 > CTC_PREFIX_MAX_V or not 1 <= beam_width <= CTC_PREFIX_MAX_W:
+                raise ValueError("decoding_algorithm='ctc_prefix_beam_search': avsr_ctc_prefix_search covers vocabularies of up to %d "
+                                 "symbols and beam widths of 1 to %d (label sequences of up to %d; got %d symbols, beam_width %d)"
+                                 % (CTC_PREFIX_MAX_V, CTC_PREFIX_MAX_W, CTC_PREFIX_MAX_L, len(self._unit_dict) - 1, beam_width))
         self._write_attention_alignment = bool(write_attention_alignment)
         if self._write_attention_alignment and decoding_algorithm != 'greedy':
             raise NotImplementedError("write_attention_alignment=True needs decoding_algorithm='greedy' (the alignment history is "
@@ -466,9 +477,12 @@ class AVSR(object):
                 ids = self._model.beam_search_decode(batch, beam_width=self._beam_width, max_steps=self._cfg.max_label_length,
                                                      lm=self._lm, lm_weight=self._lm_weight if self._lm is not None else 0.0,
                                                      ctc_weight=self._ctc_decode_weight)
+            elif self._decoding_algorithm == 'ctc_prefix_beam_search':     # the head's own search: the attention decoder never runs
+                ids = self._model.ctc_prefix_beam_search(batch, beam_width=self._beam_width, max_steps=self._cfg.max_label_length)
             else:
                 ids = self._model.greedy_decode(batch, max_steps=self._cfg.max_label_length)
-            ids = ids.cpu().numpy()
+            if not isinstance(ids, list):
+                ids = ids.cpu().numpy()
             if self._write_attention_alignment:
                 self._write_alignments(names, alignments_outdir)
             for idx in range(len(names)):

@@ -8,7 +8,7 @@ import os
 import numpy as np
 import torch
 from . import ops, params as PR
-from ._lib import AttnRnn, RnnStack
+from ._lib import AttnRnn, CTC_PREFIX_MAX_L, CTC_PREFIX_MAX_V, CTC_PREFIX_MAX_W, RnnStack
 from .config import ATT_CODE, BAHDANAU_TYPES, CELL_ID_DECODER, LUONG_TYPES, ModelConfig, encoder_cell_id
 from .model_base import Batch, Ref, SeqBuf, _FlagReader, _PtrView, _splitk, desc_steplen  # noqa: F401
 
@@ -487,6 +487,47 @@ class EncoderMixin:
                 prev = k
             out.append(seq)
         return out
+
+    def ctc_prefix_beam_search(self, batch, beam_width=10, max_steps=None, nbest=False):
+        """use_ctc: CTC prefix beam search on the head alone (avsr_ctc_prefix_search, csrc/ctc_prefix.hip; the rule is INTEGRATION.md
+        section 8) -- encoders in evaluation mode, the head, ONE launch for the batch; no decoder step.  max_steps bounds the label
+        sequences (default: max_label_length).  One id list per utterance, the beam's best; nbest=True: per utterance the whole final
+        beam as (ids, score) pairs, best first, score = log p_ctc(ids | x) up to what pruning lost."""
+        out = self._ctc_prefix_beam_search(batch, beam_width, max_steps, nbest)
+        if self.check_persistent():
+            out = self._ctc_prefix_beam_search(batch, beam_width, max_steps, nbest)
+        return out
+
+    def _ctc_prefix_beam_search(self, batch, beam_width, max_steps, nbest):
+        cfg, dev = self.cfg, self.dev
+        if not cfg.use_ctc:
+            raise ValueError("ctc_prefix_beam_search needs a model built with use_ctc=True")
+        W, V = int(beam_width), cfg.vocab_size
+        Lm = int(cfg.max_label_length if max_steps is None else max_steps)
+        if W < 1 or Lm < 1:
+            raise ValueError("ctc_prefix_beam_search: beam_width and max_steps must be positive (got %d, %d)" % (W, Lm))
+        if not ops.ctc_prefix_search_supported(V, W, Lm):
+            raise ValueError("ctc_prefix_beam_search: avsr_ctc_prefix_search covers vocabularies of up to %d symbols, beam widths of up to "
+                             "%d and label sequences of up to %d (got %d, %d, %d)"
+                             % (CTC_PREFIX_MAX_V, CTC_PREFIX_MAX_W, CTC_PREFIX_MAX_L, V, W, Lm))
+        B = (batch.audio if batch.audio is not None else batch.video).shape[0]
+        Ta = self._audio_rows(batch)
+        Tv = batch.video.shape[1] if batch.video is not None else 0
+        ws = self._get_ws(B, Ta, Tv, 1, True)
+        self._refresh_derived()
+        self._encode(ws, batch, False)
+        E, Cc = self._ctc_head(ws)
+        key = ("ctc_prefix", W, Lm)
+        if key not in E:
+            E[key] = (torch.zeros(B, W, Lm, dtype=torch.int32, device=dev), torch.zeros(B, W, dtype=torch.int32, device=dev),
+                      torch.zeros(B, W, device=dev))
+        ids, lens, score = E[key]
+        ops.ctc_prefix_search(E["ctc_z"], Cc, E["len"], B, E["T"], V, W, Lm, ids, lens, score)
+        ids, lens, score = ids.cpu().numpy(), lens.cpu().numpy(), score.cpu().numpy()
+        if not nbest:
+            return [[int(s) for s in ids[b, 0, :lens[b, 0]]] for b in range(B)]
+        return [[([int(s) for s in ids[b, r, :lens[b, r]]], float(score[b, r])) for r in range(W) if score[b, r] > float("-inf")]
+                for b in range(B)]
 
     def persistent_flagged(self):
         """Read-only form of check_persistent(): did a persistent kernel flag the last pass on THIS rank?"""

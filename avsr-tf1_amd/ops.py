@@ -386,6 +386,23 @@ def ctc_best_path(z, ld, in_len, B, T, n_classes, ids):
     check(_L().avsr_ctc_best_path(fptr(z), int(ld), fptr(in_len), int(B), int(T), int(n_classes), fptr(ids), _s()), "avsr_ctc_best_path")
 
 
+def ctc_prefix_search_supported(V, beam_width, L_max):
+    """Host-side: does avsr_ctc_prefix_search run this shape (include/avsr_hip.h AVSR_CTC_PREFIX_MAX_*)?"""
+    return bool(_L().avsr_ctc_prefix_search_supported(int(V), int(beam_width), int(L_max)))
+
+
+def ctc_prefix_search(z, ld, in_len, B, T, V, beam_width, L_max, ids, lens, score, trace=None):
+    """avsr_ctc_prefix_search: z [B*T, ld] over V + 1 real classes (blank = V) -> the final beam ids [B, W, L_max] (-1 padded), lens and
+    score [B, W], sorted.  trace: None, or (parent, sym, pb, pnb), each [B, T, W] -- the beam after every frame."""
+    from ._lib import CtcPrefixArgs
+    a = CtcPrefixArgs()
+    a.B, a.T, a.V, a.beam_width, a.L_max, a.ld = int(B), int(T), int(V), int(beam_width), int(L_max), int(ld)
+    a.z, a.in_len, a.ids, a.lens, a.score = fptr(z), fptr(in_len), fptr(ids), fptr(lens), fptr(score)
+    if trace is not None:
+        a.trace_parent, a.trace_sym, a.trace_pb, a.trace_pnb = (fptr(t) for t in trace)
+    check(_L().avsr_ctc_prefix_search(C.byref(a), _s()), "avsr_ctc_prefix_search")
+
+
 def normed_v(v, g, vn, H):
     check(_L().avsr_normed_v(fptr(v), fptr(g), fptr(vn), H, _s()), "avsr_normed_v")
 

@@ -500,6 +500,39 @@ int avsr_beam_search_step_ctc(float* logits, int32_t n_utt, int32_t beam_width, 
 int avsr_attn_rnn_fwd_ctc(const avsr_attn_rnn* d, const avsr_beam_lm* lm, const avsr_beam_ctc* ctc, int32_t l_begin, int32_t l_end,
                           void* stream);
 
+/* CTC prefix beam search on the head's logits alone (csrc/ctc_prefix.hip; the rule is this project's own):
+ * frame-synchronous, sums over alignments, no decoder step.  z [B * T][ld] are the head's logits over V + 1 real classes, the blank
+ * is class V; in_len [B], T_b = clamp(in_len, 0, T).  Frames t >= T_b and columns >= V + 1 of a wider row are never read.
+ * Outputs, per utterance the final beam sorted by p = p_b (+) p_nb descending (ties: the lower candidate index):
+ *   ids [B][beam_width][L_max] (-1 padded), lens [B][beam_width] (0 for an empty slot), score [B][beam_width] (p; -inf for an empty
+ *   slot).  Without pruning p is log p_ctc(labels | x); T_b = 0 gives the empty sequence with score 0.  Nothing is ever NaN.
+ * Trace (all four NULL in production, or all four given): the beam after every frame t < T_b as [B][T][beam_width] -- the slot of the
+ * previous beam it continues, the symbol (V = stay; -1 / -1 for an empty slot), p_b and p_nb.  Rows t >= T_b are not written.
+ * One launch, one workgroup per utterance, no atomics: bit-identical across launches.
+ * Limits (all state of the search lives in LDS): 1 <= V <= 256, 1 <= beam_width <= 64, 1 <= L_max <= 512 -- at the three maxima the
+ * workgroup holds 135 KiB of the CU's 160 KiB. */
+#define AVSR_CTC_PREFIX_MAX_V 256
+#define AVSR_CTC_PREFIX_MAX_W 64
+#define AVSR_CTC_PREFIX_MAX_L 512
+typedef struct avsr_ctc_prefix_args {
+  int32_t B, T, V, beam_width, L_max;
+  int32_t pad_;
+  int64_t ld;
+  const float* z;
+  const int32_t* in_len;
+  int32_t* ids;
+  int32_t* lens;
+  float* score;
+  int32_t* trace_parent;
+  int32_t* trace_sym;
+  float* trace_pb;
+  float* trace_pnb;
+} avsr_ctc_prefix_args;
+/* 1 if avsr_ctc_prefix_search runs this shape, else 0 (decided on the host; nothing is dereferenced). */
+int avsr_ctc_prefix_search_supported(int32_t V, int32_t beam_width, int32_t L_max);
+/* AVSR_ERR_ARG for a NULL / non-positive / inconsistent argument, AVSR_ERR_UNSUPPORTED outside the limits: both before any launch. */
+int avsr_ctc_prefix_search(const avsr_ctc_prefix_args* a, void* stream);
+
 /* Post-loop helpers of the attention backward (see csrc/attention.hip). */
 int avsr_attn_alpha_rows(float* scores, const float* dscores, const int32_t* len, const int32_t* steplen,
                          const float* g, float* rowdot, int32_t B, int32_t L, int32_t T, void* stream);
