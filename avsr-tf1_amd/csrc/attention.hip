@@ -20,6 +20,7 @@
 #include "attn.h"
 #include "prof.h"
 #include "persist.h"
+#include "beam_gemm.h"
 
 namespace avsr {
 
@@ -644,7 +645,6 @@ __global__ void bahdanau_dkeys_kernel(const float* keys, const float* pq, long p
 
 }  // namespace avsr
 
-namespace avsr { extern int g_beam_dense; bool beam_dense_on(); }
 static int g_beam_on = 1;
 extern "C" int avsr_attn_rnn_set_beam_kernel(int32_t on) { g_beam_on = on ? 1 : 0; avsr::g_beam_dense = on == 1 ? 1 : 0; return AVSR_OK; }
 

@@ -9,21 +9,12 @@
 // GEMMs over all L steps (done by the caller with avsr_gemm).
 #include "step.h"
 #include "attn.h"
+#include "beam.h"          // the selection step, the LM / CTC steps ahead of it
+#include "beam_gemm.h"     // the tiled cell / attention-layer steps of mode 3
+#include "dec_persist.h"   // the fused launches tried first
 
-extern "C" int avsr_step_launch_raw(const void* launch, void* stream);
-extern "C" int avsr_attn_launch_raw(const void* launch, int backward, void* stream);
-namespace avsr {
-bool beam_dense_on();
-int beam_cell_launch(const avsr_attn_rnn& d, int l, hipStream_t s);
-int beam_attention_layer_launch(const avsr_attn_rnn& d, int l, hipStream_t s);
-int beam_lm_check(const avsr_beam_lm* m);                                                                  // beam_lm.hip
-int beam_lm_step_launch(const avsr_beam_lm& m, const int32_t* tok, const int32_t* parent_rows, int step, hipStream_t s);
-int beam_ctc_check(const avsr_beam_ctc* c);                                                               // beam_ctc.hip
-int beam_ctc_step_launch(const avsr_beam_ctc& c, const int32_t* tok, const int32_t* parent_rows, const int32_t* fin, int step, hipStream_t s);
-int beam_ctc_combine_launch(const float* term, float weight, const float* lm_logp, float lm_weight, float* extra, long n, hipStream_t s);
-}
-int avsr_dec_persist_fwd(const avsr_attn_rnn* d, int32_t l_begin, int32_t l_end, void* stream);   // dec_persist.hip
-int avsr_dec_persist_bwd(const avsr_attn_rnn* d, void* stream);                                      // dec_persist_bwd.hip
+extern "C" int avsr_step_launch_raw(const void* launch, void* stream);                  // step.hip
+extern "C" int avsr_attn_launch_raw(const void* launch, int backward, void* stream);    // attention.hip
 
 namespace avsr {
 
@@ -193,217 +184,6 @@ __global__ __launch_bounds__(256) void logits_sample_kernel(const float* x, long
   }
 }
 
-// One BeamSearchDecoder step for one utterance (one 256-thread workgroup per utterance): see avsr_hip.h mode 3 and
-// oracle.beam_search_decode.  Everything the step reads comes in with ONE round of loads; the per-beam log-sum-exp is a wave reduction,
-// its logf / the 2 K length penalties (powf) run one per lane side by side; every thread keeps its (at most two) candidates
-// -- score as a sortable 32-bit key, accumulated log-probability -- in REGISTERS, and the top K are K rounds of
-// {wave arg-max of a 64-bit (score key, ~index) word, four wave winners through LDS}: larger score first, LOWER index on ties
-// (= tf.nn.top_k's order; -inf scores stay selectable, in index order).
-// History, measured at c4 (B * K = 640 rows, V = 31; profiles/r04_beam_gemm_dissect.txt): round 2 one thread selecting serially 165 us;
-// round 3 one wave, candidates in LDS, parents' flags loaded inside every round 22 us; rank by counting (every candidate against
-// every other, broadcast LDS reads) 28 us -- 310 x 310 comparisons are more instructions than ten reductions.
-// NCT > 0: the output layer runs here too (seq2seq.py:339 the decoder's Dense(vocab) under BeamSearchDecoder): the utterance's K rows of
-// the attention output [K x O] times Wout^T [O x V] as NCT 16-column tiles of v_mfma_f32_16x16x4_f32, wave w taking the O / 4 inputs
-// [w O / 4, (w + 1) O / 4), the four partial tiles summed through LDS -- one launch and one read-back of the logits less per step
-// (the separate projection was a 7 us launch of 640 x 31 outputs).  Needs K <= 16, V <= 16 NCT, O % 256 == 0.  NCT == 0: logits given.
-// LM: shallow fusion (avsr_beam_lm): an unfinished beam's step log-probability gets + lm_weight * lm_logp[row][v], lm_logp = the
-// language model's log_softmax [B * K][V] (beam_lm.hip).  Weight 0 takes the branch without the term, so the search is bit for bit the
-// one without a model; LM == false compiles the term out (lm_logp / lm_weight unused): the instruction stream of the search as it was.
-template <int NCT, bool LM>
-__global__ __launch_bounds__(256) void beam_step_kernel(float* logits, long logits_sb, int V, int K, int l, int eos, float w,
-                                 const float* logp_in, const int32_t* fin_in, const int32_t* len_in,
-                                 float* logp_out, int32_t* fin_out, int32_t* len_out, int32_t* tok, int32_t* parent_rows,
-                                 int32_t* step_ids, int32_t* parent_ids, int32_t* n_unfinished,
-                                 const float* xa, long xsb, int O, const float* wout_t, const float* bout,
-                                 const float* lm_logp, float lm_weight) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];   // logits [K*V] | lse [K] | max [K] | sum [K] | penalties [K][2] | fin [K] | len [K] | logp [K] | alive | winners [2][4] x 64 bit
-  const int n = K * V;
-  float* lg_s = sm;
-  float* lse_s = lg_s + n;
-  float* mx_s = lse_s + K;
-  float* sum_s = mx_s + K;
-  float* pen = sum_s + K;
-  int* fin_s = reinterpret_cast<int*>(pen + 2 * K);
-  int* len_s = fin_s + K;
-  float* logp_s = reinterpret_cast<float*>(len_s + K);
-  int* alive_s = reinterpret_cast<int*>(logp_s + K);
-  unsigned long long* win = reinterpret_cast<unsigned long long*>(sm + ((n + 8 * K + 1 + 1) & ~1));      // 8-byte aligned
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float FMIN = -3.4028234663852886e38f;
-  // Steps queued past the end of the search (the host reads the "all finished" counter a chunk late): dynamic_decode has stopped, so
-  // the step hands its input state through unchanged.  Without this a beam that finished at the last real step would be re-scored with
-  // len + 1 and the beams re-ordered -- harmless for gather_tree (it reads step_ids / parent_ids [:T] and the maximum length) but not for
-  // a caller reading the per-beam state afterwards.  n_unfinished[-1] is the previous step's count, complete when this launch starts.
-  if (l > 0 && n_unfinished[-1] == 0) {
-    if (tid < K) {
-      const int r = b * K + tid;
-      logp_out[r] = logp_in[r]; fin_out[r] = fin_in[r]; len_out[r] = len_in[r];
-      tok[r] = eos; parent_rows[r] = r; step_ids[r] = eos; parent_ids[r] = tid;
-    }
-    return;
-  }
-  if (tid < K) { fin_s[tid] = fin_in[b * K + tid]; len_s[tid] = len_in[b * K + tid]; logp_s[tid] = logp_in[b * K + tid]; }
-  if (tid == 0) alive_s[0] = 0;
-  if constexpr (NCT > 0) {
-    typedef float f32x4 __attribute__((ext_vector_type(4)));
-    float* part = reinterpret_cast<float*>(win + 8);               // [4 waves][16 rows][16 NCT columns]
-    const int i16 = lane & 15, g = lane >> 4, kw = O >> 2;
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-    const float* xr = xa + (long)(b * K + (i16 < K ? i16 : 0)) * xsb + wave * kw + 4 * g;
-    const float* wr[NCT];
-    f32x4 acc[NCT];
-#pragma unroll
-    for (int c = 0; c < NCT; ++c) {
-      const int v = c * 16 + i16;
-      wr[c] = wout_t + (long)(v < V ? v : 0) * O + wave * kw + 4 * g;
-      acc[c] = zero;
-    }
-    const bool arow = i16 < K;
-#pragma unroll 1
-    for (int kk = 0; kk < kw; kk += 64) {                         // lane (i16, g) holds inputs kk + 16 u + 4 g .. + 3 of row / column i16
-      f32x4 a[4], bv[4][NCT];                                     // (all loads of four 16-input groups in flight, then their products)
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        a[u] = *reinterpret_cast<const f32x4*>(xr + kk + 16 * u);
-#pragma unroll
-        for (int c = 0; c < NCT; ++c) bv[u][c] = *reinterpret_cast<const f32x4*>(wr[c] + kk + 16 * u);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        if (!arow) a[u] = zero;
-#pragma unroll
-        for (int c = 0; c < NCT; ++c) if (c * 16 + i16 >= V) bv[u][c] = zero;
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-          for (int c = 0; c < NCT; ++c) acc[c] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][e], bv[u][c][e], acc[c], 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < NCT; ++c)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) part[(wave * 16 + 4 * g + r) * (16 * NCT) + c * 16 + i16] = acc[c][r];
-    __syncthreads();
-    for (int i = tid; i < n; i += 256) {
-      const int k = i / V, v = i - k * V, o = k * (16 * NCT) + v;
-      const float sv = ((part[o] + part[256 * NCT + o]) + (part[512 * NCT + o] + part[768 * NCT + o])) + bout[v];
-      lg_s[i] = sv;
-      logits[(long)(b * K + k) * logits_sb + v] = sv;
-    }
-  } else {
-    for (int i = tid; i < n; i += 256) {
-      const int k = i / V, v = i - k * V;
-      lg_s[i] = logits[(long)(b * K + k) * logits_sb + v];
-    }
-  }
-  __syncthreads();
-  for (int k = wave; k < K; k += 4) {                 // max and exp-sum of beam k: wave reductions over its V logits
-    float mx = -INFINITY;
-    for (int v = lane; v < V; v += 64) mx = fmaxf(mx, lg_s[k * V + v]);
-    mx = wave_max(mx);
-    float sum = 0.f;
-    for (int v = lane; v < V; v += 64) sum += expf(lg_s[k * V + v] - mx);
-    sum = wave_sum(sum);
-    if (lane == 0) { mx_s[k] = mx; sum_s[k] = sum; }
-  }
-  __syncthreads();
-  // one logf / powf per lane: K log-sum-exps on wave 0, the 2 K length penalties ((5 + len) / 6) ^ w of the two possible lengths of a
-  // beam's continuations on waves 1-3 (the same powf values as one call per candidate)
-  if (tid < K) lse_s[tid] = mx_s[tid] + logf(sum_s[tid]);
-  for (int j = tid - 64; j >= 0 && j < 2 * K; j += 192) pen[j] = powf((5.0f + (float)(len_s[j >> 1] + (j & 1))) / 6.0f, w);
-  __syncthreads();
-  // ---- this thread's candidates i = tid + 256 c: key (0 = none / taken) and accumulated log-probability, in registers ----
-  constexpr int NC = 4;                               // K * V <= 1024
-  unsigned key[NC];
-  float tot[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int i = tid + 256 * c;
-    key[c] = 0u; tot[c] = 0.f;
-    if (i < n) {
-      const int k = i / V, v = i - k * V;
-      const bool fin = fin_s[k] != 0;
-      float sl = fin ? (v == eos ? 0.f : FMIN) : lg_s[i] - lse_s[k];
-      if constexpr (LM) {
-        if (!fin && lm_weight != 0.f) sl += lm_weight * lm_logp[(long)(b * K + k) * V + v];
-      }
-      const float t = logp_s[k] + sl;
-      const float sc = t / pen[2 * k + ((fin || v == eos) ? 0 : 1)];
-      const unsigned u = __builtin_bit_cast(unsigned, sc);
-      key[c] = (u & 0x80000000u) ? ~u : (u | 0x80000000u);        // monotone in the score; -inf -> 0x007fffff (> 0 = none)
-      tot[c] = t;
-    }
-  }
-  int alive = 0;
-  for (int j = 0; j < K; ++j) {
-    // this thread's best remaining candidate as one 64-bit word: (score key, ~index) -- larger is better, lower index wins ties
-    unsigned long long best = 0ull;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      const unsigned long long cand = key[c] ? (((unsigned long long)key[c] << 32) | (unsigned)(0xffffffffu - (unsigned)(tid + 256 * c))) : 0ull;
-      best = cand > best ? cand : best;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const unsigned hi = (unsigned)__shfl_xor((int)(best >> 32), o, 64), lo = (unsigned)__shfl_xor((int)(unsigned)best, o, 64);
-      const unsigned long long other = ((unsigned long long)hi << 32) | lo;
-      best = other > best ? other : best;
-    }
-    unsigned long long* slot = win + (j & 1) * 4;
-    if (lane == 0) slot[wave] = best;
-    __syncthreads();
-    unsigned long long g = slot[0];
-#pragma unroll
-    for (int q = 1; q < 4; ++q) g = slot[q] > g ? slot[q] : g;
-    const int idx = (int)(0xffffffffu - (unsigned)g);
-    if ((idx & 255) == tid) {                           // the owner writes hypothesis j and retires the candidate
-      const int c = idx >> 8;
-      float t = 0.f;
-#pragma unroll
-      for (int q = 0; q < NC; ++q) if (q == c) { t = tot[q]; key[q] = 0u; }
-      const int word = idx % V, parent = idx / V, r = b * K + j, pr = b * K + parent;
-      const bool pf = fin_s[parent] != 0;
-      const int f = (pf || word == eos) ? 1 : 0;
-      logp_out[r] = t;
-      fin_out[r] = f;
-      len_out[r] = len_s[parent] + (pf ? 0 : 1);
-      tok[r] = word;
-      parent_rows[r] = pr;
-      step_ids[r] = word;
-      parent_ids[r] = parent;
-      if (!f) ++alive;
-    }
-  }
-  if (alive) atomicAdd(alive_s, alive);
-  __syncthreads();
-  if (tid == 0 && alive_s[0]) atomicAdd(n_unfinished, alive_s[0]);
-}
-
-__global__ void beam_gather_tree_kernel(const int32_t* step_ids, const int32_t* parent_ids, const int32_t* beam_len, int32_t* out,
-                                        int nutt, int K, int T, int eos) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nutt * K) return;
-  const int b = i / K, k = i % K, R = nutt * K;
-  int ml = 0;
-  for (int j = 0; j < K; ++j) ml = max(ml, beam_len[b * K + j]);
-  ml = min(ml, T);
-  int32_t* o = out + (long)b * T * K + k;              // out[b][t][k]
-  for (int t = 0; t < T; ++t) o[(long)t * K] = eos;
-  if (ml <= 0) return;
-  int parent = parent_ids[(long)(ml - 1) * R + b * K + k];
-  o[(long)(ml - 1) * K] = step_ids[(long)(ml - 1) * R + b * K + k];
-  for (int level = ml - 2; level >= 0; --level) {
-    o[(long)level * K] = step_ids[(long)level * R + b * K + parent];
-    parent = parent_ids[(long)level * R + b * K + parent];
-  }
-  bool seen = false;
-  for (int t = 0; t < ml; ++t) {
-    if (seen) o[(long)t * K] = eos;
-    else if (o[(long)t * K] == eos) seen = true;
-  }
-}
-
 static inline float* hbuf(const avsr_attn_rnn& d, int p) { return d.state + (long)p * d.B * d.H; }
 static inline float* cbuf(const avsr_attn_rnn& d, int p) { return d.state + (long)(2 + p) * d.B * d.H; }
 static inline float* dgroll(const avsr_attn_rnn& d, int p) { return d.dstate + (long)p * d.B * 4 * d.H; }
@@ -497,7 +277,7 @@ static int attn_rnn_fwd_impl(const avsr_attn_rnn* dp, const avsr_beam_lm* lm, co
   if (d.mode == 2 && (!d.embedding || !d.wout_t || !d.logits || !d.xs || !d.labels || !d.fed || !d.seed)) return AVSR_ERR_ARG;
   if (d.mode == 3 && (!d.embedding || !d.wout_t || !d.logits || !d.tok || !d.n_unfinished || d.beam_width <= 0 || B % d.beam_width ||
                       !d.beam_logp || !d.beam_fin || !d.beam_len || !d.step_ids || !d.parent_ids || !d.parent_rows)) return AVSR_ERR_ARG;
-  if (d.mode == 3 && (d.beam_width * d.V > 1024 || d.beam_width > 64)) return AVSR_ERR_UNSUPPORTED;
+  if (d.mode == 3 && (!beam_step_fits(d.beam_width, d.V) || d.beam_width > 64)) return AVSR_ERR_UNSUPPORTED;
   const bool feed = (d.mode == 1 || d.mode == 3);      // inputs come from the embedding of the previous prediction
   const bool gru = d.cell == 1;
   if (gru && (!d.wt2 || !d.rh_seq)) return AVSR_ERR_ARG;
@@ -707,10 +487,18 @@ static int attn_rnn_fwd_impl(const avsr_attn_rnn* dp, const avsr_beam_lm* lm, co
         AVSR_CHECK_LAUNCH();
         continue;
       }
-      // beam search on the dense path: the output layer inside the beam step (beam_step_kernel<NCT>)
-      const int bs_nct = (beam_dense && d.beam_width <= 16 && d.V <= 64 && O % 256 == 0 && xsb % 4 == 0 &&
-                          (((uintptr_t)xa | (uintptr_t)d.wout_t) & 15) == 0) ? (d.V <= 32 ? 2 : 4) : 0;
-      if (!bs_nct) {
+      // beam search: the selection step (beam.h); on the dense path the output layer runs inside it where beam_step_nct allows
+      BeamStep bs{};
+      bool bs_inside = false;
+      if (d.mode == 3) {
+        const long pin = (long)(l & 1) * B, pout = (long)((l + 1) & 1) * B;       // halves of the ping-pong beam state
+        bs = BeamStep{d.logits + (long)l * d.V, (long)L * d.V, B / d.beam_width, d.beam_width, d.V, l, d.eos_id, d.length_penalty,
+                      d.beam_logp + pin, d.beam_fin + pin, d.beam_len + pin, d.beam_logp + pout, d.beam_fin + pout, d.beam_len + pout,
+                      d.tok, d.parent_rows, d.step_ids, d.parent_ids, d.n_unfinished, xa, xsb, O, d.wout_t, d.bout,
+                      ctc ? ctc->extra : lm ? lm->lm_logp : nullptr, ctc ? 1.f : lm ? lm->lm_weight : 0.f};
+        bs_inside = beam_dense && beam_step_nct(bs) != 0;
+      }
+      if (!bs_inside) {
         SL.ntask = 1;
         StepTask& tk = SL.task[0];
         tk = StepTask{};
@@ -725,17 +513,7 @@ static int attn_rnn_fwd_impl(const avsr_attn_rnn* dp, const avsr_beam_lm* lm, co
         hipLaunchKernelGGL(greedy_sample_kernel, dim3(1), dim3(256), 0, s, d.logits + (long)l * d.V, (long)L * d.V, d.V,
                            d.ids + l, (long)L, d.tok, d.steplen, d.n_unfinished, B, l, d.eos_id);
       } else if (d.mode == 3) {
-        const int K = d.beam_width, pin = l & 1, pout = (l + 1) & 1;
-#define BS_GO(NCT_, LM_)                                                                                                                  \
-  hipLaunchKernelGGL((beam_step_kernel<NCT_, LM_>), dim3(B / K), dim3(256), (K * d.V + 8 * K + 24 + 1024 * NCT_) * sizeof(float), s,        \
-                     d.logits + (long)l * d.V, (long)L * d.V, d.V, K, l, d.eos_id, d.length_penalty, d.beam_logp + (long)pin * B,           \
-                     d.beam_fin + (long)pin * B, d.beam_len + (long)pin * B, d.beam_logp + (long)pout * B, d.beam_fin + (long)pout * B,    \
-                     d.beam_len + (long)pout * B, d.tok, d.parent_rows, d.step_ids + (long)l * B, d.parent_ids + (long)l * B,              \
-                     d.n_unfinished + l, xa, xsb, O, d.wout_t, d.bout, ctc ? ctc->extra : lm ? lm->lm_logp : nullptr,                       \
-                     ctc ? 1.f : lm ? lm->lm_weight : 0.f)
-        if (lm || ctc) { if (bs_nct == 2) BS_GO(2, true); else if (bs_nct == 4) BS_GO(4, true); else BS_GO(0, true); }
-        else { if (bs_nct == 2) BS_GO(2, false); else if (bs_nct == 4) BS_GO(4, false); else BS_GO(0, false); }
-#undef BS_GO
+        if ((rc = beam_step_launch(bs, bs_inside, s))) return rc;
       } else {
         hipLaunchKernelGGL(sched_sample_kernel, dim3(B), dim3(128), sizeof(float) * d.V, s, d.logits + (long)l * d.V, (long)L * d.V, d.V, d.labels,
                            d.fed, d.xs, d.embedding, B, L, E, l, d.seed, d.sampling_prob, drop ? d.keep_in : 1.0f, cid4, E + A);
@@ -1016,76 +794,4 @@ extern "C" int avsr_attn_rnn_bwd(const avsr_attn_rnn* dp, void* stream) {
   }
   if (!gru && d.dc0 && avsr::dev_copy(d.dc0, dcbuf(d, 0), bh, s) != hipSuccess) return AVSR_ERR_HIP;
   return AVSR_OK;
-}
-
-extern "C" int avsr_beam_gather_tree(const int32_t* step_ids, const int32_t* parent_ids, const int32_t* beam_len, int32_t* out,
-                                     int32_t n_utt, int32_t beam_width, int32_t T, int32_t eos_id, void* stream) {
-  using namespace avsr;
-  if (!step_ids || !parent_ids || !beam_len || !out || n_utt <= 0 || beam_width <= 0 || T <= 0) return AVSR_ERR_ARG;
-  const int n = n_utt * beam_width;
-  hipLaunchKernelGGL(beam_gather_tree_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, step_ids, parent_ids, beam_len, out,
-                     n_utt, beam_width, T, eos_id);
-  AVSR_CHECK_LAUNCH();
-  return AVSR_OK;
-}
-
-extern "C" int avsr_beam_search_step_lm(float* logits, int32_t n_utt, int32_t beam_width, int32_t V, int32_t step, int32_t eos_id,
-                                        float length_penalty_weight, const float* logp_in, const int32_t* fin_in, const int32_t* len_in,
-                                        float* logp_out, int32_t* fin_out, int32_t* len_out, int32_t* tok, int32_t* parent_rows,
-                                        int32_t* step_ids, int32_t* parent_ids, int32_t* n_unfinished, const float* x, int64_t x_stride,
-                                        int32_t O, const float* wout_t, const float* bout, const float* lm_logp, float lm_weight,
-                                        void* stream) {
-  using namespace avsr;
-  if (!logits || !logp_in || !fin_in || !len_in || !logp_out || !fin_out || !len_out || !tok || !parent_rows || !step_ids || !parent_ids ||
-      !n_unfinished || n_utt <= 0 || beam_width <= 0 || V <= 0 || step < 0 || eos_id < 0 || eos_id >= V)
-    return AVSR_ERR_ARG;
-  if ((long)beam_width * V > 1024) return AVSR_ERR_UNSUPPORTED;      // the kernel keeps a thread's candidates in registers (4 x 256)
-  const int K = beam_width;
-  const long B = (long)n_utt * K;
-  hipStream_t s = (hipStream_t)stream;
-  // the same launches avsr_attn_rnn_fwd (mode 3) issues: logits given (NCT = 0), or the output layer inside the step (x != NULL; its conditions below)
-  int nct = 0;
-  if (x) {
-    if (!wout_t || !bout || O <= 0) return AVSR_ERR_ARG;
-    if (K > 16 || V > 64 || O % 256 != 0 || x_stride % 4 != 0 || (((uintptr_t)x | (uintptr_t)wout_t) & 15) != 0) return AVSR_ERR_UNSUPPORTED;
-    nct = V <= 32 ? 2 : 4;
-  }
-#define BS_GO(NCT_, LM_)                                                                                                                  \
-  hipLaunchKernelGGL((beam_step_kernel<NCT_, LM_>), dim3(n_utt), dim3(256), (K * V + 8 * K + 24 + 1024 * NCT_) * sizeof(float), s, logits, (long)V, V, K,  \
-                     step, eos_id, length_penalty_weight, logp_in, fin_in, len_in, logp_out, fin_out, len_out, tok, parent_rows,                     \
-                     step_ids + (long)step * B, parent_ids + (long)step * B, n_unfinished + step, x, (long)x_stride, O, wout_t, bout, lm_logp,       \
-                     lm_weight)
-  if (lm_logp) { if (nct == 2) BS_GO(2, true); else if (nct == 4) BS_GO(4, true); else BS_GO(0, true); }
-  else { if (nct == 2) BS_GO(2, false); else if (nct == 4) BS_GO(4, false); else BS_GO(0, false); }
-#undef BS_GO
-  AVSR_CHECK_LAUNCH();
-  return AVSR_OK;
-}
-
-extern "C" int avsr_beam_search_step_ctc(float* logits, int32_t n_utt, int32_t beam_width, int32_t V, int32_t step, int32_t eos_id,
-                                         float length_penalty_weight, const float* logp_in, const int32_t* fin_in, const int32_t* len_in,
-                                         float* logp_out, int32_t* fin_out, int32_t* len_out, int32_t* tok, int32_t* parent_rows,
-                                         int32_t* step_ids, int32_t* parent_ids, int32_t* n_unfinished, const float* x, int64_t x_stride,
-                                         int32_t O, const float* wout_t, const float* bout, const float* lm_logp, float lm_weight,
-                                         const float* ctc_term, float ctc_weight, float* extra, void* stream) {
-  if (ctc_term && ctc_weight != 0.f) {
-    if (!extra || !(ctc_weight > 0.f) || n_utt <= 0 || beam_width <= 0 || V <= 0) return AVSR_ERR_ARG;
-    const int rc = avsr::beam_ctc_combine_launch(ctc_term, ctc_weight, lm_weight != 0.f ? lm_logp : nullptr, lm_weight, extra,
-                                                 (long)n_utt * beam_width * V, (hipStream_t)stream);
-    if (rc) return rc;
-    lm_logp = extra;
-    lm_weight = 1.f;
-  }
-  return avsr_beam_search_step_lm(logits, n_utt, beam_width, V, step, eos_id, length_penalty_weight, logp_in, fin_in, len_in, logp_out, fin_out,
-                                  len_out, tok, parent_rows, step_ids, parent_ids, n_unfinished, x, x_stride, O, wout_t, bout, lm_logp, lm_weight,
-                                  stream);
-}
-
-extern "C" int avsr_beam_search_step(float* logits, int32_t n_utt, int32_t beam_width, int32_t V, int32_t step, int32_t eos_id,
-                                     float length_penalty_weight, const float* logp_in, const int32_t* fin_in, const int32_t* len_in,
-                                     float* logp_out, int32_t* fin_out, int32_t* len_out, int32_t* tok, int32_t* parent_rows,
-                                     int32_t* step_ids, int32_t* parent_ids, int32_t* n_unfinished, const float* x, int64_t x_stride,
-                                     int32_t O, const float* wout_t, const float* bout, void* stream) {
-  return avsr_beam_search_step_lm(logits, n_utt, beam_width, V, step, eos_id, length_penalty_weight, logp_in, fin_in, len_in, logp_out, fin_out,
-                                  len_out, tok, parent_rows, step_ids, parent_ids, n_unfinished, x, x_stride, O, wout_t, bout, nullptr, 0.f, stream);
 }

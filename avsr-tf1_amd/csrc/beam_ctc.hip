@@ -21,19 +21,12 @@
 //      term[r][v] = psi(g.v) - psi(g), 0 for every v where psi(g) = -inf, T_b = 0 or the row is finished; never NaN.
 //   The selection gets ONE pre-combined buffer extra[r][v] = weight * term + lm_weight * lm_logp (the second part when a language model
 //   is fused) and runs as beam_step_kernel<.., LM = true> with weight 1: its instantiations are the ones that run without CTC.
-#include <math.h>
-#include "common.h"
+#include "wave.h"
 #include "avsr_hip.h"
 #include "prof.h"
+#include "beam.h"
 
 namespace avsr {
-
-// a (+) b in the log domain; (-inf) (+) (-inf) = -inf, never NaN
-__device__ __forceinline__ float bc_lse2(float a, float b) {
-  const float m = fmaxf(a, b);
-  if (m == -INFINITY) return -INFINITY;
-  return m + logf(1.f + expf(-fabsf(a - b)));
-}
 
 // Inclusive scan, over the 64 lanes of a wave, of the affine maps N -> (N + A) (+) B of the lanes' frame chunks (earlier chunk first);
 // returns what enters the lane's chunk when -inf enters the first: the B of the lanes before it composed.
@@ -41,7 +34,7 @@ __device__ __forceinline__ float bc_scan_maps(float A, float B, int lane) {
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
     const float Ap = __shfl_up(A, o, 64), Bp = __shfl_up(B, o, 64);
-    if (lane >= o) { B = bc_lse2(Bp + A, B); A = Ap + A; }
+    if (lane >= o) { B = lse2(Bp + A, B); A = Ap + A; }
   }
   const float in = __shfl_up(B, 1, 64);
   return lane == 0 ? -INFINITY : in;
@@ -119,7 +112,7 @@ __global__ __launch_bounds__(256) void beam_ctc_step_kernel(const avsr_beam_ctc 
     const bool empty = plast < 0, same = c == plast;
     for (int t = tid; t < Tb; t += 256) {
       const float2 v = sin[t];
-      sPhi[t] = same ? v.y : bc_lse2(v.x, v.y);
+      sPhi[t] = same ? v.y : lse2(v.x, v.y);
       sYc[t] = yb[(long)t * C + c];
       sYb[t] = yb[(long)t * C + V];
     }
@@ -134,7 +127,7 @@ __global__ __launch_bounds__(256) void beam_ctc_step_kernel(const avsr_beam_ctc 
       const int t0 = tid * CH, t1 = min(Tb, t0 + CH);
       for (int t = t0; t < t1; ++t) {
         if (t == 0) { Am = -INFINITY; Bv = empty ? sYc[0] : -INFINITY; }
-        else { const float yc = sYc[t]; Bv = bc_lse2(Bv, sPhi[t - 1]) + yc; Am += yc; }
+        else { const float yc = sYc[t]; Bv = lse2(Bv, sPhi[t - 1]) + yc; Am += yc; }
         sRn[t] = Am; sRb[t] = Bv;
       }
       mM[tid] = bc_scan_maps(Am, Bv, tid);
@@ -150,7 +143,7 @@ __global__ __launch_bounds__(256) void beam_ctc_step_kernel(const avsr_beam_ctc 
     psi = mx == -INFINITY ? -INFINITY : mx + logf(sum);
     last = c;
     __syncthreads();                                                   // wave 0's maps are in LDS; sPhi and sYc are free
-    for (int t = tid; t < Tb; t += 256) sRn[t] = bc_lse2(sRb[t], mM[t / CH] + sRn[t]);
+    for (int t = tid; t < Tb; t += 256) sRn[t] = lse2(sRb[t], mM[t / CH] + sRn[t]);
     __syncthreads();
     // r'_b[t] = (r'_n[t-1] (+) r'_b[t-1]) + y[t][blank], r'_b[0] = -inf: the same, on the finished r'_n (A goes to sYc, B to sRb)
     if (tid < 64) {
@@ -158,19 +151,19 @@ __global__ __launch_bounds__(256) void beam_ctc_step_kernel(const avsr_beam_ctc 
       const int t0 = tid * CH, t1 = min(Tb, t0 + CH);
       for (int t = t0; t < t1; ++t) {
         if (t == 0) { Am = -INFINITY; Bv = -INFINITY; }
-        else { const float ybl = sYb[t]; Bv = bc_lse2(Bv, sRn[t - 1]) + ybl; Am += ybl; }
+        else { const float ybl = sYb[t]; Bv = lse2(Bv, sRn[t - 1]) + ybl; Am += ybl; }
         sYc[t] = Am; sRb[t] = Bv;
       }
       mS[tid] = bc_scan_maps(Am, Bv, tid);
     }
     __syncthreads();
-    for (int t = tid; t < Tb; t += 256) sRb[t] = bc_lse2(sRb[t], mS[t / CH] + sYc[t]);
+    for (int t = tid; t < Tb; t += 256) sRb[t] = lse2(sRb[t], mS[t / CH] + sYc[t]);
     __syncthreads();
   }
   for (int t = tid; t < Tb; t += 256) {
     const float rn = sRn[t], rb = sRb[t];
     sout[t] = make_float2(rn, rb);
-    sPhi[t] = bc_lse2(rn, rb);
+    sPhi[t] = lse2(rn, rb);
   }
   if (tid == 0) { A.psi[(long)pout * R + r] = psi; A.last[(long)pout * R + r] = last; }
   float* term = A.term + (long)r * V;

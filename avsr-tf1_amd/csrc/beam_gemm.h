@@ -2,6 +2,7 @@
 // while they are staged.  Shared by the decoder's beam-search steps (beam_gemm.hip) and the language-model step (beam_lm.hip).
 #pragma once
 #include "common.h"
+#include "avsr_hip.h"
 
 namespace avsr {
 
@@ -22,5 +23,12 @@ struct BGLaunch { int nprob, ntiles; BGProb p[BG_MAX_PROB]; };
 
 // launches beam_gemm_kernel<lstm> over G.ntiles workgroups
 int beam_gemm_launch(const BGLaunch& G, bool lstm, hipStream_t s);
+
+// The decoder's beam-search steps on the tiled kernel (mode 3 of avsr_attn_rnn_fwd).  g_beam_dense is avsr_attn_rnn_set_beam_kernel's
+// switch; the two launches return AVSR_ERR_UNSUPPORTED where the tiled kernel does not apply (the caller then runs step_kernel).
+extern int g_beam_dense;
+bool beam_dense_on();
+int beam_cell_launch(const avsr_attn_rnn& d, int l, hipStream_t s);
+int beam_attention_layer_launch(const avsr_attn_rnn& d, int l, hipStream_t s);
 
 }  // namespace avsr

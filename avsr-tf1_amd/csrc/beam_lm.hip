@@ -9,18 +9,12 @@
 // A layer is parallel over its 4 H gate columns (1 x 256 at 640 rows: 160 workgroups); folding the layers of a 16-row tile into one
 // workgroup would make each of the 40 tiles stream every weight by itself.
 // beam_lm_out_kernel then closes the step: Dense(V) on the top layer's h as 16 x 16 MFMA tiles and log_softmax per row -> lm_logp.
-#include "persist.h"
 #include "avsr_hip.h"
 #include "prof.h"
+#include "beam.h"
 #include "beam_gemm.h"
 
 namespace avsr {
-
-__device__ __forceinline__ float group16_max(float v) {
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
 
 // lm_logp[r, :] = log_softmax(h[r, :] . Wout + bout).  One 256-thread workgroup per 16 rows: wave w takes the 16-column tiles w, w + 4, ...
 // of v_mfma_f32_16x16x4_f32 over the whole H (lane (i16, g) holds inputs kk + 4 g .. + 3 of row / column i16: one 16-byte load per

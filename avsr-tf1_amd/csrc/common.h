@@ -35,6 +35,8 @@ __host__ __device__ __forceinline__ float uniform01(uint32_t seed, uint32_t stre
 }
 
 // ---- wave64 reductions ------------------------------------------------------------------
+// __shfl_xor butterflies, distances 32 .. 1 (wave_max: the same).  NOT the summation order of wave.h's wave64_sum (DPP rows, then the four
+// row results): swapping the two changes bits, so every user keeps the one it has.
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
@@ -45,10 +47,15 @@ __device__ __forceinline__ float wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
-// sum over aligned groups of 16 lanes
+// sum / maximum over aligned groups of 16 lanes
 __device__ __forceinline__ float group16_sum(float v) {
 #pragma unroll
   for (int o = 8; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ float group16_max(float v) {
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
 
@@ -139,7 +146,6 @@ static inline hipError_t dev_copy_2d(void* d, size_t dpitch, const void* src, si
                      (long)(spitch / 4), (long)(width / 4), (long)rows);
   return hipGetLastError();
 }
-
 
 // Several independent fills / copies in ONE launch (the set-up of a decoder block was six 4-5 us launches in a row on the step's critical
 // chain).  The operations of a batch must not depend on each other; 2-D forms take byte pitches like dev_copy_2d.

@@ -23,14 +23,14 @@
 // thread k sums the states of class k in that order; the blank states (every even state) are summed by a wave reduction plus a
 // fixed-order sum over the waves.  Two launches on the same inputs are bit-identical.
 // Rows t >= T_b, and every row of an utterance without a valid alignment, are stored as zeros by every launch.
-#include <math.h>
-#include "common.h"
+#include "wave.h"
 #include "avsr_hip.h"
 
 namespace avsr {
 
 #define S_(x) ((hipStream_t)(x))
 
+// (expf(a - m) + expf(b - m): rounds differently from wave.h's lse2 (1 + expf(-|a - b|)), so the loss keeps its own)
 __device__ __forceinline__ float ctc_lse2(float a, float b) {
   const float m = fmaxf(a, b);
   if (m == -INFINITY) return -INFINITY;
@@ -40,41 +40,6 @@ __device__ __forceinline__ float ctc_lse3(float a, float b, float c) {
   const float m = fmaxf(fmaxf(a, b), c);
   if (m == -INFINITY) return -INFINITY;
   return m + logf(expf(a - m) + expf(b - m) + expf(c - m));
-}
-// Per-step barrier: LDS ordering and arrival only.  __syncthreads() carries a workgroup-scope fence that the compiler lowers to
-// s_waitcnt vmcnt(0): the rows prefetched for the next step and the alpha stores of this one would be waited for on every step
-// (measured: 1.37 ms for the launch at B = 64, T = 500 with __syncthreads() there).  The sweeps' cross-thread traffic is LDS only; the one
-// global hand-over -- row t of dz is read as log-probabilities before the step's barrier and overwritten with the gradient after it
-// -- is safe because a thread has consumed (so received) its loads before it arrives.
-__device__ __forceinline__ void ctc_step_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// wave reductions by DPP row rotations (one VALU issue each; __shfl_xor is an LDS round trip per step), the four rows combined in a
-// fixed order: a uniform, deterministic result
-template <int CTRL>
-__device__ __forceinline__ float ctc_dpp(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float ctc_lane(float v, int l) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
-}
-__device__ __forceinline__ float ctc_wave_max(float v) {
-  v = fmaxf(v, ctc_dpp<0x128>(v));      // row_ror:8, 4, 2, 1
-  v = fmaxf(v, ctc_dpp<0x124>(v));
-  v = fmaxf(v, ctc_dpp<0x122>(v));
-  v = fmaxf(v, ctc_dpp<0x121>(v));
-  return fmaxf(fmaxf(ctc_lane(v, 0), ctc_lane(v, 16)), fmaxf(ctc_lane(v, 32), ctc_lane(v, 48)));
-}
-__device__ __forceinline__ float ctc_wave_sum(float v) {
-  v += ctc_dpp<0x128>(v);
-  v += ctc_dpp<0x124>(v);
-  v += ctc_dpp<0x122>(v);
-  v += ctc_dpp<0x121>(v);
-  return (ctc_lane(v, 0) + ctc_lane(v, 16)) + (ctc_lane(v, 32) + ctc_lane(v, 48));
-}
-__device__ __forceinline__ float group16_max(float v) {
-#pragma unroll
-  for (int o = 8; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
 }
 
 // rows [r0, r1) x columns [0, C) of utterance b's block of dz = 0
@@ -183,10 +148,10 @@ __global__ __launch_bounds__(1024) void ctc_loss_kernel(const avsr_ctc_args A) {
       const bool more = t + 1 < Tb;
       if (more) { lpB = lp[(long)(t + 1) * ld + blank]; lpL = lp[(long)(t + 1) * ld + li]; }     // next row: off the chain
       const int buf = t & 1;
-      const float mx = ctc_wave_max(fmaxf(e, o));
+      const float mx = wave64_max(fmaxf(e, o));
       exO[buf * XS + i + 1] = o;
       if (lane == 0) red[buf * 16 + wv] = mx;
-      ctc_step_barrier();
+      lds_barrier();
       float m = red[buf * 16];
       for (int w = 1; w < nw; ++w) m = fmaxf(m, red[buf * 16 + w]);
       if (m == -INFINITY) m = 0.f;
@@ -257,9 +222,9 @@ __global__ __launch_bounds__(1024) void ctc_loss_kernel(const avsr_ctc_args A) {
       exE[buf * XS + i + 1] = bE;
       exO[buf * XS + i + 1] = bO;
       gam[buf * NT + i] = gO;
-      const float sB = ctc_wave_sum(gE), sA = ctc_wave_sum(gE + gO);
+      const float sB = wave64_sum(gE), sA = wave64_sum(gE + gO);
       if (lane == 0) { red[buf * 16 + wv] = sB; red2[buf * 16 + wv] = sA; }
-      ctc_step_barrier();
+      lds_barrier();
       if (i < C) {
         float G = 0.f, tot = 0.f;
         for (int w = 0; w < nw; ++w) tot += red2[buf * 16 + w];

@@ -21,55 +21,14 @@
 //      strikes its candidate and rescans its own.  Stops at p = -inf, so the beam may hold fewer than W.  The beam's slot order is the selection order: it is sorted.
 //   5. the new beam into the other half: states recomputed from the old half (a few flops), label rows copied word-wise, the appended
 //      symbol composed into its word; the trace rows; row t + 1 staged with its per-wave (max, sum) for the log-softmax.
-// The barrier is ctc.hip's: s_waitcnt lgkmcnt(0) + s_barrier, so the prefetch and the trace stores are not waited for at every phase.
-#include <math.h>
-#include "common.h"
+// The barrier is wave.h's lds_barrier: s_waitcnt lgkmcnt(0) + s_barrier, so the prefetch and the trace stores are not waited for at every phase.
+#include "wave.h"
 #include "avsr_hip.h"
 #include "prof.h"
 
 namespace avsr {
 
 #define CP_LDS_MAX_BYTES (160 * 1024)
-
-// a (+) b in the log domain; (-inf) (+) (-inf) = -inf, never NaN
-__device__ __forceinline__ float cp_lse2(float a, float b) {
-  const float m = fmaxf(a, b);
-  if (m == -INFINITY) return -INFINITY;
-  return m + logf(1.f + expf(-fabsf(a - b)));
-}
-// all cross-thread traffic of the frame loop is LDS (see ctc.hip's ctc_step_barrier)
-__device__ __forceinline__ void cp_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// wave reductions by DPP row rotations plus four readlanes (ctc.hip's ctc_wave_max): a handful of VALU issues and a UNIFORM result,
-// where a __shfl_xor butterfly is an LDS round trip per step -- the selection runs up to W of these pairs per frame on the chain
-template <int CTRL>
-__device__ __forceinline__ int cp_dpp(int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false); }
-__device__ __forceinline__ float cp_wave_max(float v) {
-  v = fmaxf(v, __builtin_bit_cast(float, cp_dpp<0x128>(__builtin_bit_cast(int, v))));      // row_ror:8, 4, 2, 1
-  v = fmaxf(v, __builtin_bit_cast(float, cp_dpp<0x124>(__builtin_bit_cast(int, v))));
-  v = fmaxf(v, __builtin_bit_cast(float, cp_dpp<0x122>(__builtin_bit_cast(int, v))));
-  v = fmaxf(v, __builtin_bit_cast(float, cp_dpp<0x121>(__builtin_bit_cast(int, v))));
-  const int i = __builtin_bit_cast(int, v);
-  return fmaxf(fmaxf(__builtin_bit_cast(float, __builtin_amdgcn_readlane(i, 0)), __builtin_bit_cast(float, __builtin_amdgcn_readlane(i, 16))),
-               fmaxf(__builtin_bit_cast(float, __builtin_amdgcn_readlane(i, 32)), __builtin_bit_cast(float, __builtin_amdgcn_readlane(i, 48))));
-}
-__device__ __forceinline__ float cp_wave_sum(float v) {                                   // (a fixed order: deterministic)
-  v += __builtin_bit_cast(float, cp_dpp<0x128>(__builtin_bit_cast(int, v)));
-  v += __builtin_bit_cast(float, cp_dpp<0x124>(__builtin_bit_cast(int, v)));
-  v += __builtin_bit_cast(float, cp_dpp<0x122>(__builtin_bit_cast(int, v)));
-  v += __builtin_bit_cast(float, cp_dpp<0x121>(__builtin_bit_cast(int, v)));
-  const int i = __builtin_bit_cast(int, v);
-  return (__builtin_bit_cast(float, __builtin_amdgcn_readlane(i, 0)) + __builtin_bit_cast(float, __builtin_amdgcn_readlane(i, 16))) +
-         (__builtin_bit_cast(float, __builtin_amdgcn_readlane(i, 32)) + __builtin_bit_cast(float, __builtin_amdgcn_readlane(i, 48)));
-}
-__device__ __forceinline__ int cp_wave_min(int v) {
-  v = min(v, cp_dpp<0x128>(v));
-  v = min(v, cp_dpp<0x124>(v));
-  v = min(v, cp_dpp<0x122>(v));
-  v = min(v, cp_dpp<0x121>(v));
-  return min(min(__builtin_amdgcn_readlane(v, 0), __builtin_amdgcn_readlane(v, 16)),
-             min(__builtin_amdgcn_readlane(v, 32), __builtin_amdgcn_readlane(v, 48)));
-}
 
 static inline size_t cp_lds_words(int V, int W, int LM) {
   const size_t C = (size_t)V + 1, LW = ((size_t)LM + 3) / 4;
@@ -105,10 +64,10 @@ __global__ __launch_bounds__(256) void ctc_prefix_kernel(const avsr_ctc_prefix_a
   auto stage = [&](int buf, float z0, float z1) {
     float mx = own0 ? z0 : -INFINITY;
     if (own1) mx = fmaxf(mx, z1);
-    mx = cp_wave_max(mx);                                           // (called by whole waves only)
+    mx = wave64_max(mx);                                           // (called by whole waves only)
     float s = own0 ? expf(z0 - mx) : 0.f;
     if (own1) s += expf(z1 - mx);
-    s = cp_wave_sum(s);
+    s = wave64_sum(s);
     if (own0) sZ[buf * C + tid] = z0;
     if (own1) sZ[buf * C + tid + 256] = z1;
     if (lane == 0) { sRed[buf * 8 + wave * 2] = mx; sRed[buf * 8 + wave * 2 + 1] = s; }
@@ -119,7 +78,7 @@ __global__ __launch_bounds__(256) void ctc_prefix_kernel(const avsr_ctc_prefix_a
     sCnt[0] = 1;
   }
   if (Tb > 0) stage(0, own0 ? zb[tid] : 0.f, own1 ? zb[tid + 256] : 0.f);
-  cp_barrier();
+  lds_barrier();
 
   for (int t = 0; t < Tb; ++t) {
     const int cur = t & 1, nxt = cur ^ 1, n = sCnt[cur];
@@ -165,7 +124,7 @@ __global__ __launch_bounds__(256) void ctc_prefix_kernel(const avsr_ctc_prefix_a
       }
       if (!diff) mrg[k] = j;
     }
-    cp_barrier();
+    lds_barrier();
 
     // p_b and p_nb of the stay of slot k, its partner's extension merged in
     auto stay = [&](int k, float& sb, float& snb) {
@@ -175,7 +134,7 @@ __global__ __launch_bounds__(256) void ctc_prefix_kernel(const avsr_ctc_prefix_a
       if (lk >= 0) {
         const float yl = zc[lk] - lse;
         snb = pnb[k] + yl;
-        if (j >= 0) snb = cp_lse2(snb, (last[j] == lk ? pb[j] : pp[j]) + yl);
+        if (j >= 0) snb = lse2(snb, (last[j] == lk ? pb[j] : pp[j]) + yl);
       }
     };
     auto extend = [&](int k, int c) { return len[k] < LM ? (c == last[k] ? pb[k] : pp[k]) + (zc[c] - lse) : -INFINITY; };
@@ -184,14 +143,14 @@ __global__ __launch_bounds__(256) void ctc_prefix_kernel(const avsr_ctc_prefix_a
     for (int idx = tid; idx < n * C; idx += 256) {
       const int k = idx / C, c = idx - k * C;
       float v;
-      if (c == V) { float sb, snb; stay(k, sb, snb); v = cp_lse2(sb, snb); }
+      if (c == V) { float sb, snb; stay(k, sb, snb); v = lse2(sb, snb); }
       else v = extend(k, c);
       sCand[idx] = v;
     }
-    cp_barrier();
+    lds_barrier();
     // ---- 3. an extension that was merged into a stay is no candidate of its own ----
     if (tid < n && mrg[tid] >= 0) sCand[mrg[tid] * C + last[tid]] = -INFINITY;
-    cp_barrier();
+    lds_barrier();
 
     // ---- 4. selection, wave 0 ----
     if (wave == 0) {
@@ -201,9 +160,9 @@ __global__ __launch_bounds__(256) void ctc_prefix_kernel(const avsr_ctc_prefix_a
       for (int i = lane; i < NC; i += 64) { const float v = sCand[i]; if (v > bv) { bv = v; bi = i; } }
       int ns = 0;
       for (int r = 0; r < W; ++r) {
-        const float v = cp_wave_max(bv);                             // (all 64 lanes are active here: the loop's exits are uniform)
+        const float v = wave64_max(bv);                             // (all 64 lanes are active here: the loop's exits are uniform)
         if (v == -INFINITY) break;
-        const int i = cp_wave_min(bv == v ? bi : 0x7fffffff);        // the lowest index among the lanes that hold the maximum
+        const int i = wave64_min_i(bv == v ? bi : 0x7fffffff);        // the lowest index among the lanes that hold the maximum
         if (lane == 0) sSel[r] = i;
         ns = r + 1;
         if (bi == i) {
@@ -214,7 +173,7 @@ __global__ __launch_bounds__(256) void ctc_prefix_kernel(const avsr_ctc_prefix_a
       }
       if (lane == 0) sCnt[2] = ns;
     }
-    cp_barrier();
+    lds_barrier();
 
     // ---- 5. the new beam, the trace, the next row ----
     const int ns = sCnt[2];
@@ -230,7 +189,7 @@ __global__ __launch_bounds__(256) void ctc_prefix_kernel(const avsr_ctc_prefix_a
         if (c == V) { stay(k, nb_, nnb_); nl = len[k]; nlast = last[k]; nh = hash[k]; nhp = hpar[k]; }
         else { nnb_ = extend(k, c); nl = len[k] + 1; nlast = c; nh = hash[k] * 0x9E3779B1u + (uint32_t)(c + 1); nhp = hash[k]; }
         const int o = nxt * W + r;
-        sPb[o] = nb_; sPnb[o] = nnb_; sP[o] = cp_lse2(nb_, nnb_); sLen[o] = nl; sLast[o] = nlast; sHash[o] = nh; sHpar[o] = nhp;
+        sPb[o] = nb_; sPnb[o] = nnb_; sP[o] = lse2(nb_, nnb_); sLen[o] = nl; sLast[o] = nlast; sHash[o] = nh; sHpar[o] = nhp;
         sM[o] = -1;
       }
       if (A.trace_parent) {
@@ -250,7 +209,7 @@ __global__ __launch_bounds__(256) void ctc_prefix_kernel(const avsr_ctc_prefix_a
     }
     if (tid == 0) sCnt[nxt] = ns;
     if (more) stage(nxt, zn0, zn1);
-    cp_barrier();
+    lds_barrier();
   }
 
   // ---- the final beam (sorted: the slot order is the selection order) ----

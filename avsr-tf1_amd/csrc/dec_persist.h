@@ -5,6 +5,7 @@
 #include "avsr_hip.h"
 #include "prof.h"
 #include "persist.h"
+#include "wave.h"         // dpp_f, row16_*, wave64_*, rdlane_f
 
 #define DP_NW 32          // workgroups per row group (= CUs of one XCD)
 #define DP_R 8            // rows per group
@@ -57,41 +58,16 @@ __device__ __forceinline__ void stb4(__amdgpu_buffer_rsrc_t r, int byte_off, f32
   typedef unsigned int u32x4_ __attribute__((ext_vector_type(4)));
   __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_, v), r, byte_off, 0, 0);
 }
-// DPP reductions: __shfl_xor lowers to ds_bpermute (an LDS round trip per step); inside a row of 16 lanes the data-parallel
-// primitives rotate for one VALU issue.  row16_*: every lane of the row gets the row's result.
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float row16_sum(float v) {
-  v += dpp_f<0x128>(v);      // row_ror:8
-  v += dpp_f<0x124>(v);      // row_ror:4
-  v += dpp_f<0x122>(v);      // row_ror:2
-  v += dpp_f<0x121>(v);      // row_ror:1
-  return v;
-}
-__device__ __forceinline__ float row16_max(float v) {
-  v = fmaxf(v, dpp_f<0x128>(v));
-  v = fmaxf(v, dpp_f<0x124>(v));
-  v = fmaxf(v, dpp_f<0x122>(v));
-  v = fmaxf(v, dpp_f<0x121>(v));
-  return v;
-}
-__device__ __forceinline__ float rdlane_f(float v, int l) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l)); }
-// whole-wave results (uniform): the four row results combined in a fixed order
-__device__ __forceinline__ float wave64_sum(float v) {
-  v = row16_sum(v);
-  return (rdlane_f(v, 0) + rdlane_f(v, 16)) + (rdlane_f(v, 32) + rdlane_f(v, 48));
-}
-__device__ __forceinline__ float wave64_max(float v) {
-  v = row16_max(v);
-  return fmaxf(fmaxf(rdlane_f(v, 0), rdlane_f(v, 16)), fmaxf(rdlane_f(v, 32), rdlane_f(v, 48)));
-}
 __device__ __forceinline__ float dot4(const f32x4 a, const f32x4 b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2] + a[3] * b[3]; }
-
 
 // Fills L for the descriptor; AVSR_ERR_UNSUPPORTED when the fused kernels do not cover it (dec_persist.hip).
 int dp_plan(const avsr_attn_rnn& d, DPLaunch& L, int* variant, size_t* lds_bytes);
 extern int g_dec_fused;
 
 }  // namespace avsr
+
+// the fused launches the per-step scheduler (attn_rnn.hip) tries first (AVSR_ERR_UNSUPPORTED: run the per-step path), their workspace regions
+int avsr_dec_persist_fwd(const avsr_attn_rnn* d, int32_t l_begin, int32_t l_end, void* stream);   // dec_persist.hip
+int avsr_dec_persist_bwd(const avsr_attn_rnn* d, void* stream);                                      // dec_persist_bwd.hip
+int64_t avsr_dec_persist_fwd_ws_floats(int32_t B, int32_t n_mech, int32_t Dmax);                     // dec_persist.hip
+int64_t avsr_dec_persist_bwd_ws_floats(int32_t B, int32_t n_mech);                                   // dec_persist_bwd.hip

@@ -875,8 +875,6 @@ static bool dp_fwd_enabled() { return g_dec_fused != 0 && g_dec_fused != 3 && g_
 
 }  // namespace avsr
 
-int64_t avsr_dec_persist_bwd_ws_floats(int32_t B, int32_t n_mech);
-
 // forward region of the fused workspace (the backward kernel's partials follow it)
 int64_t avsr_dec_persist_fwd_ws_floats(int32_t B, int32_t n_mech, int32_t Dmax) {
   const int64_t groups = (B + DP_R - 1) / DP_R + 16;

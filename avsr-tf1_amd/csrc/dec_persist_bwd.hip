@@ -598,8 +598,6 @@ static const void* db_kernel(int variant) {
 
 }  // namespace avsr
 
-int64_t avsr_dec_persist_fwd_ws_floats(int32_t B, int32_t n_mech, int32_t Dmax);
-
 // floats the backward kernel needs behind the forward region of the fused workspace
 int64_t avsr_dec_persist_bwd_ws_floats(int32_t B, int32_t n_mech) {
   const int64_t rows = ((B + 15) / 16) * 16;       // whole groups of 8 or 16 rows

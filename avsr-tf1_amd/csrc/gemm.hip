@@ -18,6 +18,7 @@
 // one barrier per K-tile.  Split-K (grid.z) with a deterministic second-pass reduction covers the
 // tall-skinny dW GEMMs (K = B*T rows, tiny M x N).
 #include "common.h"
+#include "wave.h"
 #include "avsr_hip.h"
 #include "prof.h"
 
@@ -201,7 +202,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& g, const int bx, const
     store_tile<BKC>(lds[buf ^ 1][1], rb_next);
     if (do_cs) csum += rb_next[0] + rb_next[1];
     // LDS-only barrier: __syncthreads() also drains vmcnt, i.e. it would wait for the tiles still in flight
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    lds_barrier();
   };
   for (int k0 = kbeg; k0 < kend; k0 += 2 * BK) {
     ktile(k0, 0, ra[1], rb[1], ra[0], rb[0]);

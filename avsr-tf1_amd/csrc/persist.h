@@ -1,6 +1,7 @@
 // Device helpers shared by the persistent RNN kernels (rnn_persist.hip forward, rnn_persist_bwd.hip backward).
 #pragma once
 #include "common.h"
+#include "wave.h"          // lds_barrier, p_sigmoid / p_tanh
 
 #define P_HDR 256          // sync words reserved ahead of the counters: [0] sticky error flag, [16..] debug timing
 
@@ -33,8 +34,6 @@ __device__ __forceinline__ bool wait_ge(const int* ctr, int target, int* err) {
   return false;
 }
 
-__device__ __forceinline__ float p_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float p_tanh(float x) { return 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * x)) - 1.0f; }
 // DropoutWrapper mask scale.  The seed VALUE is read once per kernel: a load inside the step loop would put an
 // s_waitcnt vmcnt(0) -- and with it every operand prefetched for the next step -- on the critical path.
 __device__ __forceinline__ float p_drop(bool on, uint32_t seedv, uint32_t stream, uint32_t idx, float keep) {
@@ -48,13 +47,6 @@ __device__ __forceinline__ f32x4 ldx_sc1(__amdgpu_buffer_rsrc_t r, int elem_off)
   const u32x4_ v = __builtin_amdgcn_raw_buffer_load_b128(r, elem_off * 4, 0, 16);                      // aux 16 = sc1
   return __builtin_bit_cast(f32x4, v);
 }
-
-
-// Workgroup barrier that does NOT drain the vector-memory queue.  __syncthreads() carries a workgroup-scope fence, which
-// the compiler lowers to s_waitcnt vmcnt(0) before s_barrier: every operand prefetched for the NEXT step would be waited
-// for on the critical path of THIS step.  The persistent kernels only need LDS ordering (and plain arrival) at their
-// in-step barriers; the publish barrier drains stores explicitly.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // 16-byte write-through store (one fabric write; four scalar sc1 stores cost ~6x per byte)
 __device__ __forceinline__ void stx_sc1(__amdgpu_buffer_rsrc_t r, int elem_off, f32x4 v) {

@@ -159,10 +159,6 @@ __device__ __forceinline__ void mm16_partial(const StepTask& tk, int row0, int c
   for (int r = 0; r < RM; ++r) out[r] = (acc[r][0] + acc[r][1]) + (acc[r][2] + acc[r][3]);
 }
 
-// fast activations: v_exp_f32 / v_rcp_f32 based (|err| ~1e-7 absolute, far inside the 1e-4 parity budget)
-__device__ __forceinline__ float fsigmoid(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
-__device__ __forceinline__ float ftanh(float x) { return 2.0f * __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * x)) - 1.0f; }
-
 // inverted-dropout factor of element idx: 1/keep if kept, 0 if dropped, 1 if dropout is off
 __device__ __forceinline__ float drop_scale(const int32_t* seed, uint32_t stream, uint32_t idx, float keep) {
   if (!seed || keep >= 1.0f) return 1.0f;
@@ -170,8 +166,8 @@ __device__ __forceinline__ float drop_scale(const int32_t* seed, uint32_t stream
 }
 
 __device__ __forceinline__ float apply_act(float v, int act) {
-  if ((act & 3) == 1) return ftanh(v);
-  if ((act & 3) == 2) return fsigmoid(v);
+  if ((act & 3) == 1) return p_tanh(v);
+  if ((act & 3) == 2) return p_sigmoid(v);
   return v;
 }
 
@@ -306,7 +302,7 @@ __global__ __launch_bounds__(TN * KP * 64) void step_kernel(const StepLaunch L) 
       if (tk.bias) { zr += tk.bias[2 * u]; zu += tk.bias[2 * u + 1]; }
       float* gp = tk.p0 + (bt * H + u) * 2;
       if (tk.s2) { zr += gp[0]; zu += gp[1]; }
-      const float rr = fsigmoid(zr), uu = fsigmoid(zu);
+      const float rr = p_sigmoid(zr), uu = p_sigmoid(zu);
       gp[0] = rr; gp[1] = uu;
       const float rh = rr * tk.p4[(long)(tk.gather2 ? tk.gather2[bb] : bb) * H + u];
       tk.p1[(long)bb * H + u] = rh;
@@ -335,7 +331,7 @@ __global__ __launch_bounds__(TN * KP * 64) void step_kernel(const StepLaunch L) 
       if (ok) {
         if (tk.bias) z += tk.bias[nn];
         if (tk.s2) z += tk.p0[bt * H + nn];
-        const float cand = ftanh(z), uu = tk.p1[(bt * H + nn) * 2 + 1];
+        const float cand = p_tanh(z), uu = tk.p1[(bt * H + nn) * 2 + 1];
         const float h = uu * hprev + (1.f - uu) * cand;
         tk.p0[bt * H + nn] = cand;
         const uint32_t oidx = (uint32_t)(bt * H + nn);
@@ -444,7 +440,7 @@ __global__ __launch_bounds__(TN * KP * 64) void step_kernel(const StepLaunch L) 
       if (tk.p10) tk.p10[bh] = dout;          // ResidualWrapper: the same gradient also reaches the lower layer's output
       const f32x4 g = pre4a;
       const float c = pre2, cprev = pre3;
-      const float tc = ftanh(c);
+      const float tc = p_tanh(c);
       float dc = dh * g[3] * (1.f - tc * tc) + pre0;
       if (!(fabsf(c) < 1.0f)) dc = 0.f;      // cell_clip=1.0: no gradient through a clipped cell
       dg[3] = dh * tc * g[3] * (1.f - g[3]);
@@ -478,13 +474,13 @@ __global__ __launch_bounds__(TN * KP * 64) void step_kernel(const StepLaunch L) 
         z[gi] += zz;
       }
       f32x4 g;
-      g[0] = fsigmoid(z[0]);
-      g[1] = ftanh(z[1]);
-      g[2] = fsigmoid(z[2] + 1.0f);          // forget_bias = 1.0
-      g[3] = fsigmoid(z[3]);
+      g[0] = p_sigmoid(z[0]);
+      g[1] = p_tanh(z[1]);
+      g[2] = p_sigmoid(z[2] + 1.0f);          // forget_bias = 1.0
+      g[3] = p_sigmoid(z[3]);
       float c = g[2] * cprev + g[0] * g[1];
       c = fminf(1.0f, fmaxf(-1.0f, c));      // cell_clip = 1.0 (cells.py:16)
-      const float h = g[3] * ftanh(c);
+      const float h = g[3] * p_tanh(c);
       st4(tk.p0 + (bt * H + n) * 4, g);
       tk.p1[bt * H + n] = c;
       // DropoutWrapper: emitted output and recurrent h carry independent masks; c is never dropped

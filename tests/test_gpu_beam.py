@@ -269,7 +269,7 @@ def test_beam_width_10_at_benchmark_widths_and_lengths(case, over):
 @pytest.mark.parametrize("K", [10, 16])
 @pytest.mark.parametrize("unit", ["viseme", "character", "phoneme"])
 def test_output_layer_inside_the_beam_step(unit, K):
-    """At 256 units the dense beam path runs the decoder's Dense(vocab) inside beam_step_kernel<NCT> (csrc/attn_rnn.hip: two 16-column
+    """At 256 units the dense beam path runs the decoder's Dense(vocab) inside beam_step_kernel<NCT> (csrc/beam.hip: two 16-column
     MFMA tiles for V <= 32, four for V <= 64; O = 512 attention outputs split over the four waves).  Oracle parity step by step, and
     the logits it leaves behind against those of the separate projection launch (setting 2: general step kernels), to rounding."""
     from avsr_tf1_amd import ops
@@ -372,3 +372,68 @@ def test_hip_beam_step_replays_the_reference_trace(output_layer_inside):
     for u in range(U):
         best = [names[int(i)] for i in out[u, :, 0].cpu()]
         assert "".join(n for n in best if n != "EOS") == "and the next day" and best[16:] == ["EOS"] * 3
+
+
+@pytest.mark.parametrize("output_layer_inside", [False, True])
+@pytest.mark.parametrize("K,V", [(3, 15), (10, 31)])
+def test_the_three_step_entries_are_one_launch(K, V, output_layer_inside):
+    """avsr_beam_search_step, avsr_beam_search_step_lm without a term and avsr_beam_search_step_ctc without a term (ctc_term None, and
+    ctc_term given with weight 0) fill the same description and go through the one launch site of beam_step_kernel (csrc/beam.hip:
+    beam_step_launch, which avsr_attn_rnn_fwd mode 3 calls too): every buffer the step writes is bit-identical across the four calls,
+    on given logits and with the output layer inside the step (O = 256), at step 0 and step 1.  The input state has one finished beam
+    per utterance (its continuations are EOS only; its accumulated log-probability is the best, so it is selected) and one beam at -inf
+    (all its candidates tie at -inf); the logits are multiples of 0.5, so live candidates tie too."""
+    from avsr_tf1_amd import ops
+    dev = torch.device("cuda:0")
+    U, O, eos, w = 2, 256, V - 2, 0.6
+    R = U * K
+    rng = np.random.default_rng(1000 * K + V)
+    dv = lambda a, dt: torch.as_tensor(np.ascontiguousarray(a), dtype=dt).to(dev)
+    bits = lambda t: t.view(torch.int32) if t.dtype == torch.float32 else t
+    lg = np.round(rng.normal(0.0, 2.0, (R, V)) * 2.0) / 2.0
+    logp = -1.0 - rng.random((U, K)) * 2.0
+    fin, length = np.zeros((U, K), np.int32), rng.integers(1, 6, (U, K)).astype(np.int32)
+    logp[:, 1], fin[:, 1] = -0.1, 1                       # the finished beam, best of its utterance
+    logp[:, K - 1] = -np.inf
+    x = rng.integers(-2, 3, (R, O)).astype(np.float32)    # small integers: the inside form's logits are exact sums
+    wout_t = rng.integers(-1, 2, (V, O)).astype(np.float32) * 0.5
+    bout = np.round(rng.normal(0.0, 1.0, V) * 2.0) / 2.0
+    term = dv(rng.normal(0.0, 1.0, (R, V)), torch.float32)
+    state = (dv(logp.reshape(R), torch.float32), dv(fin.reshape(R), torch.int32), dv(length.reshape(R), torch.int32))
+    inside = dict(x=dv(x, torch.float32), x_stride=O, O=O, wout_t=dv(wout_t, torch.float32), bout=dv(bout, torch.float32)) \
+        if output_layer_inside else {}
+
+    def run(step, entry):
+        i32 = dict(dtype=torch.int32, device=dev)
+        logits = torch.full((R, V), float("nan"), device=dev) if output_layer_inside else dv(lg, torch.float32)
+        out = dict(logits=logits, logp=torch.full((R,), 7.0, device=dev), fin=torch.full((R,), -7, **i32), len=torch.full((R,), -7, **i32),
+                   tok=torch.full((R,), -7, **i32), prow=torch.full((R,), -7, **i32), sid=torch.full((2, R), -7, **i32),
+                   pid=torch.full((2, R), -7, **i32), nun=torch.zeros(2, **i32))
+        if step == 1:
+            out["nun"][0] = 3                              # the previous step left unfinished beams: the search goes on
+        args = (logits, U, K, V, step, eos, w) + state + (out["logp"], out["fin"], out["len"], out["tok"], out["prow"], out["sid"],
+                                                          out["pid"], out["nun"])
+        if entry == "step":
+            ops.beam_search_step(*args, **inside)
+        elif entry == "lm":
+            ops.beam_search_step_lm(*args, None, 0.0, **inside)
+        elif entry == "ctc":
+            ops.beam_search_step_ctc(*args, None, 0.0, None, 0.0, None, **inside)
+        else:
+            ops.beam_search_step_ctc(*args, None, 0.0, term, 0.0, torch.zeros(R, V, device=dev), **inside)
+        torch.cuda.synchronize()
+        return out
+
+    for step in (0, 1):
+        ref = run(step, "step")
+        # the step ran and took the paths the state was built for
+        assert not (ref["tok"] == -7).any() and not (ref["sid"][step] == -7).any() and (ref["sid"][1 - step] == -7).all()
+        assert torch.isfinite(ref["logits"]).all() and 0 < int(ref["nun"][step]) < R
+        took_finished = (ref["prow"].view(U, K) % K == 1) & (ref["tok"].view(U, K) == eos) & (ref["fin"].view(U, K) == 1)
+        assert took_finished.any(dim=1).all()
+        if output_layer_inside:
+            assert torch.equal(ref["logits"].cpu(), torch.as_tensor(x @ wout_t.T + bout[None], dtype=torch.float32))
+        for entry in ("lm", "ctc", "ctc_weight_0"):
+            got = run(step, entry)
+            for name in ref:
+                assert torch.equal(bits(got[name]), bits(ref[name])), (step, entry, name)
