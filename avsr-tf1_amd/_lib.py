@@ -218,6 +218,8 @@ _SIGS = {
     "avsr_ctc_best_path": [_vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp],
     "avsr_ctc_prefix_search_supported": [_i32, _i32, _i32],
     "avsr_ctc_prefix_search": [C.POINTER(CtcPrefixArgs), _vp],
+    "avsr_seq_logprob": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp],
+    "avsr_rescore_select": [_vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp],
     "avsr_batchnorm_apply": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp],
     "avsr_attn_rnn_bwd": [C.POINTER(AttnRnn), _vp],
     "avsr_beam_gather_tree": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],

@@ -32,6 +32,9 @@ beam search then adds ctc_decode_weight * (CTC prefix score of the continuation 
 (joint CTC / attention decoding, csrc/beam_ctc.hip); it works together with `lm_checkpoint`.
 `decoding_algorithm='ctc_prefix_beam_search'` (a `use_ctc` model; not in the reference) makes `evaluate` take its predictions from a CTC
 prefix beam search of width `beam_width` on that head alone -- no decoder step (csrc/ctc_prefix.hip).
+`decoding_algorithm='attention_rescoring'` (a `use_ctc` model; not in the reference) is the two-pass decode: that search's n-best, every
+hypothesis scored by the attention decoder teacher-forced, the best of log p_att + ctc_decode_weight * log p_ctc kept -- no step-by-step
+decode (csrc/rescore.hip).  No language-model term, no length normalisation.
 """
 import glob
 import os
@@ -138,9 +141,9 @@ class AVSR(object):
             from .audio_frontend import LogmelSpec
             self._audio_frontend = LogmelSpec(kwargs.get('audio_transformation', 'logmel_stack_w8s3'), kwargs.get('num_mel_bins', 30),
                                               kwargs.get('sample_rate', 16000))
-        if decoding_algorithm not in ('greedy', 'beam_search', 'ctc_prefix_beam_search'):
+        if decoding_algorithm not in ('greedy', 'beam_search', 'ctc_prefix_beam_search', 'attention_rescoring'):
             raise Exception('The only supported algorithms are `greedy`, `beam_search` and (not in the reference) '
-                            '`ctc_prefix_beam_search`')                                          # decoder_unimodal.py:124
+                            '`ctc_prefix_beam_search`, `attention_rescoring`')                   # decoder_unimodal.py:124
         self._decoding_algorithm, self._beam_width = decoding_algorithm, beam_width
         if decoding_algorithm == 'ctc_prefix_beam_search':    # the CTC head's own search (csrc/ctc_prefix.hip): no decoder step at evaluate
             from ._lib import CTC_PREFIX_MAX_L, CTC_PREFIX_MAX_V, CTC_PREFIX_MAX_W
@@ -148,6 +151,14 @@ class AVSR(object):
                 raise ValueError("decoding_algorithm='ctc_prefix_beam_search' needs use_ctc=True: the search runs on the CTC head")
             if len(self._unit_dict) - 1 > CTC_PREFIX_MAX_V or not 1 <= beam_width <= CTC_PREFIX_MAX_W:
                 raise ValueError("decoding_algorithm='ctc_prefix_beam_search': avsr_ctc_prefix_search covers vocabularies of up to %d "
+                                 "symbols and beam widths of 1 to %d (label sequences of up to %d; got %d symbols, beam_width %d)"
+                                 % (CTC_PREFIX_MAX_V, CTC_PREFIX_MAX_W, CTC_PREFIX_MAX_L, len(self._unit_dict) - 1, beam_width))
+        if decoding_algorithm == 'attention_rescoring':       # the prefix search's n-best rescored by the attention decoder (csrc/rescore.hip)
+            from ._lib import CTC_PREFIX_MAX_L, CTC_PREFIX_MAX_V, CTC_PREFIX_MAX_W
+            if not kwargs.get('use_ctc', False):
+                raise ValueError("decoding_algorithm='attention_rescoring' needs use_ctc=True: the hypotheses are the CTC head's n-best")
+            if len(self._unit_dict) - 1 > CTC_PREFIX_MAX_V or not 1 <= beam_width <= CTC_PREFIX_MAX_W:
+                raise ValueError("decoding_algorithm='attention_rescoring': avsr_ctc_prefix_search covers vocabularies of up to %d "
                                  "symbols and beam widths of 1 to %d (label sequences of up to %d; got %d symbols, beam_width %d)"
                                  % (CTC_PREFIX_MAX_V, CTC_PREFIX_MAX_W, CTC_PREFIX_MAX_L, len(self._unit_dict) - 1, beam_width))
         self._write_attention_alignment = bool(write_attention_alignment)
@@ -174,9 +185,10 @@ class AVSR(object):
             from ._lib import BEAM_CTC_MAX_V
             if not kwargs.get('use_ctc', False):
                 raise ValueError("ctc_decode_weight needs use_ctc=True: the term is the CTC head's prefix score")
-            if decoding_algorithm != 'beam_search':
-                raise ValueError("ctc_decode_weight needs decoding_algorithm='beam_search': the joint scoring is defined on the beam")
-            if len(self._unit_dict) - 1 > BEAM_CTC_MAX_V or beam_width > 64:
+            if decoding_algorithm not in ('beam_search', 'attention_rescoring'):
+                raise ValueError("ctc_decode_weight needs decoding_algorithm='beam_search' (the joint scoring is defined on the beam) "
+                                 "or 'attention_rescoring' (the weight of the n-best's CTC score)")
+            if decoding_algorithm == 'beam_search' and (len(self._unit_dict) - 1 > BEAM_CTC_MAX_V or beam_width > 64):
                 raise ValueError("ctc_decode_weight: avsr_beam_ctc_supported covers vocabularies of up to %d symbols and beam widths "
                                  "of up to 64 (got %d, %d)" % (BEAM_CTC_MAX_V, len(self._unit_dict) - 1, beam_width))
 
@@ -477,6 +489,9 @@ class AVSR(object):
                 ids = self._model.beam_search_decode(batch, beam_width=self._beam_width, max_steps=self._cfg.max_label_length,
                                                      lm=self._lm, lm_weight=self._lm_weight if self._lm is not None else 0.0,
                                                      ctc_weight=self._ctc_decode_weight)
+            elif self._decoding_algorithm == 'attention_rescoring':        # two passes: the head's n-best, then teacher-forced scoring
+                ids = self._model.attention_rescoring(batch, beam_width=self._beam_width, max_steps=self._cfg.max_label_length,
+                                                      ctc_weight=self._ctc_decode_weight)
             elif self._decoding_algorithm == 'ctc_prefix_beam_search':     # the head's own search: the attention decoder never runs
                 ids = self._model.ctc_prefix_beam_search(batch, beam_width=self._beam_width, max_steps=self._cfg.max_label_length)
             else:

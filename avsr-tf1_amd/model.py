@@ -28,9 +28,10 @@ from .config import ATT_CODE, BAHDANAU_TYPES, CELL_ID_DECODER, LUONG_TYPES, Mode
 from .model_base import Batch, Ref, SeqBuf, _FlagReader, _PtrView, _splitk, desc_steplen  # noqa: F401  (re-exported: the public names live here)
 from .model_decoder import DecoderMixin
 from .model_encoder import EncoderMixin
+from .model_rescore import RescoreMixin
 
 
-class Seq2SeqModel(EncoderMixin, DecoderMixin):
+class Seq2SeqModel(EncoderMixin, DecoderMixin, RescoreMixin):
     def __init__(self, cfg: ModelConfig, device="cuda", seed=0, weights: Optional[Dict[str, np.ndarray]] = None):
         cfg.validate()
         if not torch.cuda.is_available():
@@ -432,41 +433,8 @@ class Seq2SeqModel(EncoderMixin, DecoderMixin):
         ops.add_int(self.step, int(self.seed_offset), self.seed)
         self._encode(ws, batch, True)
         D = ws["dec"]
-        H, E, V = D["H"], D["E"], cfg.vocab_size
-        self._decoder_init_state(ws)
-        sampling = cfg.sampling_probability > 0
-        A = D["A"]
-        drop_in = self._dropping and cfg.decoder_dropout[0] < 1.0
-        xm = ops.mat(D["xemb"], E)
-        # decoder inputs = embedding of the GO-prefixed labels (all steps when teacher forcing, only step 0 when sampling)
-        ops.embed_labels(self._emb_t(), batch.labels, cfg.go_id, D["xemb"], D["fed"], B, L, E, 1 if sampling else L)
-        if drop_in:
-            if sampling:     # only row (b, 0): address rows with stride L*E, mask index (b*L + 0)*(E+A) + e
-                ops.dropout_rows(ops.mat(D["xemb"], L * E), ops.mat(D["xemb"], L * E), B, E, self.seed, CELL_ID_DECODER * 4,
-                                 cfg.decoder_dropout[0], L * (E + A))
-            else:
-                ops.dropout_rows(xm, xm, B * L, E, self.seed, CELL_ID_DECODER * 4, cfg.decoder_dropout[0], E + A)
-        if not sampling:
-            ops.gemm(xm, self.P[self._kn("dec/l0")[0]].mat(self.G * H), ops.mat(D["gates"], self.G * H), B * L, self.G * H, E)
-            if self.gru:
-                ops.gemm(xm, self.P["dec/l0/cand_kernel"].mat(H), ops.mat(D["cs"], H), B * L, H, E)
-        self._block_prepare(ws, D)
-        D["desc"] = d = self._block_desc(ws, D, batch.labels_len, 2 if sampling else 0, D["h0"], D["c0"], with_bwd=True)
-        if sampling:
-            d.output_attention = int(cfg.output_attention())
-            d.seed = ops.fptr(self.seed)
-            d.sampling_prob = cfg.sampling_probability
-            if not self._bdrop(D):
-                d.keep_in = d.keep_state = d.keep_out = 1.0
-                d.cell_id = CELL_ID_DECODER
-            d.embedding = ops.fptr(*self._emb())
-            d.wout_t = ops.fptr(self.derived, self.Tr["dec/out/kernel"].off)
-            d.bout = ops.fptr(self.params, self.P["dec/out/bias"].off)
-            d.logits, d.xs, d.labels, d.fed = ops.fptr(D["logits"]), ops.fptr(D["xemb"]), ops.fptr(batch.labels), ops.fptr(D["fed"])
-        ops.attn_rnn_fwd(d, 0, L)
-        if not sampling:
-            ov, O = self._out_vec(D)
-            ops.gemm(ov, self.P["dec/out/kernel"].mat(V), ops.mat(D["logits"], V), B * L, V, O, bias=self._pp("dec/out/bias"))
+        V = cfg.vocab_size
+        self._decoder_train_pass(ws, D, batch.labels, batch.labels_len, cfg.sampling_probability > 0)
         ops.seq_loss(D["logits"], batch.labels, batch.labels_len, self.denom, compute_denom, D["row_loss"], D["dlogits"], B, L, V,
                      loss_fun=cfg.loss_code(), label_smoothing=cfg.label_smoothing)
         ops.reduce_scalar(D["row_loss"], B * L, self.loss)

@@ -369,6 +369,54 @@ class DecoderMixin:
             return D["att"].mat(0), D["A"]
         return D["cell_out"].mat(0), D["H"]
 
+    def _decoder_train_pass(self, ws, D, labels, labels_len, sampling, with_bwd=True, prepare=True, logits=None):
+        """The train graph's decoder on the label rows `labels` [B, L] (fed GO-prefixed): embedding, hoisted input products, the
+        attention-wrapped block in mode 0 (teacher forcing; mode 2 when `sampling`) and the output layer into `logits` (default: the
+        block's own [B, L, V]).  forward_train calls it with its workspace's block; attention_rescoring (model_rescore.py) once per
+        n-best rank over the same memories with prepare=False after the first pass: the initial state and the per-memory preparation
+        (_block_prepare: keys, projected values) depend on the batch alone.  Dropout follows self._dropping, which the preceding
+        _encode(training=...) set: after an evaluation-mode encode every keep-probability is 1 whatever the model was built with."""
+        cfg = self.cfg
+        B, L = D["B"], D["L"]
+        H, E, V = D["H"], D["E"], cfg.vocab_size
+        logits = D["logits"] if logits is None else logits
+        if prepare:
+            self._decoder_init_state(ws)
+        A = D["A"]
+        drop_in = self._dropping and cfg.decoder_dropout[0] < 1.0
+        xm = ops.mat(D["xemb"], E)
+        # decoder inputs = embedding of the GO-prefixed labels (all steps when teacher forcing, only step 0 when sampling)
+        ops.embed_labels(self._emb_t(), labels, cfg.go_id, D["xemb"], D["fed"], B, L, E, 1 if sampling else L)
+        if drop_in:
+            if sampling:     # only row (b, 0): address rows with stride L*E, mask index (b*L + 0)*(E+A) + e
+                ops.dropout_rows(ops.mat(D["xemb"], L * E), ops.mat(D["xemb"], L * E), B, E, self.seed, CELL_ID_DECODER * 4,
+                                 cfg.decoder_dropout[0], L * (E + A))
+            else:
+                ops.dropout_rows(xm, xm, B * L, E, self.seed, CELL_ID_DECODER * 4, cfg.decoder_dropout[0], E + A)
+        if not sampling:
+            ops.gemm(xm, self.P[self._kn("dec/l0")[0]].mat(self.G * H), ops.mat(D["gates"], self.G * H), B * L, self.G * H, E)
+            if self.gru:
+                ops.gemm(xm, self.P["dec/l0/cand_kernel"].mat(H), ops.mat(D["cs"], H), B * L, H, E)
+        if prepare:
+            self._block_prepare(ws, D)
+        D["desc"] = d = self._block_desc(ws, D, labels_len, 2 if sampling else 0, D["h0"], D["c0"], with_bwd=with_bwd)
+        if sampling:
+            d.output_attention = int(cfg.output_attention())
+            d.seed = ops.fptr(self.seed)
+            d.sampling_prob = cfg.sampling_probability
+            if not self._bdrop(D):
+                d.keep_in = d.keep_state = d.keep_out = 1.0
+                d.cell_id = CELL_ID_DECODER
+            d.embedding = ops.fptr(*self._emb())
+            d.wout_t = ops.fptr(self.derived, self.Tr["dec/out/kernel"].off)
+            d.bout = ops.fptr(self.params, self.P["dec/out/bias"].off)
+            d.logits, d.xs, d.labels, d.fed = ops.fptr(logits), ops.fptr(D["xemb"]), ops.fptr(labels), ops.fptr(D["fed"])
+        ops.attn_rnn_fwd(d, 0, L)
+        if not sampling:
+            ov, O = self._out_vec(D)
+            ops.gemm(ov, self.P["dec/out/kernel"].mat(V), ops.mat(logits, V), B * L, V, O, bias=self._pp("dec/out/bias"))
+        return logits
+
     def beam_search_decode(self, *args, **kw):
         """See _beam_search_decode.  If a persistent kernel's bounded wait expired during the pass (workgroups not co-resident) the
         results are invalid: check_persistent() has then switched the one-launch paths off and the pass is redone with one launch

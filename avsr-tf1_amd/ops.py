@@ -403,6 +403,20 @@ def ctc_prefix_search(z, ld, in_len, B, T, V, beam_width, L_max, ids, lens, scor
     check(_L().avsr_ctc_prefix_search(C.byref(a), _s()), "avsr_ctc_prefix_search")
 
 
+def seq_logprob(logits, labels, labels_len, B, L, V, out, out_stride=1, out_offset=0):
+    """avsr_seq_logprob: out[out_offset + b * out_stride] = sum_{t < min(labels_len[b], L)} log_softmax(logits[b, t])[labels[b, t]]."""
+    assert out_offset >= 0 and out_stride >= 1 and out_offset + (int(B) - 1) * int(out_stride) < out.numel()
+    check(_L().avsr_seq_logprob(fptr(logits), fptr(labels), fptr(labels_len), int(B), int(L), int(V), fptr(out, out_offset),
+                                int(out_stride), _s()), "avsr_seq_logprob")
+
+
+def rescore_select(s_att, s_ctc, n, B, K, weight, order, final):
+    """avsr_rescore_select: final = s_att (+ weight * s_ctc) over the first n[b] of K slots, order = their stable sort, best first."""
+    assert min(s_att.numel(), s_ctc.numel(), order.numel(), final.numel()) >= int(B) * int(K) and n.numel() >= int(B)
+    check(_L().avsr_rescore_select(fptr(s_att), fptr(s_ctc), fptr(n), int(B), int(K), float(weight), fptr(order), fptr(final), _s()),
+          "avsr_rescore_select")
+
+
 def normed_v(v, g, vn, H):
     check(_L().avsr_normed_v(fptr(v), fptr(g), fptr(vn), H, _s()), "avsr_normed_v")
 

@@ -533,6 +533,22 @@ int avsr_ctc_prefix_search_supported(int32_t V, int32_t beam_width, int32_t L_ma
 /* AVSR_ERR_ARG for a NULL / non-positive / inconsistent argument, AVSR_ERR_UNSUPPORTED outside the limits: both before any launch. */
 int avsr_ctc_prefix_search(const avsr_ctc_prefix_args* a, void* stream);
 
+/* Attention rescoring of the CTC n-best (csrc/rescore.hip; the rule is this project's own).
+ * avsr_seq_logprob: out[b * out_stride] = sum_{t < min(labels_len[b], L)} log_softmax(logits[b][t][:V])[labels[b][t]] -- the
+ *   log-probability of a teacher-forced label row; labels_len[b] <= 0 gives 0.0.  logits [B][L][V] and labels [B][L] are read only (no
+ *   d logits, no normaliser).  2 <= V <= 1024 (AVSR_ERR_UNSUPPORTED above), any remainder.  The labels are on the device and so not
+ *   checked by the host: a label outside 0 .. V-1 contributes -inf and is never dereferenced.  out_stride >= 1: with
+ *   out = s_att + k, out_stride = K, pass k fills column k of s_att [B][K]; no other element of out is written.
+ * avsr_rescore_select: per utterance final[k] = s_att[b][k] + weight * s_ctc[b][k] (weight == 0: s_att[b][k], the product is not
+ *   formed; product and sum rounded separately) for k < n[b] (clamped to 0 .. K), then order [B][K] = the k sorted by final descending,
+ *   ties to the lower k, and final_out [B][K] in that order; slots >= n[b] get order -1 and final -inf.  1 <= K <= 64.
+ * Both: one launch, no atomics, fixed reduction order -- bit-identical across launches.  AVSR_ERR_ARG (NULL pointer, B <= 0, L <= 0,
+ * V < 2, out_stride < 1, K outside 1..64, weight negative or not finite) is decided on the host before any launch. */
+int avsr_seq_logprob(const float* logits, const int32_t* labels, const int32_t* labels_len, int32_t B, int32_t L, int32_t V,
+                     float* out, int64_t out_stride, void* stream);
+int avsr_rescore_select(const float* s_att, const float* s_ctc, const int32_t* n, int32_t B, int32_t K, float weight,
+                        int32_t* order, float* final_out, void* stream);
+
 /* Post-loop helpers of the attention backward (see csrc/attention.hip). */
 int avsr_attn_alpha_rows(float* scores, const float* dscores, const int32_t* len, const int32_t* steplen,
                          const float* g, float* rowdot, int32_t B, int32_t L, int32_t T, void* stream);
