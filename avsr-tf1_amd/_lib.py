@@ -162,6 +162,15 @@ class CtcPrefixArgs(C.Structure):
                [(n, C.c_void_p) for n in ("z", "in_len", "ids", "lens", "score", "trace_parent", "trace_sym", "trace_pb", "trace_pnb")]
 
 
+CTC_ALIGN_MAX_L = 512                  # AVSR_CTC_ALIGN_MAX_L of include/avsr_hip.h
+
+
+class CtcAlignArgs(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("B", "T", "L", "V")] + [("ld", C.c_int64)] + \
+               [(n, C.c_void_p) for n in ("z", "labels", "target_len", "in_len", "score", "status", "path", "frame_lp", "start", "end", "ws")] + \
+               [("ws_bytes", C.c_int64)]
+
+
 class ColsumJob(C.Structure):
     _fields_ = [("a", Mat), ("b", Mat), ("out", C.c_void_p), ("rows", C.c_int32), ("F", C.c_int32), ("alpha", C.c_float), ("beta", C.c_float)]
 
@@ -172,7 +181,8 @@ class TransposeJob(C.Structure):
 
 _STRUCTS = {"avsr_dec_layer": DecLayer, "avsr_mat": Mat, "avsr_gemm_desc": GemmDesc, "avsr_rnn_layer": RnnLayer, "avsr_rnn_stack": RnnStack,
             "avsr_conv_desc": ConvDesc, "avsr_conv_launch": ConvLaunch, "avsr_conv3d_desc": Conv3dDesc, "avsr_logmel_args": LogmelArgs, "avsr_ctc_args": CtcArgs, "avsr_attn_mech": AttnMech, "avsr_attn_rnn": AttnRnn, "avsr_transpose_job": TransposeJob,
-            "avsr_colsum_job": ColsumJob, "avsr_beam_lm": BeamLm, "avsr_beam_ctc": BeamCtc, "avsr_ctc_prefix_args": CtcPrefixArgs}
+            "avsr_colsum_job": ColsumJob, "avsr_beam_lm": BeamLm, "avsr_beam_ctc": BeamCtc, "avsr_ctc_prefix_args": CtcPrefixArgs,
+            "avsr_ctc_align_args": CtcAlignArgs}
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 # argument types of every entry point that returns an int status (include/avsr_hip.h)
@@ -218,6 +228,8 @@ _SIGS = {
     "avsr_ctc_best_path": [_vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp],
     "avsr_ctc_prefix_search_supported": [_i32, _i32, _i32],
     "avsr_ctc_prefix_search": [C.POINTER(CtcPrefixArgs), _vp],
+    "avsr_ctc_align_supported": [_i32, _i32],
+    "avsr_ctc_align": [C.POINTER(CtcAlignArgs), _vp],
     "avsr_seq_logprob": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp],
     "avsr_rescore_select": [_vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp],
     "avsr_batchnorm_apply": [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp],
@@ -288,8 +300,9 @@ _SIGS = {
     "avsr_prof_begin": [_i32],
     "avsr_prof_end": [C.POINTER(_i32), C.POINTER(_f32), C.POINTER(C.c_double)],
 }
-# every symbol the library must export: the table above plus the five whose return type load() sets on its own
-EXPORTS = ["avsr_abi_version", "avsr_sizeof", "avsr_attn_rnn_fused_ws_floats", "avsr_conv3d_wgrad_scratch_floats", "avsr_ctc_ws_floats"] + list(_SIGS)
+# every symbol the library must export: the table above plus the six whose return type load() sets on its own
+EXPORTS = ["avsr_abi_version", "avsr_sizeof", "avsr_attn_rnn_fused_ws_floats", "avsr_conv3d_wgrad_scratch_floats", "avsr_ctc_ws_floats",
+           "avsr_ctc_align_ws_bytes"] + list(_SIGS)
 
 _lib = None
 
@@ -328,6 +341,8 @@ def load():
     lib.avsr_conv3d_wgrad_scratch_floats.restype = C.c_int64
     lib.avsr_ctc_ws_floats.argtypes = [_i32, _i32, _i32]
     lib.avsr_ctc_ws_floats.restype = C.c_int64
+    lib.avsr_ctc_align_ws_bytes.argtypes = [_i32, _i32, _i32]
+    lib.avsr_ctc_align_ws_bytes.restype = C.c_int64
     for name, st in _STRUCTS.items():
         n = lib.avsr_sizeof(name.encode())
         if n != C.sizeof(st):

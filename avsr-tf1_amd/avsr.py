@@ -35,6 +35,8 @@ prefix beam search of width `beam_width` on that head alone -- no decoder step (
 `decoding_algorithm='attention_rescoring'` (a `use_ctc` model; not in the reference) is the two-pass decode: that search's n-best, every
 hypothesis scored by the attention decoder teacher-forced, the best of log p_att + ctc_decode_weight * log p_ctc kept -- no step-by-step
 decode (csrc/rescore.hip).  No language-model term, no length normalisation.
+`AVSR.align` (a `use_ctc` model; not in the reference) returns and writes the forced alignment of every evaluate utterance's labels, or of
+its predictions, on the CTC head: per label the first and last frame and a confidence (csrc/ctc_align.hip).
 """
 import glob
 import os
@@ -476,6 +478,76 @@ class AVSR(object):
                 if arch == 'av_align':
                     write_png_gray(base + '_av.png', alignment_image(enc[idx]))
 
+    def _decode(self, batch):
+        """The predictions of one batch under `decoding_algorithm`: rows of ids (a numpy array or a list of id lists)."""
+        if self._decoding_algorithm == 'beam_search':     # avsr.py:58-59 default: width 10, first beam returned
+            ids = self._model.beam_search_decode(batch, beam_width=self._beam_width, max_steps=self._cfg.max_label_length,
+                                                 lm=self._lm, lm_weight=self._lm_weight if self._lm is not None else 0.0,
+                                                 ctc_weight=self._ctc_decode_weight)
+        elif self._decoding_algorithm == 'attention_rescoring':        # two passes: the head's n-best, then teacher-forced scoring
+            ids = self._model.attention_rescoring(batch, beam_width=self._beam_width, max_steps=self._cfg.max_label_length,
+                                                  ctc_weight=self._ctc_decode_weight)
+        elif self._decoding_algorithm == 'ctc_prefix_beam_search':     # the head's own search: the attention decoder never runs
+            ids = self._model.ctc_prefix_beam_search(batch, beam_width=self._beam_width, max_steps=self._cfg.max_label_length)
+        else:
+            ids = self._model.greedy_decode(batch, max_steps=self._cfg.max_label_length)
+        if not isinstance(ids, list):
+            ids = ids.cpu().numpy()
+        return ids
+
+    def align(self, checkpoint_path, epoch=None, targets='labels', frame_shift=None):
+        """Forced alignment on the CTC head (not in the reference; INTEGRATION.md section 8, csrc/ctc_align.hip): restores the checkpoint,
+        walks the evaluate records and returns {name: [(symbol, start, end, confidence), ...]}, one tuple per label -- the Viterbi
+        alignment of each utterance's labels (targets='labels', the EOS left out) or of what `evaluate` would predict for it
+        (targets='predictions', cut at the first EOS).  start / end are the first / last frame of the label's run, frames of the CTC
+        stream's encoder; with frame_shift (seconds per frame, the caller's knowledge of the features) they are seconds rounded to three
+        decimals and end is exclusive.  confidence = exp(mean log-probability of the run's frames).  An utterance whose target has no
+        valid alignment (fewer frames than labels plus adjacent repeats) maps to None.  Rank 0 writes
+        predictions/<run>/ctc_alignment_epoch_<N>.txt: per utterance `name score`, one `start end symbol confidence` line per label
+        (or `# no alignment`), then a line holding `.`."""
+        if not self._cfg.use_ctc:
+            raise ValueError("align needs use_ctc=True: the alignment is computed on the CTC head")
+        if targets not in ('labels', 'predictions'):
+            raise ValueError("align: targets must be 'labels' or 'predictions' (got %r)" % (targets,))
+        if frame_shift is not None and not (float(frame_shift) > 0.0 and float(frame_shift) < float('inf')):
+            raise ValueError("align: frame_shift must be a positive number of seconds per frame (got %r)" % (frame_shift,))
+        self.restore(checkpoint_path)
+        eos = self._cfg.eos_id
+        result, scores = {}, {}
+        for bd in self._iterator('evaluate'):
+            batch, names = self._to_batch(bd)
+            tg = None
+            if targets == 'predictions':
+                tg = []
+                for row in self._decode(batch):
+                    row = [int(s) for s in row]
+                    tg.append(row[:row.index(eos)] if eos in row else row)
+            for name, al in zip(names, self._model.ctc_align(batch, tg)):
+                file = name.decode('utf-8')
+                scores[file] = al['score']
+                if not al['status']:
+                    result[file] = None
+                    continue
+                segs = []
+                for lab, s, e, conf in al['segments']:
+                    if frame_shift is not None:
+                        s, e = round(s * float(frame_shift), 3), round((e + 1) * float(frame_shift), 3)
+                    segs.append((self._unit_dict[lab], s, e, conf))
+                result[file] = segs
+        if self._rank == 0:
+            outdir = path.join('predictions', path.split(path.split(checkpoint_path)[0])[-1])
+            makedirs(outdir, exist_ok=True)
+            tf = '{:.3f}' if frame_shift is not None else '{:d}'
+            with open(path.join(outdir, 'ctc_alignment_epoch_{}.txt'.format(epoch)), 'w') as f:
+                for file, segs in result.items():
+                    f.write('{} {:.6f}\n'.format(file, scores[file]))
+                    if segs is None:
+                        f.write('# no alignment\n')
+                    for sym, s, e, conf in segs or ():
+                        f.write((tf + ' ' + tf + ' {} {:.6f}\n').format(s, e, sym, conf))
+                    f.write('.\n')
+        return result
+
     def evaluate(self, checkpoint_path, epoch=None, alignments_outdir='./alignments/tmp/', beam_graphs_outdir='./beam_graphs/tmp/'):
         self.restore(checkpoint_path)                         # the path argument is honoured, as in avsr.py:328-331
         predictions_dict, labels_dict, ctc_dict = {}, {}, {}
@@ -485,19 +557,7 @@ class AVSR(object):
             it = self._prefetched(it, depth=2)
         for bd in it:
             batch, names = self._to_batch(bd)
-            if self._decoding_algorithm == 'beam_search':     # avsr.py:58-59 default: width 10, first beam returned
-                ids = self._model.beam_search_decode(batch, beam_width=self._beam_width, max_steps=self._cfg.max_label_length,
-                                                     lm=self._lm, lm_weight=self._lm_weight if self._lm is not None else 0.0,
-                                                     ctc_weight=self._ctc_decode_weight)
-            elif self._decoding_algorithm == 'attention_rescoring':        # two passes: the head's n-best, then teacher-forced scoring
-                ids = self._model.attention_rescoring(batch, beam_width=self._beam_width, max_steps=self._cfg.max_label_length,
-                                                      ctc_weight=self._ctc_decode_weight)
-            elif self._decoding_algorithm == 'ctc_prefix_beam_search':     # the head's own search: the attention decoder never runs
-                ids = self._model.ctc_prefix_beam_search(batch, beam_width=self._beam_width, max_steps=self._cfg.max_label_length)
-            else:
-                ids = self._model.greedy_decode(batch, max_steps=self._cfg.max_label_length)
-            if not isinstance(ids, list):
-                ids = ids.cpu().numpy()
+            ids = self._decode(batch)
             if self._write_attention_alignment:
                 self._write_alignments(names, alignments_outdir)
             for idx in range(len(names)):

@@ -8,7 +8,7 @@ import os
 import numpy as np
 import torch
 from . import ops, params as PR
-from ._lib import AttnRnn, CTC_PREFIX_MAX_L, CTC_PREFIX_MAX_V, CTC_PREFIX_MAX_W, RnnStack
+from ._lib import AttnRnn, CTC_ALIGN_MAX_L, CTC_PREFIX_MAX_L, CTC_PREFIX_MAX_V, CTC_PREFIX_MAX_W, RnnStack
 from .config import ATT_CODE, BAHDANAU_TYPES, CELL_ID_DECODER, LUONG_TYPES, ModelConfig, encoder_cell_id
 from .model_base import Batch, Ref, SeqBuf, _FlagReader, _PtrView, _splitk, desc_steplen  # noqa: F401
 
@@ -486,6 +486,74 @@ class EncoderMixin:
                     seq.append(k)
                 prev = k
             out.append(seq)
+        return out
+
+    def ctc_align(self, batch, targets=None):
+        """use_ctc: forced alignment on the head (avsr_ctc_align, csrc/ctc_align.hip; the rule is INTEGRATION.md section 8) -- encoders in
+        evaluation mode, the head, ONE launch for the batch: the single most probable alignment of a given label sequence to the frames
+        of the CTC stream's encoder.  targets=None aligns batch.labels without their EOS; otherwise a list of B id lists (no EOS), for
+        example what ctc_prefix_beam_search or attention_rescoring returned.  One dict per utterance: status (1, or 0 where the labels
+        have no valid alignment: score 0.0, empty path and segments), score (log-probability of the alignment), path (the class of every
+        frame, blank = vocab_size) and segments, one (label_id, start, end, confidence) per label with start / end the first / last frame
+        of its run and confidence = exp(mean log-probability of the run's frames)."""
+        out = self._ctc_align(batch, targets)
+        if self.check_persistent():
+            out = self._ctc_align(batch, targets)
+        return out
+
+    def _ctc_align(self, batch, targets):
+        cfg = self.cfg
+        if cfg.architecture == "lm":
+            raise ValueError("ctc_align: architecture='lm' has no encoder, so no CTC head to align on")
+        if not cfg.use_ctc:
+            raise ValueError("ctc_align needs a model built with use_ctc=True")
+        B = (batch.audio if batch.audio is not None else batch.video).shape[0]
+        if targets is None:
+            L = int(batch.labels.shape[1])
+        else:
+            targets = [[int(s) for s in g] for g in targets]
+            if len(targets) != B:
+                raise ValueError("ctc_align: targets must hold one id list per utterance (got %d lists for a batch of %d)" % (len(targets), B))
+            L = max([len(g) for g in targets] + [1])
+        if L > CTC_ALIGN_MAX_L:
+            raise ValueError("ctc_align: avsr_ctc_align covers targets of up to %d labels (got %d)" % (CTC_ALIGN_MAX_L, L))
+        V, dev = cfg.vocab_size, self.dev
+        if targets is None:
+            labels = batch.labels
+            tlen = (batch.labels_len.clamp(0, L) - 1).clamp(min=0).to(torch.int32)     # on the device: the row without its EOS
+        else:
+            lab = np.zeros((B, L), np.int32)
+            for b, g in enumerate(targets):
+                lab[b, :len(g)] = g
+            labels = torch.as_tensor(lab).to(dev)
+            tlen = torch.as_tensor(np.array([len(g) for g in targets], np.int32)).to(dev)
+        Ta = self._audio_rows(batch)
+        Tv = batch.video.shape[1] if batch.video is not None else 0
+        ws = self._get_ws(B, Ta, Tv, 1, True)
+        self._refresh_derived()
+        self._encode(ws, batch, False)
+        E, Cc = self._ctc_head(ws)
+        T = E["T"]
+        key = ("ctc_align", L)
+        if key not in E:
+            i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)
+            E[key] = dict(score=torch.zeros(B, device=dev), status=i32(B), path=i32(B, T), frame_lp=torch.zeros(B, T, device=dev),
+                          start=i32(B, L), end=i32(B, L),
+                          ws=torch.zeros(ops.ctc_align_ws_bytes(B, T, L) // 8, dtype=torch.int64, device=dev))
+        O = E[key]
+        ops.ctc_align(E["ctc_z"], Cc, labels, tlen, E["len"], B, T, L, V, O["score"], O["status"], O["path"], O["frame_lp"], O["start"],
+                      O["end"], O["ws"])
+        score, status, path, lp = (O[k].cpu().numpy() for k in ("score", "status", "path", "frame_lp"))
+        start, end, tl, lab = O["start"].cpu().numpy(), O["end"].cpu().numpy(), tlen.cpu().numpy(), labels.cpu().numpy()
+        lens = np.clip(E["len"].cpu().numpy(), 0, T)
+        out = []
+        for b in range(B):
+            if not status[b]:
+                out.append(dict(status=0, score=0.0, path=[], segments=[]))
+                continue
+            segs = [(int(lab[b, j]), int(start[b, j]), int(end[b, j]),
+                     float(np.exp(np.mean(lp[b, start[b, j]:end[b, j] + 1], dtype=np.float64)))) for j in range(int(tl[b]))]
+            out.append(dict(status=1, score=float(score[b]), path=[int(k) for k in path[b, :lens[b]]], segments=segs))
         return out
 
     def ctc_prefix_beam_search(self, batch, beam_width=10, max_steps=None, nbest=False):

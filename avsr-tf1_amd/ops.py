@@ -403,6 +403,27 @@ def ctc_prefix_search(z, ld, in_len, B, T, V, beam_width, L_max, ids, lens, scor
     check(_L().avsr_ctc_prefix_search(C.byref(a), _s()), "avsr_ctc_prefix_search")
 
 
+def ctc_align_supported(V, L):
+    """Host-side: does avsr_ctc_align run this shape (include/avsr_hip.h AVSR_CTC_ALIGN_MAX_L)?"""
+    return bool(_L().avsr_ctc_align_supported(int(V), int(L)))
+
+
+def ctc_align_ws_bytes(B, T, L):
+    return int(_L().avsr_ctc_align_ws_bytes(int(B), int(T), int(L)))
+
+
+def ctc_align(z, ld, labels, target_len, in_len, B, T, L, V, score, status, path, frame_lp, start, end, ws):
+    """avsr_ctc_align: z [B*T, ld] over V + 1 real classes (blank = V), labels [B, L] with target_len [B] labels each (no EOS) -> the
+    Viterbi alignment: score / status [B], path / frame_lp [B, T], start / end [B, L].  ws: a byte buffer of ctc_align_ws_bytes(B, T, L)."""
+    from ._lib import CtcAlignArgs
+    a = CtcAlignArgs()
+    a.B, a.T, a.L, a.V, a.ld = int(B), int(T), int(L), int(V), int(ld)
+    a.z, a.labels, a.target_len, a.in_len = fptr(z), fptr(labels), fptr(target_len), fptr(in_len)
+    a.score, a.status, a.path, a.frame_lp, a.start, a.end = fptr(score), fptr(status), fptr(path), fptr(frame_lp), fptr(start), fptr(end)
+    a.ws, a.ws_bytes = fptr(ws), int(ws.numel() * ws.element_size())
+    check(_L().avsr_ctc_align(C.byref(a), _s()), "avsr_ctc_align")
+
+
 def seq_logprob(logits, labels, labels_len, B, L, V, out, out_stride=1, out_offset=0):
     """avsr_seq_logprob: out[out_offset + b * out_stride] = sum_{t < min(labels_len[b], L)} log_softmax(logits[b, t])[labels[b, t]]."""
     assert out_offset >= 0 and out_stride >= 1 and out_offset + (int(B) - 1) * int(out_stride) < out.numel()

@@ -533,6 +533,45 @@ int avsr_ctc_prefix_search_supported(int32_t V, int32_t beam_width, int32_t L_ma
 /* AVSR_ERR_ARG for a NULL / non-positive / inconsistent argument, AVSR_ERR_UNSUPPORTED outside the limits: both before any launch. */
 int avsr_ctc_prefix_search(const avsr_ctc_prefix_args* a, void* stream);
 
+/* CTC forced alignment (csrc/ctc_align.hip; the rule is this project's own): the single most probable
+ * alignment (Viterbi path) of a GIVEN label row to the frames of the head.  z [B * T][ld] are the head's logits over V + 1 real classes,
+ * the blank is class V; in_len [B], T_b = clamp(in_len, 0, T); labels [B][L], target_len [B], U = clamp(target_len, 0, L) -- a plain
+ * label count: nothing is cut off for an EOS.  Frames t >= T_b and columns >= V + 1 of a wider row are never read.
+ *   score [B]          log-probability of the best alignment (0 without one)
+ *   status [B]         1, or 0 when the utterance has no valid alignment -- avsr_ctc_loss's test: T_b < U + adjacent equal label
+ *                      pairs, T_b == 0, or a label outside 0 .. V-1; then every per-frame and per-label output holds its padding
+ *   path [B][T]        the class of every frame t < T_b (blank = V), -1 for t >= T_b
+ *   frame_lp [B][T]    log_softmax(z[b, t, :V+1])[path[t]], 0 for t >= T_b
+ *   start, end [B][L]  first and last frame of label j's run, inclusive; -1 for j >= U
+ * Ties go to the higher state index: stay over s - 1 over s - 2, and at the end the last blank over the last label.
+ * ws: avsr_ctc_align_ws_bytes(B, T, L) bytes of scratch, 8-byte aligned (row normalisers and 2-bit backpointers over all T frames
+ * live there, so T is not bounded by on-chip memory).  One launch, one workgroup per utterance, no atomics (two launches on the same
+ * inputs are bit-identical), no host read, no memset / memcpy: safe under stream capture.  Every output element is written by every
+ * launch.  Nothing is ever NaN.  Limits: 1 <= L <= 512, any V >= 1, any T. */
+#define AVSR_CTC_ALIGN_MAX_L 512
+typedef struct avsr_ctc_align_args {
+  int32_t B, T, L, V;
+  int64_t ld;
+  const float* z;
+  const int32_t* labels;
+  const int32_t* target_len;
+  const int32_t* in_len;
+  float* score;
+  int32_t* status;
+  int32_t* path;
+  float* frame_lp;
+  int32_t* start;
+  int32_t* end;
+  void* ws;
+  int64_t ws_bytes;
+} avsr_ctc_align_args;
+/* 1 if avsr_ctc_align runs this shape, else 0 (decided on the host; nothing is dereferenced). */
+int avsr_ctc_align_supported(int32_t V, int32_t L);
+int64_t avsr_ctc_align_ws_bytes(int32_t B, int32_t T, int32_t L);
+/* AVSR_ERR_ARG for a NULL pointer, a non-positive size, ld < V + 1, a misaligned ws or ws_bytes too small, AVSR_ERR_UNSUPPORTED outside
+ * the limit: both before any launch. */
+int avsr_ctc_align(const avsr_ctc_align_args* a, void* stream);
+
 /* Attention rescoring of the CTC n-best (csrc/rescore.hip; the rule is this project's own).
  * avsr_seq_logprob: out[b * out_stride] = sum_{t < min(labels_len[b], L)} log_softmax(logits[b][t][:V])[labels[b][t]] -- the
  *   log-probability of a teacher-forced label row; labels_len[b] <= 0 gives 0.0.  logits [B][L][V] and labels [B][L] are read only (no
