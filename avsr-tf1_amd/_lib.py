@@ -59,6 +59,12 @@ class RnnStack(C.Structure):
                 ("layer", RnnLayer * MAX_LAYERS)]
 
 
+class RnnLaunch(C.Structure):
+    """avsr_rnn_launch: one record of avsr_rnn_plan."""
+    _fields_ = [(n, C.c_int32) for n in ("form", "stacks", "rows_per_group", "rows_per_slice", "launches", "wg_per_xcd", "crossing_edges",
+                                         "top_tiles")]
+
+
 class AttnMech(C.Structure):
     _fields_ = [("type", C.c_int32), ("T", C.c_int32), ("D", C.c_int32), ("chunk", C.c_int32),
                 ("len", C.c_void_p), ("keys", C.c_void_p), ("values", C.c_void_p),
@@ -180,6 +186,7 @@ class TransposeJob(C.Structure):
 
 
 _STRUCTS = {"avsr_dec_layer": DecLayer, "avsr_mat": Mat, "avsr_gemm_desc": GemmDesc, "avsr_rnn_layer": RnnLayer, "avsr_rnn_stack": RnnStack,
+            "avsr_rnn_launch": RnnLaunch,
             "avsr_conv_desc": ConvDesc, "avsr_conv_launch": ConvLaunch, "avsr_conv3d_desc": Conv3dDesc, "avsr_logmel_args": LogmelArgs, "avsr_ctc_args": CtcArgs, "avsr_attn_mech": AttnMech, "avsr_attn_rnn": AttnRnn, "avsr_transpose_job": TransposeJob,
             "avsr_colsum_job": ColsumJob, "avsr_beam_lm": BeamLm, "avsr_beam_ctc": BeamCtc, "avsr_ctc_prefix_args": CtcPrefixArgs,
             "avsr_ctc_align_args": CtcAlignArgs}
@@ -194,6 +201,7 @@ _SIGS = {
     "avsr_rnn_set_persistent": [_vp, _i64],
     "avsr_rnn_set_persistent_mode": [_i32],
     "avsr_rnn_set_persistent_scratch": [_vp, _i64],
+    "avsr_rnn_plan": [C.POINTER(RnnStack), _i32, _i32, _i32, _i64, _i64, C.POINTER(RnnLaunch), _i32],
     "avsr_attn_rnn_fwd": [C.POINTER(AttnRnn), _i32, _i32, _vp],
     "avsr_attn_rnn_fused_eligible": [C.POINTER(AttnRnn)],
     "avsr_attn_rnn_fused_fwd_active": [C.POINTER(AttnRnn)],

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include "wave.h"          // lds_barrier, p_sigmoid / p_tanh
+#include "avsr_hip.h"      // avsr_rnn_launch
 
 #define P_HDR 256          // sync words reserved ahead of the counters: [0] sticky error flag, [16..] debug timing
 
@@ -10,6 +11,22 @@ namespace avsr {
 extern int32_t* g_sync;
 extern int64_t g_sync_ints;
 extern int g_persist_mode;
+extern float* g_persist_scratch;
+extern int64_t g_persist_scratch_floats;
+
+// avsr_rnn_plan: while this thread's recorder is set, the dry paths of avsr_rnn_fwd_persistent / avsr_rnn_bwd_persistent note the form
+// they decided on (every real call runs with it NULL)
+struct RnnPlanRec { avsr_rnn_launch* out; int cap, n; };
+extern thread_local RnnPlanRec* g_rnn_plan;
+static inline void rnn_plan_note(int form, int stacks, int rows_per_group, int rows_per_slice, int B, int wg_per_xcd, int crossing = 0,
+                                 int top_tiles = 0) {
+  RnnPlanRec* R = g_rnn_plan;
+  if (!R) return;
+  if (R->n < R->cap)
+    R->out[R->n] = avsr_rnn_launch{form, stacks, rows_per_group, rows_per_slice, (B + rows_per_slice - 1) / rows_per_slice, wg_per_xcd, crossing,
+                                   top_tiles};
+  ++R->n;
+}
 
 __device__ __forceinline__ f32x4 ld4_sc1(const float* p) {
   // 16-byte load that bypasses this CU's L1 (the line may have been rewritten by another CU since we last read it)

@@ -8,6 +8,7 @@
 // (BPTT) runs the mirrored wavefront.
 #include "step.h"
 #include "avsr_hip.h"
+#include "persist.h"
 
 extern "C" int avsr_step_launch_raw(const void* launch, void* stream);
 int avsr_rnn_fwd_persistent(const avsr_rnn_stack* st, int32_t n, void* stream, int dry);
@@ -15,20 +16,39 @@ int avsr_rnn_bwd_persistent(const avsr_rnn_stack* st, int32_t n, void* stream, i
 
 // Persistent execution: all stacks in one launch when they fit together, else one launch per stack when every
 // stack fits on its own (checked first: nothing runs unless everything can), else AVSR_ERR_UNSUPPORTED.
-static int run_persistent(int (*fn)(const avsr_rnn_stack*, int32_t, void*, int), const avsr_rnn_stack* st, int32_t n, void* stream) {
+// dry: decide only (avsr_rnn_plan): the same conditions in the same order, nothing launched.
+static int run_persistent(int (*fn)(const avsr_rnn_stack*, int32_t, void*, int), const avsr_rnn_stack* st, int32_t n, void* stream, int dry = 0) {
   for (int i = 0; i < n; ++i)                      // ResidualWrapper'd layers run through the per-step launches
     for (int l = 0; l < st[i].n_layers && l < AVSR_MAX_LAYERS; ++l)
       if (st[i].layer[l].residual) return AVSR_ERR_UNSUPPORTED;
-  int rc = fn(st, n, stream, 0);
+  int rc = fn(st, n, stream, dry);
   if (rc != AVSR_ERR_UNSUPPORTED || n == 1) return rc;
+  avsr::RnnPlanRec* const rec = avsr::g_rnn_plan;
+  const int noted = rec ? rec->n : 0;
   for (int i = 0; i < n; ++i)
-    if ((rc = fn(st + i, 1, stream, 1)) != AVSR_OK) return rc;
+    if ((rc = fn(st + i, 1, stream, 1)) != AVSR_OK) { if (rec) rec->n = noted; return rc; }   // (a plan keeps no record of stacks that fitted)
+  if (dry) return AVSR_OK;
   for (int i = 0; i < n; ++i)
     if ((rc = fn(st + i, 1, stream, 0)) != AVSR_OK) return rc;
   return AVSR_OK;
 }
 
+// launches of the per-step form: the wavefront's anti-diagonals (two phases each for a GRU)
+static int wavefront_steps(const avsr_rnn_stack* st, int32_t n) {
+  int nsteps = 0;
+  for (int i = 0; i < n; ++i) nsteps = nsteps > st[i].T + st[i].n_layers - 1 ? nsteps : st[i].T + st[i].n_layers - 1;
+  return nsteps;
+}
+// tasks of its widest launch (every layer of every stack): one StepLaunch holds STEP_MAX_TASKS
+static int wavefront_tasks(const avsr_rnn_stack* st, int32_t n) {
+  int ntask = 0;
+  for (int i = 0; i < n; ++i) ntask += st[i].n_layers;
+  return ntask;
+}
+
 namespace avsr {
+
+thread_local RnnPlanRec* g_rnn_plan = nullptr;
 
 static inline float* hbuf(const avsr_rnn_layer& l, int B, int parity) { return l.state + (long)parity * B * l.units; }
 static inline float* cbuf(const avsr_rnn_layer& l, int B, int parity) { return l.state + (long)(2 + parity) * B * l.units; }
@@ -69,7 +89,7 @@ extern "C" int avsr_rnn_fwd(const avsr_rnn_stack* st, int32_t n, void* stream) {
     rc = run_persistent(avsr_rnn_fwd_persistent, st, n, stream);             // 8-row groups per XCD / the agent-scope form
     if (rc != AVSR_ERR_UNSUPPORTED) return rc;
   }
-  int nsteps = 0, ntask_max = 0;
+  const int nsteps = wavefront_steps(st, n);
   for (int i = 0; i < n; ++i) {
     const avsr_rnn_stack& S = st[i];
     if (S.cell != 0 && S.cell != 1) return AVSR_ERR_UNSUPPORTED;
@@ -84,10 +104,8 @@ extern "C" int avsr_rnn_fwd(const avsr_rnn_stack* st, int32_t n, void* stream) {
       if (avsr::dev_zero(hbuf(Ly, S.B, 0), sizeof(float) * S.B * Ly.units, s) != hipSuccess) return AVSR_ERR_HIP;
       if (avsr::dev_zero(cbuf(Ly, S.B, 0), sizeof(float) * S.B * Ly.units, s) != hipSuccess) return AVSR_ERR_HIP;
     }
-    nsteps = nsteps > S.T + S.n_layers - 1 ? nsteps : S.T + S.n_layers - 1;
-    ntask_max += S.n_layers;
   }
-  if (ntask_max > STEP_MAX_TASKS) return AVSR_ERR_UNSUPPORTED;
+  if (wavefront_tasks(st, n) > STEP_MAX_TASKS) return AVSR_ERR_UNSUPPORTED;
 
   static thread_local StepLaunch L;
   const bool gru = st[0].cell == 1;
@@ -197,7 +215,7 @@ extern "C" int avsr_rnn_bwd(const avsr_rnn_stack* st, int32_t n, void* stream) {
   using namespace avsr;
   if (!st || n <= 0 || n > AVSR_MAX_STACKS) return AVSR_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  int nsteps = 0, ntask_max = 0;
+  const int nsteps = wavefront_steps(st, n);
   for (int i = 0; i < n; ++i) {
     const avsr_rnn_stack& S = st[i];
     if ((S.cell != 0 && S.cell != 1) || S.cell != st[0].cell) return AVSR_ERR_UNSUPPORTED;
@@ -220,10 +238,8 @@ extern "C" int avsr_rnn_bwd(const avsr_rnn_stack* st, int32_t n, void* stream) {
         }
       }
     }
-    nsteps = nsteps > S.T + S.n_layers - 1 ? nsteps : S.T + S.n_layers - 1;
-    ntask_max += S.n_layers;
   }
-  if (ntask_max > STEP_MAX_TASKS) return AVSR_ERR_UNSUPPORTED;
+  if (wavefront_tasks(st, n) > STEP_MAX_TASKS) return AVSR_ERR_UNSUPPORTED;
   {
     int rc = AVSR_ERR_UNSUPPORTED;                                            // one launch for the whole BPTT when it fits:
     rc = run_persistent(avsr_rnn_bwd_persistent, st, n, stream);
@@ -321,4 +337,32 @@ extern "C" int avsr_rnn_bwd(const avsr_rnn_stack* st, int32_t n, void* stream) {
    }
   }
   return AVSR_OK;
+}
+
+// What a call would launch (avsr_hip.h): run_persistent's dry path under the asked-for mode and scratch sizes, with this thread's recorder
+// set.  The scratch addresses are dummies that nothing dereferences (the dry paths only offset them).
+extern "C" int avsr_rnn_plan(const avsr_rnn_stack* st, int32_t n, int32_t bwd, int32_t mode, int64_t sync_ints, int64_t scratch_floats,
+                             avsr_rnn_launch* out, int32_t cap) {
+  using namespace avsr;
+  if (!st || n <= 0 || n > AVSR_MAX_STACKS || cap < 0 || (cap > 0 && !out) || sync_ints < 0 || scratch_floats < 0) return AVSR_ERR_ARG;
+  for (int i = 0; i < n; ++i)
+    if (st[i].n_layers <= 0 || st[i].n_layers > AVSR_MAX_LAYERS || st[i].B <= 0 || st[i].T <= 0) return AVSR_ERR_ARG;
+  static int32_t dummy_sync[1];
+  static float dummy_scratch[1];
+  int32_t* const sync0 = g_sync; const int64_t ints0 = g_sync_ints; const int mode0 = g_persist_mode;
+  float* const scr0 = g_persist_scratch; const int64_t floats0 = g_persist_scratch_floats;
+  g_sync = sync_ints ? dummy_sync : nullptr; g_sync_ints = sync_ints; g_persist_mode = mode;
+  g_persist_scratch = scratch_floats ? dummy_scratch : nullptr; g_persist_scratch_floats = scratch_floats;
+  RnnPlanRec R = {out, cap, 0};
+  g_rnn_plan = &R;
+  const int rc = run_persistent(bwd ? avsr_rnn_bwd_persistent : avsr_rnn_fwd_persistent, st, n, nullptr, 1);
+  g_rnn_plan = nullptr;
+  g_sync = sync0; g_sync_ints = ints0; g_persist_mode = mode0; g_persist_scratch = scr0; g_persist_scratch_floats = floats0;
+  // avsr_rnn_bwd sizes its per-step launch before it tries the persistent forms, avsr_rnn_fwd only when it needs it
+  if ((bwd || rc == AVSR_ERR_UNSUPPORTED) && wavefront_tasks(st, n) > STEP_MAX_TASKS) return AVSR_ERR_UNSUPPORTED;
+  if (rc == AVSR_ERR_UNSUPPORTED) {
+    if (cap > 0) out[0] = avsr_rnn_launch{AVSR_RNN_FORM_PER_STEP, n, 0, 0, wavefront_steps(st, n) * (st[0].cell == 1 ? 2 : 1), 0, 0, 0};
+    return 1;
+  }
+  return rc < 0 ? rc : R.n;
 }

@@ -745,20 +745,23 @@ int avsr_rnn_fwd_persistent(const avsr_rnn_stack* st, int32_t n, void* stream, i
   hipStream_t s = (hipStream_t)stream;
   int wg = 0; long words = 0;
   if ((g_persist_mode & 2) && build_tasks(st, n, true, sync, sync_ints, L, &wg, &words) == AVSR_OK) {
-    if (dry) return AVSR_OK;
     // 8 XCDs x R rows per launch (R = 8 up to 64 utterances, 16 above); a larger batch runs as consecutive launches over slices
     // (rows are independent)
     const int B = st[0].B;
     const int R = B > 64 ? 16 : 8;
+    // 8-row groups at H = 256 everywhere: recurrent product on the 4x4x1 MFMA with A-block broadcast (no padding rows)
+    bool q4 = R == 8;
+    for (int i = 0; i < L.ntask && q4; ++i) q4 = L.task[i].H == 256 && (L.task[i].hoisted ? L.task[i].uw == 16 : (L.task[i].uw == 8 && L.task[i].in == 256));
+    if (dry) {
+      rnn_plan_note(R == 16 ? AVSR_RNN_FORM_FWD_XCD16 : q4 ? AVSR_RNN_FORM_FWD_XCD8_Q4 : AVSR_RNN_FORM_FWD_XCD8, n, R, 8 * R, B, wg);
+      return AVSR_OK;
+    }
     for (int b0 = 0; b0 < B; b0 += 8 * R) {
       const int rows = B - b0 < 8 * R ? B - b0 : 8 * R;
       L.b0 = b0; L.ngroups = (rows + R - 1) / R;
       if (avsr::dev_zero(sync + P_HDR, sizeof(int32_t) * (words - P_HDR), s) != hipSuccess) return AVSR_ERR_HIP;
       {
         ProfScope ps(PROF_RNN_PERSIST_FWD, s, g_fwd_flops * rows / B);
-        // 8-row groups at H = 256 everywhere: recurrent product on the 4x4x1 MFMA with A-block broadcast (no padding rows)
-        bool q4 = R == 8;
-        for (int i = 0; i < L.ntask && q4; ++i) q4 = L.task[i].H == 256 && (L.task[i].hoisted ? L.task[i].uw == 16 : (L.task[i].uw == 8 && L.task[i].in == 256));
         if (R == 16) hipLaunchKernelGGL(rnn_persist_fwd_xcd_kernel<16>, dim3(8 * wg), dim3(256), 0, s, L);
         else if (q4) hipLaunchKernelGGL((rnn_persist_fwd_xcd_kernel<8, true>), dim3(8 * wg), dim3(256), 0, s, L);
         else hipLaunchKernelGGL(rnn_persist_fwd_xcd_kernel<8>, dim3(8 * wg), dim3(256), 0, s, L);
@@ -770,8 +773,8 @@ int avsr_rnn_fwd_persistent(const avsr_rnn_stack* st, int32_t n, void* stream, i
   // two stacks that do not fit one XCD together (the directions of a bidirectional encoder), <= 64 utterances: one launch, each
   // stack on four XCDs in 16-row groups -- the directions run side by side instead of one after the other
   if ((g_persist_mode & 2) && build_tasks(st, n, true, sync, sync_ints, L, &wg, &words, true) == AVSR_OK) {
-    if (dry) return AVSR_OK;
     const int B = st[0].B;
+    if (dry) { rnn_plan_note(AVSR_RNN_FORM_FWD_PARTS, n, 16, 64, B, wg); return AVSR_OK; }
     L.b0 = 0; L.ngroups = (B + 15) / 16;
     if (avsr::dev_zero(sync + P_HDR, sizeof(int32_t) * (words - P_HDR), s) != hipSuccess) return AVSR_ERR_HIP;
     {
@@ -782,7 +785,7 @@ int avsr_rnn_fwd_persistent(const avsr_rnn_stack* st, int32_t n, void* stream, i
     return AVSR_OK;
   }
   if ((g_persist_mode & 1) && build_tasks(st, n, false, sync, sync_ints, L, &wg, &words) == AVSR_OK) {
-    if (dry) return AVSR_OK;
+    if (dry) { rnn_plan_note(AVSR_RNN_FORM_FWD_AGENT, n, 16, st[0].B, st[0].B, wg); return AVSR_OK; }
     if (avsr::dev_zero(sync + P_HDR, sizeof(int32_t) * (words - P_HDR), s) != hipSuccess) return AVSR_ERR_HIP;
     {
       ProfScope ps(PROF_RNN_PERSIST_FWD, s, g_fwd_flops);

@@ -774,11 +774,17 @@ static int bwd_persistent(const avsr_rnn_stack* st, int32_t n, void* stream, int
     }
   }
   if (words > sync_ints) UNSUP(10);
-  if (dry) return AVSR_OK;
-  L.err = sync; L.claim = sync + P_HDR; L.wpx0 = slots[0]; L.wpx1 = slots[1]; L.solo = solo ? 1 : 0;
   const int slice = solo ? 128 : 64;
-  hipStream_t s = (hipStream_t)stream;
   const int wpx = slots[0] > slots[1] ? slots[0] : slots[1];
+  if (dry) {
+    int crossing = 0, tiles = 1;
+    for (int i = 0; i < L.ntask; ++i) { crossing += L.task[i].up_remote; if (L.task[i].ntile > tiles) tiles = L.task[i].ntile; }
+    rnn_plan_note(!ksplit ? AVSR_RNN_FORM_BWD_UNIT : solo ? AVSR_RNN_FORM_BWD_KSPLIT_SOLO : AVSR_RNN_FORM_BWD_KSPLIT, n, 16, slice, B, wpx, crossing,
+                  ksplit ? 0 : tiles);
+    return AVSR_OK;
+  }
+  L.err = sync; L.claim = sync + P_HDR; L.wpx0 = slots[0]; L.wpx1 = slots[1]; L.solo = solo ? 1 : 0;
+  hipStream_t s = (hipStream_t)stream;
   for (int b0 = 0; b0 < B; b0 += slice) {              // rows are independent: consecutive launches over 64-row (solo: 128-row) slices
     const int rows = B - b0 < slice ? B - b0 : slice;
     L.b0 = b0; L.ngroups = (rows + 15) / 16;

@@ -154,6 +154,29 @@ def rnn_bwd(stacks):
     check(_L().avsr_rnn_bwd(arr, len(stacks), _s()), "avsr_rnn_bwd")
 
 
+RNN_FORMS = ("per_step", "fwd_xcd8", "fwd_xcd8_q4", "fwd_xcd16", "fwd_parts", "fwd_agent", "bwd_ksplit", "bwd_ksplit_solo", "bwd_unit")
+
+
+def rnn_plan(stacks, bwd=False, mode=3, sync_ints=1 << 20, scratch_floats=64 << 20):
+    """avsr_rnn_plan: what rnn_fwd / rnn_bwd (bwd=True) would launch for these RnnStack descriptors under rnn_set_persistent(True, mode=mode)
+    with these scratch sizes (sync_ints=0: persistent execution off), decided by the library's host code without touching HIP (no GPU
+    needed; descriptor pointers are only tested for NULL).  A list of dicts with the fields of avsr_rnn_launch, `form` as its RNN_FORMS
+    name: one when all stacks share the launches, else one per stack."""
+    from ._lib import RnnLaunch
+    arr = (RnnStack * len(stacks))(*stacks)
+    out = (RnnLaunch * MAX_STACKS_PLAN)()
+    n = _L().avsr_rnn_plan(arr, len(stacks), int(bool(bwd)), int(mode), int(sync_ints), int(scratch_floats), out, MAX_STACKS_PLAN)
+    if n < 0:
+        check(n, "avsr_rnn_plan")
+    recs = [{f: getattr(out[i], f) for f, _ in RnnLaunch._fields_} for i in range(n)]
+    for r in recs:
+        r["form"] = RNN_FORMS[r["form"]]
+    return recs
+
+
+MAX_STACKS_PLAN = 4       # AVSR_MAX_STACKS
+
+
 def attn_rnn_fwd(desc, l_begin, l_end):
     check(_L().avsr_attn_rnn_fwd(C.byref(desc), int(l_begin), int(l_end), _s()), "avsr_attn_rnn_fwd")
 

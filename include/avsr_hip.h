@@ -170,8 +170,18 @@ int avsr_rnn_bwd(const avsr_rnn_stack* stacks, int32_t n_stacks, void* stream);
  * weights and (c, h) state stay in registers, steps are ordered by device-side arrival counters instead of
  * launch boundaries.  `sync` = caller-owned int32 device scratch of `ints` words: word 0 is a sticky error flag
  * (a bounded wait expired; zero it before installing, read it back to check), the rest are counters
- * (needs 1 + sum over layers of ceil(B/16)*T).  NULL disables.  Configurations that do not fit (GRU,
- * units %% 8, in+units > 512, > 512 workgroups) silently use the per-step launches.  Same results either way. */
+ * (264 header words, then per layer 256 progress words for the XCD-local kernels or ceil(B/16)*T arrival counters for the
+ * agent-scope forward; a BPTT task whose output crosses an XCD pair adds groups*T more).  NULL disables.  What does not fit
+ * silently uses the next form, in the end the per-step launches; same results either way.  A call goes per-step as a whole when
+ * any stack is a GRU, has a ResidualWrapper'd layer, or the stacks differ in B.  Forward, per layer: units % 8 == 0, units <= 256,
+ * in_dim % 4 == 0, in_dim <= 256 unless hoisted, layer 0 hoisted, `out` given, B*(T+2)*max(ld_out, 4*units) < 2^29, with dropout
+ * hs_seq given (and the lower layer's xt_seq); at most 8 layers in a launch, and 96 workgroups per XCD (units/16 for a hoisted layer
+ * of units % 16 == 0, else units/8) for the XCD-local kernels, 512 workgroups in all (ceil(B/16) * units/8 per layer) for the
+ * agent-scope kernel.  Two stacks that pass all but the 96 together run side by side on XCD halves when each has <= 96 and B <= 64.
+ * BPTT, per layer: units % 16 == 0, units <= 256, the layer above takes in_dim == units, B*T*units*4 < 2^29; at most 12 tasks in a
+ * launch (K-split: one per layer and one helper per layer edge) and, after the cells are divided over the two XCDs of a pair, 64
+ * workgroups (units/16 per task) per XCD for the K-split kernel, which also needs its float scratch, or 28 (units/16, units/32 for a
+ * top layer of units % 32 == 0) for the unit-partitioned one.  avsr_rnn_plan answers which form a call would take. */
 int avsr_rnn_set_persistent(int32_t* sync, int64_t ints);
 /* Which persistent kernels may be used: bit 0 = agent-scope (any placement, 16-row tiles), bit 1 = XCD-local
  * (8-row groups bound to the XCD their workgroups actually run on; tried first) and the persistent BPTT,
@@ -181,6 +191,36 @@ int avsr_rnn_set_persistent_mode(int mode);
  * [B,T,units] operand per encoder cell that has a layer above it.  NULL / too small: that form is skipped (the unit-partitioned
  * BPTT or the per-step launches run instead). */
 int avsr_rnn_set_persistent_scratch(float* scratch, int64_t floats);
+/* Read-only plan query: what avsr_rnn_fwd (bwd == 0) or avsr_rnn_bwd (bwd == 1) WOULD launch for these stacks if `mode` were the
+ * avsr_rnn_set_persistent_mode bits, a sync scratch of `sync_ints` words (0 = none) and a K-split float scratch of `scratch_floats`
+ * (0 = none) were installed.  Decided by the same host code on its dry path: the descriptors' pointers are only tested for NULL, never
+ * dereferenced, nothing is launched and no HIP call is made (runs without a GPU); the installed scratch and mode are left as they
+ * were.  Not to be called while another thread is inside avsr_rnn_fwd / avsr_rnn_bwd.  Writes up to `cap` records and returns their
+ * number: 1 when all stacks share the launches (and for the per-step form), n_stacks when every stack gets launches of its own; or
+ * AVSR_ERR_ARG, or AVSR_ERR_UNSUPPORTED where the call itself would return it (more than 8 layers in all for the per-step form).
+ *   form            AVSR_RNN_FORM_*
+ *   stacks          stacks covered by this record
+ *   rows_per_group  batch rows of a group (forward: per XCD, 8 or 16; agent-scope: per 16-row tile; BPTT: 16 per XCD pair / XCD)
+ *   rows_per_slice  batch rows of one launch (0 per-step)
+ *   launches        kernel launches: ceil(B / rows_per_slice); per-step: wavefront steps x phases
+ *   wg_per_xcd      workgroup slots per XCD (the larger half; agent-scope: workgroups of the launch; 0 per-step)
+ *   crossing_edges  BPTT: layer edges that cross the XCD pair
+ *   top_tiles       unit-partitioned BPTT: 16-unit tiles per workgroup of a top layer (2 if any top layer takes two) */
+#define AVSR_RNN_FORM_PER_STEP 0          /* one launch per wavefront step (csrc/step.hip) */
+#define AVSR_RNN_FORM_FWD_XCD8 1          /* rnn_persist_fwd_xcd_kernel<8> */
+#define AVSR_RNN_FORM_FWD_XCD8_Q4 2       /* rnn_persist_fwd_xcd_kernel<8, true>: every layer 256 wide */
+#define AVSR_RNN_FORM_FWD_XCD16 3         /* rnn_persist_fwd_xcd_kernel<16>: B > 64, 128-row slices */
+#define AVSR_RNN_FORM_FWD_PARTS 4         /* rnn_persist_fwd_xcd_kernel<16>, two stacks on XCD halves */
+#define AVSR_RNN_FORM_FWD_AGENT 5         /* rnn_persist_fwd_kernel (agent scope) */
+#define AVSR_RNN_FORM_BWD_KSPLIT 6        /* rnn_persist_bwdk_kernel, a group per XCD pair, 64-row slices */
+#define AVSR_RNN_FORM_BWD_KSPLIT_SOLO 7   /* rnn_persist_bwdk_kernel, a group per XCD, 128-row slices */
+#define AVSR_RNN_FORM_BWD_UNIT 8          /* rnn_persist_bwd_kernel (unit-partitioned), 64-row slices */
+typedef struct avsr_rnn_launch {
+  int32_t form, stacks, rows_per_group, rows_per_slice;
+  int32_t launches, wg_per_xcd, crossing_edges, top_tiles;
+} avsr_rnn_launch;
+int avsr_rnn_plan(const avsr_rnn_stack* stacks, int32_t n_stacks, int32_t bwd, int32_t mode, int64_t sync_ints, int64_t scratch_floats,
+                  avsr_rnn_launch* out, int32_t cap);
 
 /* ---------------------------------------------------------------------------------------------
  * Attention-wrapped LSTM over a sequence.  Replaces
