@@ -168,6 +168,16 @@ class CtcPrefixArgs(C.Structure):
                [(n, C.c_void_p) for n in ("z", "in_len", "ids", "lens", "score", "trace_parent", "trace_sym", "trace_pb", "trace_pnb")]
 
 
+CTC_PREFIX_LM_MAX_W = 16               # AVSR_CTC_PREFIX_LM_MAX_W of include/avsr_hip.h
+
+
+class CtcPrefixLm(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_layers", "H", "E", "V", "one_hot", "go_id", "eos_id")] + \
+               [("weight", C.c_float), ("bonus", C.c_float), ("pad_", C.c_int32), ("embedding", C.c_void_p),
+                ("wt", C.c_void_p * MAX_LM_LAYERS), ("bias", C.c_void_p * MAX_LM_LAYERS), ("wout_t", C.c_void_p), ("bout", C.c_void_p),
+                ("ws", C.c_void_p), ("ws_bytes", C.c_int64), ("s_lm", C.c_void_p), ("lm_steps", C.c_void_p), ("lm_logp", C.c_void_p)]
+
+
 CTC_ALIGN_MAX_L = 512                  # AVSR_CTC_ALIGN_MAX_L of include/avsr_hip.h
 
 
@@ -189,6 +199,7 @@ _STRUCTS = {"avsr_dec_layer": DecLayer, "avsr_mat": Mat, "avsr_gemm_desc": GemmD
             "avsr_rnn_launch": RnnLaunch,
             "avsr_conv_desc": ConvDesc, "avsr_conv_launch": ConvLaunch, "avsr_conv3d_desc": Conv3dDesc, "avsr_logmel_args": LogmelArgs, "avsr_ctc_args": CtcArgs, "avsr_attn_mech": AttnMech, "avsr_attn_rnn": AttnRnn, "avsr_transpose_job": TransposeJob,
             "avsr_colsum_job": ColsumJob, "avsr_beam_lm": BeamLm, "avsr_beam_ctc": BeamCtc, "avsr_ctc_prefix_args": CtcPrefixArgs,
+            "avsr_ctc_prefix_lm": CtcPrefixLm,
             "avsr_ctc_align_args": CtcAlignArgs}
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -236,6 +247,8 @@ _SIGS = {
     "avsr_ctc_best_path": [_vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp],
     "avsr_ctc_prefix_search_supported": [_i32, _i32, _i32],
     "avsr_ctc_prefix_search": [C.POINTER(CtcPrefixArgs), _vp],
+    "avsr_ctc_prefix_lm_supported": [_i32, _i32, _i32, _i32, _i32, _i32, _i32],
+    "avsr_ctc_prefix_search_lm": [C.POINTER(CtcPrefixArgs), C.POINTER(CtcPrefixLm), _vp],
     "avsr_ctc_align_supported": [_i32, _i32],
     "avsr_ctc_align": [C.POINTER(CtcAlignArgs), _vp],
     "avsr_seq_logprob": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp],
@@ -308,9 +321,9 @@ _SIGS = {
     "avsr_prof_begin": [_i32],
     "avsr_prof_end": [C.POINTER(_i32), C.POINTER(_f32), C.POINTER(C.c_double)],
 }
-# every symbol the library must export: the table above plus the six whose return type load() sets on its own
+# every symbol the library must export: the table above plus the seven whose return type load() sets on its own
 EXPORTS = ["avsr_abi_version", "avsr_sizeof", "avsr_attn_rnn_fused_ws_floats", "avsr_conv3d_wgrad_scratch_floats", "avsr_ctc_ws_floats",
-           "avsr_ctc_align_ws_bytes"] + list(_SIGS)
+           "avsr_ctc_align_ws_bytes", "avsr_ctc_prefix_lm_ws_bytes"] + list(_SIGS)
 
 _lib = None
 
@@ -351,6 +364,8 @@ def load():
     lib.avsr_ctc_ws_floats.restype = C.c_int64
     lib.avsr_ctc_align_ws_bytes.argtypes = [_i32, _i32, _i32]
     lib.avsr_ctc_align_ws_bytes.restype = C.c_int64
+    lib.avsr_ctc_prefix_lm_ws_bytes.argtypes = [_i32, _i32, _i32, _i32]
+    lib.avsr_ctc_prefix_lm_ws_bytes.restype = C.c_int64
     for name, st in _STRUCTS.items():
         n = lib.avsr_sizeof(name.encode())
         if n != C.sizeof(st):

@@ -32,6 +32,11 @@ beam search then adds ctc_decode_weight * (CTC prefix score of the continuation 
 (joint CTC / attention decoding, csrc/beam_ctc.hip); it works together with `lm_checkpoint`.
 `decoding_algorithm='ctc_prefix_beam_search'` (a `use_ctc` model; not in the reference) makes `evaluate` take its predictions from a CTC
 prefix beam search of width `beam_width` on that head alone -- no decoder step (csrc/ctc_prefix.hip).
+`ctc_lm_checkpoint` (a checkpoint written by `LM.train`; the model's shape through `lm_units_per_layer` / `lm_embedding_size` /
+`lm_cell_type`), `ctc_lm_weight` (0.3: a conventional value, not a tuned one) and `ctc_lm_length_bonus` (0.0) arrive through **kwargs and
+fuse that language model INTO this search: an extension by c also gets ctc_lm_weight * log p_lm(c | labels) + ctc_lm_length_bonus, and the
+final beam is re-sorted with ctc_lm_weight * log p_lm(EOS | labels) added (csrc/ctc_prefix_lm.hip; beam widths
+of up to 16).  `lm_checkpoint` itself stays a 'beam_search' option.
 `decoding_algorithm='attention_rescoring'` (a `use_ctc` model; not in the reference) is the two-pass decode: that search's n-best, every
 hypothesis scored by the attention decoder teacher-forced, the best of log p_att + ctc_decode_weight * log p_ctc kept -- no step-by-step
 decode (csrc/rescore.hip).  No language-model term, no length normalisation.
@@ -179,6 +184,28 @@ class AVSR(object):
                                        kwargs.get('lm_cell_type', 'lstm'))
             lm_weights = _lm.checkpoint_weights(lm_cfg, lm_checkpoint)
 
+        # language model fused into the CTC prefix search (csrc/ctc_prefix_lm.hip): its own keywords, refused on the host like lm_checkpoint
+        self._ctc_lm = None
+        self._ctc_lm_weight, self._ctc_lm_bonus = float(kwargs.get('ctc_lm_weight', 0.3)), float(kwargs.get('ctc_lm_length_bonus', 0.0))
+        if not self._ctc_lm_weight >= 0.0 or self._ctc_lm_weight == float('inf'):
+            raise ValueError("ctc_lm_weight must be a finite number >= 0 (got %r)" % (kwargs.get('ctc_lm_weight'),))
+        if self._ctc_lm_bonus != self._ctc_lm_bonus or abs(self._ctc_lm_bonus) == float('inf'):
+            raise ValueError("ctc_lm_length_bonus must be finite (got %r)" % (kwargs.get('ctc_lm_length_bonus'),))
+        ctc_lm_checkpoint, ctc_lm_cfg, ctc_lm_weights = kwargs.get('ctc_lm_checkpoint'), None, None
+        if ctc_lm_checkpoint is not None:
+            from . import lm as _lm
+            from ._lib import CTC_PREFIX_LM_MAX_W, MAX_LM_LAYERS
+            if decoding_algorithm != 'ctc_prefix_beam_search':
+                raise ValueError("ctc_lm_checkpoint needs decoding_algorithm='ctc_prefix_beam_search': the model is fused into the CTC "
+                                 "head's own search (beam search takes lm_checkpoint; 'attention_rescoring' takes no language model)")
+            ctc_lm_cfg = _lm.fusion_config(self._unit_dict, kwargs.get('lm_units_per_layer', (256,)), kwargs.get('lm_embedding_size', 128),
+                                           kwargs.get('lm_cell_type', 'lstm'))
+            if beam_width > CTC_PREFIX_LM_MAX_W or len(ctc_lm_cfg.decoder_units) > MAX_LM_LAYERS:
+                raise ValueError("ctc_lm_checkpoint: avsr_ctc_prefix_lm_supported covers beam widths of up to %d and language models of up "
+                                 "to %d layers (got beam_width %d, %d layers)"
+                                 % (CTC_PREFIX_LM_MAX_W, MAX_LM_LAYERS, beam_width, len(ctc_lm_cfg.decoder_units)))
+            ctc_lm_weights = _lm.checkpoint_weights(ctc_lm_cfg, ctc_lm_checkpoint)
+
         # joint CTC / attention scoring in beam search: an evaluate-time weight, held like _lm_weight; 0 = off, nothing new is launched
         self._ctc_decode_weight = float(kwargs.get('ctc_decode_weight', 0.0))
         if not self._ctc_decode_weight >= 0.0 or self._ctc_decode_weight == float('inf'):
@@ -240,6 +267,8 @@ class AVSR(object):
         self._model = Seq2SeqModel(self._cfg, seed=kwargs.get('seed', 0))
         if lm_cfg is not None:
             self._lm = _lm.load_fusion_engine(lm_cfg, lm_weights)
+        if ctc_lm_cfg is not None:
+            self._ctc_lm = _lm.load_fusion_engine(ctc_lm_cfg, ctc_lm_weights)
         self._shuffle_seed = kwargs.get('shuffle_seed')        # None = a fresh order every run, as tf.data's unseeded shuffle(5000)
         # Data parallelism (the reference's num_gpus is deprecated and ignored, avsr/avsr.py:67,:127): when the process was started
         # under torch.distributed (one process per GPU, `torchrun`), every rank builds the same model, reads the same records,
@@ -488,7 +517,8 @@ class AVSR(object):
             ids = self._model.attention_rescoring(batch, beam_width=self._beam_width, max_steps=self._cfg.max_label_length,
                                                   ctc_weight=self._ctc_decode_weight)
         elif self._decoding_algorithm == 'ctc_prefix_beam_search':     # the head's own search: the attention decoder never runs
-            ids = self._model.ctc_prefix_beam_search(batch, beam_width=self._beam_width, max_steps=self._cfg.max_label_length)
+            ids = self._model.ctc_prefix_beam_search(batch, beam_width=self._beam_width, max_steps=self._cfg.max_label_length,
+                                                     lm=self._ctc_lm, lm_weight=self._ctc_lm_weight, length_bonus=self._ctc_lm_bonus)
         else:
             ids = self._model.greedy_decode(batch, max_steps=self._cfg.max_label_length)
         if not isinstance(ids, list):

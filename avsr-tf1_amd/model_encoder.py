@@ -8,7 +8,7 @@ import os
 import numpy as np
 import torch
 from . import ops, params as PR
-from ._lib import AttnRnn, CTC_ALIGN_MAX_L, CTC_PREFIX_MAX_L, CTC_PREFIX_MAX_V, CTC_PREFIX_MAX_W, RnnStack
+from ._lib import AttnRnn, CTC_ALIGN_MAX_L, CTC_PREFIX_LM_MAX_W, CTC_PREFIX_MAX_L, CTC_PREFIX_MAX_V, CTC_PREFIX_MAX_W, MAX_LM_LAYERS, RnnStack
 from .config import ATT_CODE, BAHDANAU_TYPES, CELL_ID_DECODER, LUONG_TYPES, ModelConfig, encoder_cell_id
 from .model_base import Batch, Ref, SeqBuf, _FlagReader, _PtrView, _splitk, desc_steplen  # noqa: F401
 
@@ -556,17 +556,21 @@ class EncoderMixin:
             out.append(dict(status=1, score=float(score[b]), path=[int(k) for k in path[b, :lens[b]]], segments=segs))
         return out
 
-    def ctc_prefix_beam_search(self, batch, beam_width=10, max_steps=None, nbest=False):
+    def ctc_prefix_beam_search(self, batch, beam_width=10, max_steps=None, nbest=False, lm=None, lm_weight=0.3, length_bonus=0.0):
         """use_ctc: CTC prefix beam search on the head alone (avsr_ctc_prefix_search, csrc/ctc_prefix.hip; the rule is INTEGRATION.md
         section 8) -- encoders in evaluation mode, the head, ONE launch for the batch; no decoder step.  max_steps bounds the label
         sequences (default: max_label_length).  One id list per utterance, the beam's best; nbest=True: per utterance the whole final
-        beam as (ids, score) pairs, best first, score = log p_ctc(ids | x) up to what pruning lost."""
-        out = self._ctc_prefix_beam_search(batch, beam_width, max_steps, nbest)
+        beam as (ids, score) pairs, best first, score = log p_ctc(ids | x) up to what pruning lost.
+        lm: a Seq2SeqModel with architecture='lm' (LSTM) over the same vocabulary -- the model's step runs inside the search's frame
+        loop (avsr_ctc_prefix_search_lm, csrc/ctc_prefix_lm.hip): an extension by c also gets lm_weight * log p_lm(c | labels) +
+        length_bonus, and the final beam is re-sorted by final = p + lm_weight * log p_lm(EOS | labels).  nbest=True then gives
+        (ids, final, s_lm) triples, s_lm = log p_lm(labels, EOS).  Without lm the plain kernel runs and nothing new is allocated."""
+        out = self._ctc_prefix_beam_search(batch, beam_width, max_steps, nbest, lm, lm_weight, length_bonus)
         if self.check_persistent():
-            out = self._ctc_prefix_beam_search(batch, beam_width, max_steps, nbest)
+            out = self._ctc_prefix_beam_search(batch, beam_width, max_steps, nbest, lm, lm_weight, length_bonus)
         return out
 
-    def _ctc_prefix_beam_search(self, batch, beam_width, max_steps, nbest):
+    def _ctc_prefix_beam_search(self, batch, beam_width, max_steps, nbest, lm=None, lm_weight=0.3, length_bonus=0.0):
         cfg, dev = self.cfg, self.dev
         if not cfg.use_ctc:
             raise ValueError("ctc_prefix_beam_search needs a model built with use_ctc=True")
@@ -578,6 +582,20 @@ class EncoderMixin:
             raise ValueError("ctc_prefix_beam_search: avsr_ctc_prefix_search covers vocabularies of up to %d symbols, beam widths of up to "
                              "%d and label sequences of up to %d (got %d, %d, %d)"
                              % (CTC_PREFIX_MAX_V, CTC_PREFIX_MAX_W, CTC_PREFIX_MAX_L, V, W, Lm))
+        if lm is not None:
+            self._check_lm(lm)
+            lm_weight, length_bonus = float(lm_weight), float(length_bonus)
+            if not lm_weight >= 0.0 or lm_weight == float("inf"):
+                raise ValueError("ctc_prefix_beam_search: lm_weight must be a finite number >= 0 (got %r)" % (lm_weight,))
+            if length_bonus != length_bonus or abs(length_bonus) == float("inf"):
+                raise ValueError("ctc_prefix_beam_search: length_bonus must be finite (got %r)" % (length_bonus,))
+            lc = lm.cfg
+            nl, H, El = len(lc.decoder_units), lc.decoder_units[0], lc.embedding_size
+            if not ops.ctc_prefix_lm_supported(V, W, Lm, nl, H, El, int(lm.onehot is not None)):
+                raise ValueError("ctc_prefix_beam_search: with a language model avsr_ctc_prefix_search_lm covers beam widths of up to %d "
+                                 "(vocabularies of up to %d symbols, label sequences of up to %d) and LSTM models of up to %d equal layers "
+                                 "(got beam width %d, %d symbols, %d labels, %d layers of %d units)"
+                                 % (CTC_PREFIX_LM_MAX_W, CTC_PREFIX_MAX_V, CTC_PREFIX_MAX_L, MAX_LM_LAYERS, W, V, Lm, nl, H))
         B = (batch.audio if batch.audio is not None else batch.video).shape[0]
         Ta = self._audio_rows(batch)
         Tv = batch.video.shape[1] if batch.video is not None else 0
@@ -590,12 +608,45 @@ class EncoderMixin:
             E[key] = (torch.zeros(B, W, Lm, dtype=torch.int32, device=dev), torch.zeros(B, W, dtype=torch.int32, device=dev),
                       torch.zeros(B, W, device=dev))
         ids, lens, score = E[key]
-        ops.ctc_prefix_search(E["ctc_z"], Cc, E["len"], B, E["T"], V, W, Lm, ids, lens, score)
+        if lm is None:
+            ops.ctc_prefix_search(E["ctc_z"], Cc, E["len"], B, E["T"], V, W, Lm, ids, lens, score)
+        else:
+            s_lm = self._ctc_prefix_lm_launch(E, Cc, B, V, W, Lm, ids, lens, score, lm, lm_weight, length_bonus).cpu().numpy()
         ids, lens, score = ids.cpu().numpy(), lens.cpu().numpy(), score.cpu().numpy()
         if not nbest:
             return [[int(s) for s in ids[b, 0, :lens[b, 0]]] for b in range(B)]
+        if lm is not None:
+            return [[([int(s) for s in ids[b, r, :lens[b, r]]], float(score[b, r]), float(s_lm[b, r])) for r in range(W)
+                     if score[b, r] > float("-inf")] for b in range(B)]
         return [[([int(s) for s in ids[b, r, :lens[b, r]]], float(score[b, r])) for r in range(W) if score[b, r] > float("-inf")]
                 for b in range(B)]
+
+    def _ctc_prefix_lm_launch(self, E, Cc, B, V, W, Lm, ids, lens, score, lm, lm_weight, length_bonus):
+        """avsr_ctc_prefix_search_lm over the language model's own (4-padded) weights; the state workspace, s_lm and lm_steps are
+        cached next to the ("ctc_prefix", W, Lm) buffers, keyed by the model's shape.  Returns s_lm [B, W] (device)."""
+        from ._lib import CtcPrefixLm
+        lc, dev = lm.cfg, self.dev
+        nl, H = len(lc.decoder_units), lc.decoder_units[0]
+        lm._refresh_derived()
+        key = ("ctc_prefix_lm", W, Lm, nl, H)
+        if key not in E:
+            E[key] = dict(ws=torch.zeros(ops.ctc_prefix_lm_ws_bytes(B, W, nl, H) // 4, device=dev), s_lm=torch.zeros(B, W, device=dev),
+                          steps=torch.zeros(B, dtype=torch.int32, device=dev))
+        buf = E[key]
+        m = CtcPrefixLm()
+        m.n_layers, m.H, m.E, m.V, m.one_hot = nl, H, lc.embedding_size, V, int(lm.onehot is not None)
+        m.go_id, m.eos_id, m.weight, m.bonus = lc.go_id, lc.eos_id, lm_weight, length_bonus
+        m.embedding = ops.fptr(*lm._emb())
+        for j in range(nl):
+            m.wt[j] = ops.fptr(lm.derived, lm.Tr["dec/l%d/kernel" % j].off)
+            m.bias[j] = ops.fptr(lm.params, lm.P["dec/l%d/bias" % j].off)
+        m.wout_t = ops.fptr(lm.derived, lm.Tr["dec/out/kernel"].off)
+        m.bout = ops.fptr(lm.params, lm.P["dec/out/bias"].off)
+        m.ws, m.ws_bytes = ops.fptr(buf["ws"]), buf["ws"].numel() * 4
+        m.s_lm, m.lm_steps = ops.fptr(buf["s_lm"]), ops.fptr(buf["steps"])
+        ops.ctc_prefix_search_lm(E["ctc_z"], Cc, E["len"], B, E["T"], V, W, Lm, ids, lens, score, m)
+        self._last_ctc_lm_steps = buf["steps"]
+        return buf["s_lm"]
 
     def persistent_flagged(self):
         """Read-only form of check_persistent(): did a persistent kernel flag the last pass on THIS rank?"""

@@ -426,6 +426,27 @@ def ctc_prefix_search(z, ld, in_len, B, T, V, beam_width, L_max, ids, lens, scor
     check(_L().avsr_ctc_prefix_search(C.byref(a), _s()), "avsr_ctc_prefix_search")
 
 
+def ctc_prefix_lm_supported(V, beam_width, L_max, n_layers, H, E, one_hot):
+    """Host-side: does avsr_ctc_prefix_search_lm run this search shape with this language-model shape?"""
+    return bool(_L().avsr_ctc_prefix_lm_supported(int(V), int(beam_width), int(L_max), int(n_layers), int(H), int(E), int(one_hot)))
+
+
+def ctc_prefix_lm_ws_bytes(B, beam_width, n_layers, H):
+    return int(_L().avsr_ctc_prefix_lm_ws_bytes(int(B), int(beam_width), int(n_layers), int(H)))
+
+
+def ctc_prefix_search_lm(z, ld, in_len, B, T, V, beam_width, L_max, ids, lens, score, lm, trace=None):
+    """avsr_ctc_prefix_search_lm: ctc_prefix_search with the language-model term of the descriptor lm (a _lib.CtcPrefixLm with its
+    weights, workspace and the outputs s_lm [B, W], lm_steps [B] and, optionally, lm_logp [B, W, V] set).  score holds final."""
+    from ._lib import CtcPrefixArgs
+    a = CtcPrefixArgs()
+    a.B, a.T, a.V, a.beam_width, a.L_max, a.ld = int(B), int(T), int(V), int(beam_width), int(L_max), int(ld)
+    a.z, a.in_len, a.ids, a.lens, a.score = fptr(z), fptr(in_len), fptr(ids), fptr(lens), fptr(score)
+    if trace is not None:
+        a.trace_parent, a.trace_sym, a.trace_pb, a.trace_pnb = (fptr(t) for t in trace)
+    check(_L().avsr_ctc_prefix_search_lm(C.byref(a), C.byref(lm), _s()), "avsr_ctc_prefix_search_lm")
+
+
 def ctc_align_supported(V, L):
     """Host-side: does avsr_ctc_align run this shape (include/avsr_hip.h AVSR_CTC_ALIGN_MAX_L)?"""
     return bool(_L().avsr_ctc_align_supported(int(V), int(L)))

@@ -573,6 +573,46 @@ int avsr_ctc_prefix_search_supported(int32_t V, int32_t beam_width, int32_t L_ma
 /* AVSR_ERR_ARG for a NULL / non-positive / inconsistent argument, AVSR_ERR_UNSUPPORTED outside the limits: both before any launch. */
 int avsr_ctc_prefix_search(const avsr_ctc_prefix_args* a, void* stream);
 
+/* The prefix search with a language model fused into the frame loop (csrc/ctc_prefix_lm.hip; the rule is INTEGRATION.md section 8):
+ *   extend g by c < V:   next[g.c].p_nb (+)= (p_b if c == last(g) else p) + y[t][c] + (weight * lam(c | g) + bonus)
+ *   after the last frame final[g] = p + weight * lam(EOS | g), and the beam is re-sorted by final (descending, ties to the earlier slot)
+ * lam(. | g) = log_softmax of avsr.LM's evaluate graph (avsr_beam_lm's model and buffer layouts: embedding [V][E], wt[j] [4H][K_j],
+ * bias[j] [H][4], wout_t [V][H], bout [V]) after GO, g_0 .. g_{n-1} from the zero state.  Stays, merging, candidate indices, selection
+ * on p and ties are avsr_ctc_prefix_search's; weight == 0 and bonus == 0 give its ids, lens and score.  Every one of the V classes, GO
+ * and EOS included, gets its term.  a->score holds final; the trace (a->trace_*) is the per-frame beam, before the final re-sort.
+ *   s_lm [B][beam_width]        sum_i lam(g_i | g_0 .. g_{i-1}) + lam(EOS | g) of the entry at that output position (0 for an empty slot)
+ *   lm_steps [B]                number of frames on which the model's step ran (the frames that kept an extension)
+ *   lm_logp [B][beam_width][V]  NULL, or (debug) the row lam(. | g) of every output entry (0 for an empty slot)
+ *   ws                          avsr_ctc_prefix_lm_ws_bytes(B, beam_width, n_layers, H) bytes, 16-byte aligned: (c, h) of 2 beam_width
+ *                               label sequences per utterance; written before it is read, so it needs no initial value
+ * One launch, one workgroup per utterance, no atomics: bit-identical across launches.  The model's step runs inside the frame loop.
+ * Limits: avsr_ctc_prefix_search's on V and L_max, 1 <= beam_width <= AVSR_CTC_PREFIX_LM_MAX_W (the kept extensions of a frame are ONE
+ * 16-row MFMA tile), V == lm->V, 0 <= go_id, eos_id < V, and a model avsr_beam_lm_supported accepts: 1 <= n_layers <= AVSR_MAX_LM_LAYERS,
+ * H % 4 == 0, E % 4 == 0 (one_hot != 0: E >= V).  weight finite and >= 0, bonus finite. */
+#define AVSR_CTC_PREFIX_LM_MAX_W 16
+typedef struct avsr_ctc_prefix_lm {
+  int32_t n_layers, H, E, V;
+  int32_t one_hot, go_id, eos_id;
+  float weight, bonus;
+  int32_t pad_;
+  const float* embedding;
+  const float* wt[AVSR_MAX_LM_LAYERS];
+  const float* bias[AVSR_MAX_LM_LAYERS];
+  const float* wout_t;
+  const float* bout;
+  void* ws;
+  int64_t ws_bytes;
+  float* s_lm;
+  int32_t* lm_steps;
+  float* lm_logp;
+} avsr_ctc_prefix_lm;
+/* 1 if avsr_ctc_prefix_search_lm runs this shape, else 0 (decided on the host; nothing is dereferenced). */
+int avsr_ctc_prefix_lm_supported(int32_t V, int32_t beam_width, int32_t L_max, int32_t n_layers, int32_t H, int32_t E, int32_t one_hot);
+/* Bytes of avsr_ctc_prefix_lm.ws (0 for a non-positive argument). */
+int64_t avsr_ctc_prefix_lm_ws_bytes(int32_t B, int32_t beam_width, int32_t n_layers, int32_t H);
+/* AVSR_ERR_ARG for a NULL / non-positive / inconsistent argument, AVSR_ERR_UNSUPPORTED outside the limits: both before any launch. */
+int avsr_ctc_prefix_search_lm(const avsr_ctc_prefix_args* a, const avsr_ctc_prefix_lm* lm, void* stream);
+
 /* CTC forced alignment (csrc/ctc_align.hip; the rule is this project's own): the single most probable
  * alignment (Viterbi path) of a GIVEN label row to the frames of the head.  z [B * T][ld] are the head's logits over V + 1 real classes,
  * the blank is class V; in_len [B], T_b = clamp(in_len, 0, T); labels [B][L], target_len [B], U = clamp(target_len, 0, L) -- a plain
