@@ -178,6 +178,17 @@ class CtcPrefixLm(C.Structure):
                 ("ws", C.c_void_p), ("ws_bytes", C.c_int64), ("s_lm", C.c_void_p), ("lm_steps", C.c_void_p), ("lm_logp", C.c_void_p)]
 
 
+CTC_PREFIX_NGRAM_MAX_ORDER = 16        # AVSR_CTC_PREFIX_NGRAM_MAX_ORDER, _MAX_NODES, _MAX_ARCS of include/avsr_hip.h
+CTC_PREFIX_NGRAM_MAX_NODES = 1 << 24
+CTC_PREFIX_NGRAM_MAX_ARCS = 1 << 26
+
+
+class CtcPrefixNgram(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_nodes", "n_arcs", "V", "start", "go_id", "eos_id")] + \
+               [("weight", C.c_float), ("bonus", C.c_float)] + \
+               [(n, C.c_void_p) for n in ("bow", "backoff", "arc_begin", "sym", "logp", "next", "s_lm", "lm_steps", "lm_logp")]
+
+
 CTC_ALIGN_MAX_L = 512                  # AVSR_CTC_ALIGN_MAX_L of include/avsr_hip.h
 
 
@@ -199,7 +210,7 @@ _STRUCTS = {"avsr_dec_layer": DecLayer, "avsr_mat": Mat, "avsr_gemm_desc": GemmD
             "avsr_rnn_launch": RnnLaunch,
             "avsr_conv_desc": ConvDesc, "avsr_conv_launch": ConvLaunch, "avsr_conv3d_desc": Conv3dDesc, "avsr_logmel_args": LogmelArgs, "avsr_ctc_args": CtcArgs, "avsr_attn_mech": AttnMech, "avsr_attn_rnn": AttnRnn, "avsr_transpose_job": TransposeJob,
             "avsr_colsum_job": ColsumJob, "avsr_beam_lm": BeamLm, "avsr_beam_ctc": BeamCtc, "avsr_ctc_prefix_args": CtcPrefixArgs,
-            "avsr_ctc_prefix_lm": CtcPrefixLm,
+            "avsr_ctc_prefix_lm": CtcPrefixLm, "avsr_ctc_prefix_ngram": CtcPrefixNgram,
             "avsr_ctc_align_args": CtcAlignArgs}
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -249,6 +260,8 @@ _SIGS = {
     "avsr_ctc_prefix_search": [C.POINTER(CtcPrefixArgs), _vp],
     "avsr_ctc_prefix_lm_supported": [_i32, _i32, _i32, _i32, _i32, _i32, _i32],
     "avsr_ctc_prefix_search_lm": [C.POINTER(CtcPrefixArgs), C.POINTER(CtcPrefixLm), _vp],
+    "avsr_ctc_prefix_ngram_supported": [_i32, _i32, _i32, _i32, _i32],
+    "avsr_ctc_prefix_search_ngram": [C.POINTER(CtcPrefixArgs), C.POINTER(CtcPrefixNgram), _vp],
     "avsr_ctc_align_supported": [_i32, _i32],
     "avsr_ctc_align": [C.POINTER(CtcAlignArgs), _vp],
     "avsr_seq_logprob": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp],

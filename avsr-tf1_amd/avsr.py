@@ -37,6 +37,9 @@ prefix beam search of width `beam_width` on that head alone -- no decoder step (
 fuse that language model INTO this search: an extension by c also gets ctc_lm_weight * log p_lm(c | labels) + ctc_lm_length_bonus, and the
 final beam is re-sorted with ctc_lm_weight * log p_lm(EOS | labels) added (csrc/ctc_prefix_lm.hip; beam widths
 of up to 16).  `lm_checkpoint` itself stays a 'beam_search' option.
+`ctc_ngram_lm` (the path of an ARPA file over the units: <s> = GO, </s> = EOS, <space> = ' ', every other token a unit's string) fuses a
+back-off n-gram into the same search instead, with the same two weights (ngram.py, csrc/ctc_prefix_ngram.hip): a table walk per kept
+extension, no weight-matrix product.  It is refused together with `ctc_lm_checkpoint` and under any other `decoding_algorithm`.
 `decoding_algorithm='attention_rescoring'` (a `use_ctc` model; not in the reference) is the two-pass decode: that search's n-best, every
 hypothesis scored by the attention decoder teacher-forced, the best of log p_att + ctc_decode_weight * log p_ctc kept -- no step-by-step
 decode (csrc/rescore.hip).  No language-model term, no length normalisation.
@@ -205,6 +208,27 @@ class AVSR(object):
                                  "to %d layers (got beam_width %d, %d layers)"
                                  % (CTC_PREFIX_LM_MAX_W, MAX_LM_LAYERS, beam_width, len(ctc_lm_cfg.decoder_units)))
             ctc_lm_weights = _lm.checkpoint_weights(ctc_lm_cfg, ctc_lm_checkpoint)
+
+        # back-off n-gram fused into the CTC prefix search (csrc/ctc_prefix_ngram.hip): parsed and compiled on the host, here
+        self._ctc_ngram = None
+        ctc_ngram_lm = kwargs.get('ctc_ngram_lm')
+        if ctc_ngram_lm is not None:
+            from . import ngram as _ngram
+            from ._lib import CTC_PREFIX_LM_MAX_W
+            if decoding_algorithm != 'ctc_prefix_beam_search':
+                raise ValueError("ctc_ngram_lm needs decoding_algorithm='ctc_prefix_beam_search': the n-gram is fused into the CTC head's "
+                                 "own search ('beam_search' and 'attention_rescoring' take no n-gram)")
+            if ctc_lm_checkpoint is not None:
+                raise ValueError("ctc_ngram_lm and ctc_lm_checkpoint are two language models for one search: give one of them")
+            if beam_width > CTC_PREFIX_LM_MAX_W:
+                raise ValueError("ctc_ngram_lm: avsr_ctc_prefix_ngram_supported covers beam widths of up to %d (got beam_width %d)"
+                                 % (CTC_PREFIX_LM_MAX_W, beam_width))
+            self._ctc_ngram = _ngram.load_tables(ctc_ngram_lm, self._unit_dict)     # ValueError: not an ARPA file, a token that is no unit
+            from ._lib import CTC_PREFIX_NGRAM_MAX_NODES, CTC_PREFIX_NGRAM_MAX_ARCS
+            if self._ctc_ngram["n_nodes"] > CTC_PREFIX_NGRAM_MAX_NODES or self._ctc_ngram["n_arcs"] > CTC_PREFIX_NGRAM_MAX_ARCS:
+                raise ValueError("ctc_ngram_lm: avsr_ctc_prefix_ngram_supported covers automata of up to %d nodes and %d arcs (got %d, %d)"
+                                 % (CTC_PREFIX_NGRAM_MAX_NODES, CTC_PREFIX_NGRAM_MAX_ARCS, self._ctc_ngram["n_nodes"],
+                                    self._ctc_ngram["n_arcs"]))
 
         # joint CTC / attention scoring in beam search: an evaluate-time weight, held like _lm_weight; 0 = off, nothing new is launched
         self._ctc_decode_weight = float(kwargs.get('ctc_decode_weight', 0.0))
@@ -518,7 +542,8 @@ class AVSR(object):
                                                   ctc_weight=self._ctc_decode_weight)
         elif self._decoding_algorithm == 'ctc_prefix_beam_search':     # the head's own search: the attention decoder never runs
             ids = self._model.ctc_prefix_beam_search(batch, beam_width=self._beam_width, max_steps=self._cfg.max_label_length,
-                                                     lm=self._ctc_lm, lm_weight=self._ctc_lm_weight, length_bonus=self._ctc_lm_bonus)
+                                                     lm=self._ctc_lm, lm_weight=self._ctc_lm_weight, length_bonus=self._ctc_lm_bonus,
+                                                     ngram=self._ctc_ngram)
         else:
             ids = self._model.greedy_decode(batch, max_steps=self._cfg.max_label_length)
         if not isinstance(ids, list):

@@ -1,0 +1,130 @@
+// CTC prefix beam search with a back-off n-gram fused into the frame loop (avsr_ctc_prefix_search_ngram, include/avsr_hip.h; the rule is
+// INTEGRATION.md section 8): the fused search of csrc/ctc_prefix_fused.h (cpl_search: ONE launch per batch, one 256-thread workgroup per
+// utterance, the beam in LDS, fp32, no atomics, two launches bit-identical) with lam(. | g) read from a device-resident back-off
+// automaton.  This file is the model's side only: the walk, the Step object the search calls, the limits and the launch.
+//
+// State placement.  Per label sequence the model holds ONE int32: the node of the longest suffix of (GO, g) that is a context of the
+// model.  It lives in LDS behind the search's own words, [2 W rows], addressed by the same per-slot row index as the lam rows (a stay
+// inherits its parent's row, an extension takes a row no old slot references, so no step reads a node that the same step writes).
+// No workspace, no global-memory state: the only global traffic of a step is the read-only tables.
+//
+// Phase 6 for the M <= 16 kept extensions of a frame (skipped by the search's workgroup-uniform branch when M = 0):
+//   a. thread m < M:  node[new_m] = next[arc], arc = the arc the walk for (node[parent_m], tok_m) ends on        (prologue: node[0] = start)
+//   b. M * V independent walks over the 256 threads: lam[new_m][c] = walk(node[new_m], c)
+// One walk: acc = 0; while the node has no arc for c (binary search among its sorted arcs; the ROOT holds all V classes, so there the arc
+// is index c): acc += bow[node], node = backoff[node]; then acc + logp[arc].  fp32 additions in this fixed order, plain loads and stores.
+// A walk is a chain of dependent L2 reads (arc_begin, ~log2(arcs) probes of sym, bow / backoff per level); the tables are not staged in
+// LDS.  It cannot run away on tables it was not meant for: at most AVSR_CTC_PREFIX_NGRAM_MAX_ORDER - 1 nodes are visited before the root
+// is read directly, and every node id and arc range is clamped into its table.
+#include "ctc_prefix_fused.h"
+#include "prof.h"
+
+namespace avsr {
+
+__device__ __forceinline__ int cpn_node(const avsr_ctc_prefix_ngram& G, int n) { return (unsigned)n < (unsigned)G.n_nodes ? n : 0; }
+
+// the arc of class c at node n != 0, or -1
+__device__ __forceinline__ int cpn_find(const avsr_ctc_prefix_ngram& G, int n, int c) {
+  int lo = G.arc_begin[n], end = G.arc_begin[n + 1];
+  lo = lo < 0 ? 0 : lo;
+  end = end > G.n_arcs ? G.n_arcs : end;
+  int hi = end;
+  while (lo < hi) {                                                        // the first arc with sym >= c
+    const int mid = (lo + hi) >> 1;
+    if (G.sym[mid] < c) lo = mid + 1; else hi = mid;
+  }
+  return lo < end && G.sym[lo] == c ? lo : -1;
+}
+
+// lam(c | the context of node n); arc: the arc it ended on
+__device__ __forceinline__ float cpn_walk(const avsr_ctc_prefix_ngram& G, int n, int c, int& arc) {
+  float acc = 0.f;
+  for (int d = 1; d < AVSR_CTC_PREFIX_NGRAM_MAX_ORDER && n != 0; ++d) {
+    const int a = cpn_find(G, n, c);
+    if (a >= 0) { arc = a; return acc + G.logp[a]; }
+    acc += G.bow[n];
+    n = cpn_node(G, G.backoff[n]);
+  }
+  arc = c;                                                                 // the root: one arc per class, c < V <= n_arcs
+  return acc + G.logp[c];
+}
+
+// the n-gram as cpl_search's Step: one node id per pool row in LDS
+struct cpn_step {
+  const avsr_ctc_prefix_ngram& G;
+  int* sNode;                                                              // [2 W]
+  static size_t extra(int W) { return 2 * (size_t)W; }
+  __device__ __forceinline__ void init(int, int, uint32_t* words) { sNode = reinterpret_cast<int*>(words); }
+  __device__ __forceinline__ void prologue(int) {}
+  __device__ __forceinline__ void step(int M, const int* sTok, const int* sPar, const int* sNew, float* sLam, bool first) {
+    const int tid = threadIdx.x, V = G.V;
+    if (tid < M) {
+      int node = cpn_node(G, G.start);
+      if (!first) {
+        int arc;
+        cpn_walk(G, cpn_node(G, sNode[sPar[tid]]), sTok[tid], arc);
+        node = cpn_node(G, G.next[arc]);
+      }
+      sNode[sNew[tid]] = node;
+    }
+    lds_barrier();
+    for (int e = tid; e < M * V; e += 256) {
+      const int m = e / V, c = e - m * V, nw = sNew[m];
+      int arc;
+      sLam[nw * V + c] = cpn_walk(G, sNode[nw], c, arc);
+    }
+    lds_barrier();
+  }
+};
+
+// dynamic LDS: cpl_lds_words(V, W, L_max) + 2 W words
+__global__ __launch_bounds__(256) void ctc_prefix_ngram_kernel(const avsr_ctc_prefix_args A, const avsr_ctc_prefix_ngram G) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t cpn_smem[];
+  cpn_step step{G, nullptr};
+  const cpl_terms terms{G.weight, G.bonus, G.go_id, G.eos_id, G.s_lm, G.lm_steps, G.lm_logp};
+  cpl_search(A, terms, step, cpn_smem);
+}
+
+static size_t cpn_lds_bytes(int V, int W, int LM) { return sizeof(uint32_t) * (cpl_lds_words(V, W, LM) + cpn_step::extra(W)); }
+
+// AVSR_OK, or why the shape cannot run (decided on the host, nothing dereferenced)
+static int ctc_prefix_ngram_limits(int V, int W, int LM, int n_nodes, int n_arcs) {
+  if (V < 1 || W < 1 || LM < 1 || n_nodes < 1 || n_arcs < V) return AVSR_ERR_ARG;
+  if (V > AVSR_CTC_PREFIX_MAX_V || W > AVSR_CTC_PREFIX_LM_MAX_W || LM > AVSR_CTC_PREFIX_MAX_L) return AVSR_ERR_UNSUPPORTED;
+  if (n_nodes > AVSR_CTC_PREFIX_NGRAM_MAX_NODES || n_arcs > AVSR_CTC_PREFIX_NGRAM_MAX_ARCS) return AVSR_ERR_UNSUPPORTED;
+  if (cpn_lds_bytes(V, W, LM) > CPL_LDS_MAX_BYTES) return AVSR_ERR_UNSUPPORTED;      // (holds at the three maxima: 70 KiB)
+  return AVSR_OK;
+}
+
+}  // namespace avsr
+
+extern "C" int avsr_ctc_prefix_ngram_supported(int32_t V, int32_t beam_width, int32_t L_max, int32_t n_nodes, int32_t n_arcs) {
+  return avsr::ctc_prefix_ngram_limits(V, beam_width, L_max, n_nodes, n_arcs) == AVSR_OK ? 1 : 0;
+}
+
+extern "C" int avsr_ctc_prefix_search_ngram(const avsr_ctc_prefix_args* a, const avsr_ctc_prefix_ngram* ng, void* stream) {
+  using namespace avsr;
+  if (!a || !ng || !a->z || !a->in_len || !a->ids || !a->lens || !a->score) return AVSR_ERR_ARG;
+  if (a->B <= 0 || a->T <= 0 || a->ld < (int64_t)a->V + 1) return AVSR_ERR_ARG;
+  const int ntr = (a->trace_parent != 0) + (a->trace_sym != 0) + (a->trace_pb != 0) + (a->trace_pnb != 0);
+  if (ntr != 0 && ntr != 4) return AVSR_ERR_ARG;
+  if (ng->V != a->V || ng->go_id < 0 || ng->go_id >= a->V || ng->eos_id < 0 || ng->eos_id >= a->V) return AVSR_ERR_ARG;
+  if (!(ng->weight >= 0.f) || ng->weight == INFINITY || !(ng->bonus == ng->bonus) || ng->bonus == INFINITY || ng->bonus == -INFINITY)
+    return AVSR_ERR_ARG;
+  const int rc = ctc_prefix_ngram_limits(a->V, a->beam_width, a->L_max, ng->n_nodes, ng->n_arcs);
+  if (rc) return rc;
+  if (ng->start < 0 || ng->start >= ng->n_nodes) return AVSR_ERR_ARG;
+  if (!ng->bow || !ng->backoff || !ng->arc_begin || !ng->sym || !ng->logp || !ng->next || !ng->s_lm || !ng->lm_steps) return AVSR_ERR_ARG;
+  const size_t lds = cpn_lds_bytes(a->V, a->beam_width, a->L_max);
+  static bool attr_set = false;                                             // (per kernel: the LSTM form sets its own)
+  if (lds > 64 * 1024 && !attr_set) {
+    if (hipFuncSetAttribute((const void*)ctc_prefix_ngram_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CPL_LDS_MAX_BYTES) != hipSuccess)
+      return AVSR_ERR_HIP;
+    attr_set = true;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(PROF_STEP_LINEAR, s);
+  hipLaunchKernelGGL(ctc_prefix_ngram_kernel, dim3(a->B), dim3(256), lds, s, *a, *ng);
+  AVSR_CHECK_LAUNCH();
+  return AVSR_OK;
+}

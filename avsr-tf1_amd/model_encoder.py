@@ -556,7 +556,8 @@ class EncoderMixin:
             out.append(dict(status=1, score=float(score[b]), path=[int(k) for k in path[b, :lens[b]]], segments=segs))
         return out
 
-    def ctc_prefix_beam_search(self, batch, beam_width=10, max_steps=None, nbest=False, lm=None, lm_weight=0.3, length_bonus=0.0):
+    def ctc_prefix_beam_search(self, batch, beam_width=10, max_steps=None, nbest=False, lm=None, lm_weight=0.3, length_bonus=0.0,
+                               ngram=None):
         """use_ctc: CTC prefix beam search on the head alone (avsr_ctc_prefix_search, csrc/ctc_prefix.hip; the rule is INTEGRATION.md
         section 8) -- encoders in evaluation mode, the head, ONE launch for the batch; no decoder step.  max_steps bounds the label
         sequences (default: max_label_length).  One id list per utterance, the beam's best; nbest=True: per utterance the whole final
@@ -564,13 +565,16 @@ class EncoderMixin:
         lm: a Seq2SeqModel with architecture='lm' (LSTM) over the same vocabulary -- the model's step runs inside the search's frame
         loop (avsr_ctc_prefix_search_lm, csrc/ctc_prefix_lm.hip): an extension by c also gets lm_weight * log p_lm(c | labels) +
         length_bonus, and the final beam is re-sorted by final = p + lm_weight * log p_lm(EOS | labels).  nbest=True then gives
-        (ids, final, s_lm) triples, s_lm = log p_lm(labels, EOS).  Without lm the plain kernel runs and nothing new is allocated."""
-        out = self._ctc_prefix_beam_search(batch, beam_width, max_steps, nbest, lm, lm_weight, length_bonus)
+        (ids, final, s_lm) triples, s_lm = log p_lm(labels, EOS).  Without lm the plain kernel runs and nothing new is allocated.
+        ngram: instead of lm, the tables of a back-off n-gram (ngram.compile_tables / ngram.load_tables) -- the same rule and the same
+        outputs with lam read from the automaton (avsr_ctc_prefix_search_ngram, csrc/ctc_prefix_ngram.hip); the tables are uploaded
+        once per model object.  lm and ngram together are refused."""
+        out = self._ctc_prefix_beam_search(batch, beam_width, max_steps, nbest, lm, lm_weight, length_bonus, ngram)
         if self.check_persistent():
-            out = self._ctc_prefix_beam_search(batch, beam_width, max_steps, nbest, lm, lm_weight, length_bonus)
+            out = self._ctc_prefix_beam_search(batch, beam_width, max_steps, nbest, lm, lm_weight, length_bonus, ngram)
         return out
 
-    def _ctc_prefix_beam_search(self, batch, beam_width, max_steps, nbest, lm=None, lm_weight=0.3, length_bonus=0.0):
+    def _ctc_prefix_beam_search(self, batch, beam_width, max_steps, nbest, lm=None, lm_weight=0.3, length_bonus=0.0, ngram=None):
         cfg, dev = self.cfg, self.dev
         if not cfg.use_ctc:
             raise ValueError("ctc_prefix_beam_search needs a model built with use_ctc=True")
@@ -582,6 +586,23 @@ class EncoderMixin:
             raise ValueError("ctc_prefix_beam_search: avsr_ctc_prefix_search covers vocabularies of up to %d symbols, beam widths of up to "
                              "%d and label sequences of up to %d (got %d, %d, %d)"
                              % (CTC_PREFIX_MAX_V, CTC_PREFIX_MAX_W, CTC_PREFIX_MAX_L, V, W, Lm))
+        if lm is not None and ngram is not None:
+            raise ValueError("ctc_prefix_beam_search takes one language model: lm (an avsr.LM network) or ngram (back-off tables), not both")
+        if ngram is not None:
+            lm_weight, length_bonus = float(lm_weight), float(length_bonus)
+            if not lm_weight >= 0.0 or lm_weight == float("inf"):
+                raise ValueError("ctc_prefix_beam_search: lm_weight must be a finite number >= 0 (got %r)" % (lm_weight,))
+            if length_bonus != length_bonus or abs(length_bonus) == float("inf"):
+                raise ValueError("ctc_prefix_beam_search: length_bonus must be finite (got %r)" % (length_bonus,))
+            if (ngram["V"], ngram["go_id"], ngram["eos_id"]) != (V, cfg.go_id, cfg.eos_id):
+                raise ValueError("ctc_prefix_beam_search: the n-gram tables were compiled for V = %d, GO = %d, EOS = %d; the model has %d, "
+                                 "%d, %d" % (ngram["V"], ngram["go_id"], ngram["eos_id"], V, cfg.go_id, cfg.eos_id))
+            if not ops.ctc_prefix_ngram_supported(V, W, Lm, ngram["n_nodes"], ngram["n_arcs"]):
+                raise ValueError("ctc_prefix_beam_search: with an n-gram avsr_ctc_prefix_search_ngram covers beam widths of up to %d "
+                                 "(vocabularies of up to %d symbols, label sequences of up to %d) and automata of up to %d nodes and %d "
+                                 "arcs (got beam width %d, %d symbols, %d labels, %d nodes, %d arcs)"
+                                 % (CTC_PREFIX_LM_MAX_W, CTC_PREFIX_MAX_V, CTC_PREFIX_MAX_L, 1 << 24, 1 << 26, W, V, Lm,
+                                    ngram["n_nodes"], ngram["n_arcs"]))
         if lm is not None:
             self._check_lm(lm)
             lm_weight, length_bonus = float(lm_weight), float(length_bonus)
@@ -608,14 +629,16 @@ class EncoderMixin:
             E[key] = (torch.zeros(B, W, Lm, dtype=torch.int32, device=dev), torch.zeros(B, W, dtype=torch.int32, device=dev),
                       torch.zeros(B, W, device=dev))
         ids, lens, score = E[key]
-        if lm is None:
+        if ngram is not None:
+            s_lm = self._ctc_prefix_ngram_launch(E, Cc, B, V, W, Lm, ids, lens, score, ngram, lm_weight, length_bonus).cpu().numpy()
+        elif lm is None:
             ops.ctc_prefix_search(E["ctc_z"], Cc, E["len"], B, E["T"], V, W, Lm, ids, lens, score)
         else:
             s_lm = self._ctc_prefix_lm_launch(E, Cc, B, V, W, Lm, ids, lens, score, lm, lm_weight, length_bonus).cpu().numpy()
         ids, lens, score = ids.cpu().numpy(), lens.cpu().numpy(), score.cpu().numpy()
         if not nbest:
             return [[int(s) for s in ids[b, 0, :lens[b, 0]]] for b in range(B)]
-        if lm is not None:
+        if lm is not None or ngram is not None:
             return [[([int(s) for s in ids[b, r, :lens[b, r]]], float(score[b, r]), float(s_lm[b, r])) for r in range(W)
                      if score[b, r] > float("-inf")] for b in range(B)]
         return [[([int(s) for s in ids[b, r, :lens[b, r]]], float(score[b, r])) for r in range(W) if score[b, r] > float("-inf")]
@@ -645,6 +668,31 @@ class EncoderMixin:
         m.ws, m.ws_bytes = ops.fptr(buf["ws"]), buf["ws"].numel() * 4
         m.s_lm, m.lm_steps = ops.fptr(buf["s_lm"]), ops.fptr(buf["steps"])
         ops.ctc_prefix_search_lm(E["ctc_z"], Cc, E["len"], B, E["T"], V, W, Lm, ids, lens, score, m)
+        self._last_ctc_lm_steps = buf["steps"]
+        return buf["s_lm"]
+
+    def _ctc_prefix_ngram_launch(self, E, Cc, B, V, W, Lm, ids, lens, score, ngram, lm_weight, length_bonus):
+        """avsr_ctc_prefix_search_ngram over the automaton `ngram` (ngram.compile_tables): its six arrays go to the device once per
+        model object (kept with the dict they came from); s_lm and lm_steps are cached next to the ("ctc_prefix", W, Lm) buffers.
+        Returns s_lm [B, W] (device)."""
+        from ._lib import CtcPrefixNgram
+        dev = self.dev
+        cache = self.__dict__.setdefault("_ngram_tables", {})
+        if id(ngram) not in cache:
+            cache[id(ngram)] = (ngram, {k: torch.as_tensor(np.ascontiguousarray(ngram[k])).to(dev)
+                                        for k in ("bow", "backoff", "arc_begin", "sym", "logp", "next")})
+        tb = cache[id(ngram)][1]
+        key = ("ctc_prefix_ngram", W, Lm)
+        if key not in E:
+            E[key] = dict(s_lm=torch.zeros(B, W, device=dev), steps=torch.zeros(B, dtype=torch.int32, device=dev))
+        buf = E[key]
+        g = CtcPrefixNgram()
+        g.n_nodes, g.n_arcs, g.V, g.start = int(ngram["n_nodes"]), int(ngram["n_arcs"]), V, int(ngram["start"])
+        g.go_id, g.eos_id, g.weight, g.bonus = int(ngram["go_id"]), int(ngram["eos_id"]), lm_weight, length_bonus
+        for k in ("bow", "backoff", "arc_begin", "sym", "logp", "next"):
+            setattr(g, k, ops.fptr(tb[k]))
+        g.s_lm, g.lm_steps = ops.fptr(buf["s_lm"]), ops.fptr(buf["steps"])
+        ops.ctc_prefix_search_ngram(E["ctc_z"], Cc, E["len"], B, E["T"], V, W, Lm, ids, lens, score, g)
         self._last_ctc_lm_steps = buf["steps"]
         return buf["s_lm"]
 

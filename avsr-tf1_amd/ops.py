@@ -447,6 +447,23 @@ def ctc_prefix_search_lm(z, ld, in_len, B, T, V, beam_width, L_max, ids, lens, s
     check(_L().avsr_ctc_prefix_search_lm(C.byref(a), C.byref(lm), _s()), "avsr_ctc_prefix_search_lm")
 
 
+def ctc_prefix_ngram_supported(V, beam_width, L_max, n_nodes, n_arcs):
+    """Host-side: does avsr_ctc_prefix_search_ngram run this search shape with an automaton of this size?"""
+    return bool(_L().avsr_ctc_prefix_ngram_supported(int(V), int(beam_width), int(L_max), int(n_nodes), int(n_arcs)))
+
+
+def ctc_prefix_search_ngram(z, ld, in_len, B, T, V, beam_width, L_max, ids, lens, score, ng, trace=None):
+    """avsr_ctc_prefix_search_ngram: ctc_prefix_search with the term of the back-off n-gram ng (a _lib.CtcPrefixNgram with its tables
+    and the outputs s_lm [B, W], lm_steps [B] and, optionally, lm_logp [B, W, V] set).  score holds final."""
+    from ._lib import CtcPrefixArgs
+    a = CtcPrefixArgs()
+    a.B, a.T, a.V, a.beam_width, a.L_max, a.ld = int(B), int(T), int(V), int(beam_width), int(L_max), int(ld)
+    a.z, a.in_len, a.ids, a.lens, a.score = fptr(z), fptr(in_len), fptr(ids), fptr(lens), fptr(score)
+    if trace is not None:
+        a.trace_parent, a.trace_sym, a.trace_pb, a.trace_pnb = (fptr(t) for t in trace)
+    check(_L().avsr_ctc_prefix_search_ngram(C.byref(a), C.byref(ng), _s()), "avsr_ctc_prefix_search_ngram")
+
+
 def ctc_align_supported(V, L):
     """Host-side: does avsr_ctc_align run this shape (include/avsr_hip.h AVSR_CTC_ALIGN_MAX_L)?"""
     return bool(_L().avsr_ctc_align_supported(int(V), int(L)))

@@ -613,6 +613,46 @@ int64_t avsr_ctc_prefix_lm_ws_bytes(int32_t B, int32_t beam_width, int32_t n_lay
 /* AVSR_ERR_ARG for a NULL / non-positive / inconsistent argument, AVSR_ERR_UNSUPPORTED outside the limits: both before any launch. */
 int avsr_ctc_prefix_search_lm(const avsr_ctc_prefix_args* a, const avsr_ctc_prefix_lm* lm, void* stream);
 
+/* The same fused search with a back-off N-GRAM as the model (csrc/ctc_prefix_ngram.hip; the rule is INTEGRATION.md section 8): every
+ * word above about extensions, final, s_lm, lm_steps, lm_logp, the trace and weight == 0 holds; only lam(. | g) differs.  The model is
+ * a device-resident automaton (avsr-tf1_amd/ngram.py compile_tables writes it).  Node 0 is the root (the empty context); every other node
+ * is a context of 1 .. N-1 symbols:
+ *   bow [n_nodes]            back-off weight of the context (natural log; 0 at the root, which is never left)
+ *   backoff [n_nodes]        node of the context without its first symbol (0 at the root)
+ *   arc_begin [n_nodes + 1]  the node's arcs are [arc_begin[n], arc_begin[n + 1]), sorted by sym; the root's are the V arcs 0 .. V-1 with
+ *                            sym[c] == c (a class the model lacks holds the floor -99 ln 10 and next = 0), so arc_begin[1] == V
+ *   sym, logp, next [n_arcs] the class, lam(sym | context) where the n-gram is listed, and the node of the longest suffix of
+ *                            context . sym that is a node
+ * One value: acc = 0; while the node has no arc for c: acc += bow[node], node = backoff[node]; then lam = acc + logp[arc] -- fp32
+ * additions in exactly this order, so a host restatement in fp32 gives the same bits.  The walk visits at most
+ * AVSR_CTC_PREFIX_NGRAM_MAX_ORDER - 1 nodes before it looks at the root, whatever the tables hold, and every index it reads is clamped
+ * into its table.  The label sequence () has node `start` (the node of (GO), or 0); an extension by c moves its node along next.
+ * No workspace: the state is one node id per pool row, in LDS.
+ * Limits: avsr_ctc_prefix_search's on V and L_max, 1 <= beam_width <= AVSR_CTC_PREFIX_LM_MAX_W, 1 <= n_nodes <=
+ * AVSR_CTC_PREFIX_NGRAM_MAX_NODES, V <= n_arcs <= AVSR_CTC_PREFIX_NGRAM_MAX_ARCS; V == a->V, 0 <= go_id, eos_id < V, 0 <= start <
+ * n_nodes; weight finite and >= 0, bonus finite. */
+#define AVSR_CTC_PREFIX_NGRAM_MAX_ORDER 16
+#define AVSR_CTC_PREFIX_NGRAM_MAX_NODES (1 << 24)
+#define AVSR_CTC_PREFIX_NGRAM_MAX_ARCS (1 << 26)
+typedef struct avsr_ctc_prefix_ngram {
+  int32_t n_nodes, n_arcs, V, start;
+  int32_t go_id, eos_id;
+  float weight, bonus;
+  const float* bow;
+  const int32_t* backoff;
+  const int32_t* arc_begin;
+  const int32_t* sym;
+  const float* logp;
+  const int32_t* next;
+  float* s_lm;
+  int32_t* lm_steps;
+  float* lm_logp;
+} avsr_ctc_prefix_ngram;
+/* 1 if avsr_ctc_prefix_search_ngram runs this shape, else 0 (decided on the host; nothing is dereferenced). */
+int avsr_ctc_prefix_ngram_supported(int32_t V, int32_t beam_width, int32_t L_max, int32_t n_nodes, int32_t n_arcs);
+/* AVSR_ERR_ARG for a NULL / non-positive / inconsistent argument, AVSR_ERR_UNSUPPORTED outside the limits: both before any launch. */
+int avsr_ctc_prefix_search_ngram(const avsr_ctc_prefix_args* a, const avsr_ctc_prefix_ngram* ng, void* stream);
+
 /* CTC forced alignment (csrc/ctc_align.hip; the rule is this project's own): the single most probable
  * alignment (Viterbi path) of a GIVEN label row to the frames of the head.  z [B * T][ld] are the head's logits over V + 1 real classes,
  * the blank is class V; in_len [B], T_b = clamp(in_len, 0, T); labels [B][L], target_len [B], U = clamp(target_len, 0, L) -- a plain
