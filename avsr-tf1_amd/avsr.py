@@ -31,7 +31,8 @@ ctc_weight * CTC loss per label token to the step's loss, and `evaluate` also re
 beam search then adds ctc_decode_weight * (CTC prefix score of the continuation - that of the beam) to an unfinished beam's step score
 (joint CTC / attention decoding, csrc/beam_ctc.hip); it works together with `lm_checkpoint`.
 `decoding_algorithm='ctc_prefix_beam_search'` (a `use_ctc` model; not in the reference) makes `evaluate` take its predictions from a CTC
-prefix beam search of width `beam_width` on that head alone -- no decoder step (csrc/ctc_prefix.hip).
+prefix beam search of width `beam_width` on that head alone -- no decoder step (csrc/ctc_prefix.hip; the search itself,
+shared with the two fused forms below, is csrc/ctc_prefix_search.h).
 `ctc_lm_checkpoint` (a checkpoint written by `LM.train`; the model's shape through `lm_units_per_layer` / `lm_embedding_size` /
 `lm_cell_type`), `ctc_lm_weight` (0.3: a conventional value, not a tuned one) and `ctc_lm_length_bonus` (0.0) arrive through **kwargs and
 fuse that language model INTO this search: an extension by c also gets ctc_lm_weight * log p_lm(c | labels) + ctc_lm_length_bonus, and the

@@ -1,5 +1,5 @@
 // CTC prefix beam search with a language model fused into the frame loop (avsr_ctc_prefix_search_lm, include/avsr_hip.h; the rule is
-// INTEGRATION.md section 8): ctc_prefix.hip's search -- ONE launch per batch, one 256-thread workgroup per utterance, the beam in LDS,
+// INTEGRATION.md section 8): ctc_prefix_search.h's search -- ONE launch per batch, one 256-thread workgroup per utterance, the beam in LDS,
 // fp32, no atomics, two launches bit-identical -- whose extensions also carry  w * lam(c | g) + beta,  lam = log_softmax of avsr.LM's
 // evaluate graph after GO, g.  The LM's LSTM step runs INSIDE the workgroup's frame loop, and only on the frames that keep an extension.
 //
@@ -10,11 +10,10 @@
 // once), an extension takes a row that no OLD slot references -- at most W old plus W new rows are in use, so 2 W always suffice, the
 // selection order may permute the stays freely, nothing is ever copied, and no step reads a row that the same step writes.
 //
-// The search itself -- phases 1-5 of a frame, the pool rows, the epilogue -- is csrc/ctc_prefix_fused.h's cpl_search, shared with the n-gram
-// form (csrc/ctc_prefix_ngram.hip); this file holds the LSTM step it calls and the entry points.
-// Frame t: phases 1-5 are ctc_prefix.hip's, with the term taken from the parent slot's lam row in the candidate phase, in the merged
-// partner's extension inside `stay` and in phase 5's recomputation.  Phase 5 also hands out the rows (one thread, <= 2 W bit operations)
-// and lists the kept extensions (M <= W <= 16: ONE 16-row tile).  Phase 6, skipped by a workgroup-uniform branch when M = 0:
+// The search itself -- phases 1-5 of a frame, the pool rows, the epilogue -- is csrc/ctc_prefix_search.h's cp_search, shared with the
+// plain and the n-gram form (csrc/ctc_prefix.hip, csrc/ctc_prefix_ngram.hip); this file holds the LSTM step it calls, the limits and the
+// entry points.  Phase 5 lists the kept extensions (M <= W <= 16: ONE 16-row tile).  Phase 6, skipped by a workgroup-uniform branch when
+// M = 0:
 //   per layer   z = W_j . [emb[c] | h_prev(parent row)]  as v_mfma_f32_16x16x4_f32 with the WEIGHTS as the A operand (16 gate columns of
 //               the unit-interleaved layout = 4 whole units) and the slots as the B operand: lane (i16, g) ends with the four gates of
 //               unit 4 tile + g for slot i16 in its accumulator, so bias, gates, clip and the (c, h) update finish in registers.  The four
@@ -26,8 +25,7 @@
 // share one L1, which a workgroup-scope fence keeps coherent).
 // Prologue: one step from a zeroed row on GO for slot 0.  Epilogue: final = p + w * lam(EOS | g), the <= W entries re-sorted by final
 // (descending, ties to the earlier slot), s_lm, lm_steps, and the optional lam rows of the final entries.
-#include "ctc_prefix_fused.h"
-#include "prof.h"
+#include "ctc_prefix_search.h"
 
 namespace avsr {
 
@@ -153,7 +151,7 @@ __device__ __forceinline__ void cpl_lm_step(const avsr_ctc_prefix_lm& L, float* 
   lds_barrier();
 }
 
-// the LSTM as cpl_search's Step: (c, h) of the 2 W pool rows in the caller's workspace, no LDS of its own
+// the LSTM as cp_search's Step: (c, h) of the 2 W pool rows in the caller's workspace, no LDS of its own
 struct cpl_lstm_step {
   const avsr_ctc_prefix_lm& L;
   float* wsC;
@@ -172,24 +170,21 @@ struct cpl_lstm_step {
   }
 };
 
-// dynamic LDS: cpl_lds_words(V, W, L_max) words
+// dynamic LDS: cp_lds_words(V, W, L_max, true) words
 __global__ __launch_bounds__(256) void ctc_prefix_lm_kernel(const avsr_ctc_prefix_args A, const avsr_ctc_prefix_lm L) {
   extern __shared__ __attribute__((aligned(16))) uint32_t cpl_smem[];
   cpl_lstm_step step{L, nullptr, nullptr};
-  const cpl_terms terms{L.weight, L.bonus, L.go_id, L.eos_id, L.s_lm, L.lm_steps, L.lm_logp};
-  cpl_search(A, terms, step, cpl_smem);
+  const cp_terms terms{L.weight, L.bonus, L.go_id, L.eos_id, L.s_lm, L.lm_steps, L.lm_logp};
+  cp_search(A, terms, step, cpl_smem);
 }
 
 // AVSR_OK, or why the shape cannot run (decided on the host, nothing dereferenced)
 static int ctc_prefix_lm_limits(int V, int W, int LM, int nl, int H, int E, int one_hot) {
-  if (V < 1 || W < 1 || LM < 1 || nl < 1 || H < 1 || E < 1) return AVSR_ERR_ARG;
-  if (one_hot && E < V) return AVSR_ERR_ARG;
-  if (V > AVSR_CTC_PREFIX_MAX_V || W > AVSR_CTC_PREFIX_LM_MAX_W || LM > AVSR_CTC_PREFIX_MAX_L) return AVSR_ERR_UNSUPPORTED;
-  if (nl > AVSR_MAX_LM_LAYERS || H % 4 || E % 4) return AVSR_ERR_UNSUPPORTED;
+  const bool bad = nl < 1 || H < 1 || E < 1 || (one_hot && E < V);
   const long lim = 1L << 31, kmax = (E > H ? E : H) + H;             // 32-bit element offsets inside a weight matrix and a pool
-  if ((long)V * E >= lim || 4L * H * kmax >= lim || (long)V * H >= lim || 4L * W * nl * H >= lim) return AVSR_ERR_UNSUPPORTED;
-  if (sizeof(uint32_t) * cpl_lds_words(V, W, LM) > CPL_LDS_MAX_BYTES) return AVSR_ERR_UNSUPPORTED;   // (holds at the three maxima: 70 KiB)
-  return AVSR_OK;
+  const bool big = nl > AVSR_MAX_LM_LAYERS || H % 4 || E % 4 || (long)V * E >= lim || 4L * H * kmax >= lim || (long)V * H >= lim ||
+                   4L * W * nl * H >= lim;
+  return cp_limits(V, W, LM, AVSR_CTC_PREFIX_LM_MAX_W, true, cpl_lstm_step::extra(W), bad, big);   // (LDS at the three maxima: 70 KiB)
 }
 
 }  // namespace avsr
@@ -206,29 +201,15 @@ extern "C" int64_t avsr_ctc_prefix_lm_ws_bytes(int32_t B, int32_t beam_width, in
 
 extern "C" int avsr_ctc_prefix_search_lm(const avsr_ctc_prefix_args* a, const avsr_ctc_prefix_lm* lm, void* stream) {
   using namespace avsr;
-  if (!a || !lm || !a->z || !a->in_len || !a->ids || !a->lens || !a->score) return AVSR_ERR_ARG;
-  if (a->B <= 0 || a->T <= 0 || a->ld < (int64_t)a->V + 1) return AVSR_ERR_ARG;
-  const int ntr = (a->trace_parent != 0) + (a->trace_sym != 0) + (a->trace_pb != 0) + (a->trace_pnb != 0);
-  if (ntr != 0 && ntr != 4) return AVSR_ERR_ARG;
-  if (lm->V != a->V || lm->go_id < 0 || lm->go_id >= a->V || lm->eos_id < 0 || lm->eos_id >= a->V) return AVSR_ERR_ARG;
-  if (!(lm->weight >= 0.f) || lm->weight == INFINITY || !(lm->bonus == lm->bonus) || lm->bonus == INFINITY || lm->bonus == -INFINITY)
-    return AVSR_ERR_ARG;
-  const int rc = ctc_prefix_lm_limits(a->V, a->beam_width, a->L_max, lm->n_layers, lm->H, lm->E, lm->one_hot);
+  if (!lm) return AVSR_ERR_ARG;
+  int rc = cp_check_args(a);
+  if (!rc) rc = cp_check_terms(a->V, lm->V, lm->go_id, lm->eos_id, lm->weight, lm->bonus);
+  if (!rc) rc = ctc_prefix_lm_limits(a->V, a->beam_width, a->L_max, lm->n_layers, lm->H, lm->E, lm->one_hot);
   if (rc) return rc;
   if (!lm->embedding || !lm->wout_t || !lm->bout || !lm->ws || !lm->s_lm || !lm->lm_steps) return AVSR_ERR_ARG;
   for (int j = 0; j < lm->n_layers; ++j)
     if (!lm->wt[j] || !lm->bias[j]) return AVSR_ERR_ARG;
   if (lm->ws_bytes < avsr_ctc_prefix_lm_ws_bytes(a->B, a->beam_width, lm->n_layers, lm->H)) return AVSR_ERR_ARG;
-  const size_t lds = sizeof(uint32_t) * cpl_lds_words(a->V, a->beam_width, a->L_max);
-  static bool attr_set = false;
-  if (lds > 64 * 1024 && !attr_set) {
-    if (hipFuncSetAttribute((const void*)ctc_prefix_lm_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CPL_LDS_MAX_BYTES) != hipSuccess)
-      return AVSR_ERR_HIP;
-    attr_set = true;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope ps(PROF_STEP_LINEAR, s);
-  hipLaunchKernelGGL(ctc_prefix_lm_kernel, dim3(a->B), dim3(256), lds, s, *a, *lm);
-  AVSR_CHECK_LAUNCH();
-  return AVSR_OK;
+  const size_t lds = sizeof(uint32_t) * cp_lds_words(a->V, a->beam_width, a->L_max, true, cpl_lstm_step::extra(a->beam_width));
+  return cp_launch<ctc_prefix_lm_kernel>(lds, stream, *a, *lm);
 }

@@ -1,5 +1,5 @@
 // CTC prefix beam search with a back-off n-gram fused into the frame loop (avsr_ctc_prefix_search_ngram, include/avsr_hip.h; the rule is
-// INTEGRATION.md section 8): the fused search of csrc/ctc_prefix_fused.h (cpl_search: ONE launch per batch, one 256-thread workgroup per
+// INTEGRATION.md section 8): the search of csrc/ctc_prefix_search.h (cp_search: ONE launch per batch, one 256-thread workgroup per
 // utterance, the beam in LDS, fp32, no atomics, two launches bit-identical) with lam(. | g) read from a device-resident back-off
 // automaton.  This file is the model's side only: the walk, the Step object the search calls, the limits and the launch.
 //
@@ -16,8 +16,7 @@
 // A walk is a chain of dependent L2 reads (arc_begin, ~log2(arcs) probes of sym, bow / backoff per level); the tables are not staged in
 // LDS.  It cannot run away on tables it was not meant for: at most AVSR_CTC_PREFIX_NGRAM_MAX_ORDER - 1 nodes are visited before the root
 // is read directly, and every node id and arc range is clamped into its table.
-#include "ctc_prefix_fused.h"
-#include "prof.h"
+#include "ctc_prefix_search.h"
 
 namespace avsr {
 
@@ -49,7 +48,7 @@ __device__ __forceinline__ float cpn_walk(const avsr_ctc_prefix_ngram& G, int n,
   return acc + G.logp[c];
 }
 
-// the n-gram as cpl_search's Step: one node id per pool row in LDS
+// the n-gram as cp_search's Step: one node id per pool row in LDS
 struct cpn_step {
   const avsr_ctc_prefix_ngram& G;
   int* sNode;                                                              // [2 W]
@@ -77,23 +76,19 @@ struct cpn_step {
   }
 };
 
-// dynamic LDS: cpl_lds_words(V, W, L_max) + 2 W words
+// dynamic LDS: cp_lds_words(V, W, L_max, true, 2 W) words
 __global__ __launch_bounds__(256) void ctc_prefix_ngram_kernel(const avsr_ctc_prefix_args A, const avsr_ctc_prefix_ngram G) {
   extern __shared__ __attribute__((aligned(16))) uint32_t cpn_smem[];
   cpn_step step{G, nullptr};
-  const cpl_terms terms{G.weight, G.bonus, G.go_id, G.eos_id, G.s_lm, G.lm_steps, G.lm_logp};
-  cpl_search(A, terms, step, cpn_smem);
+  const cp_terms terms{G.weight, G.bonus, G.go_id, G.eos_id, G.s_lm, G.lm_steps, G.lm_logp};
+  cp_search(A, terms, step, cpn_smem);
 }
-
-static size_t cpn_lds_bytes(int V, int W, int LM) { return sizeof(uint32_t) * (cpl_lds_words(V, W, LM) + cpn_step::extra(W)); }
 
 // AVSR_OK, or why the shape cannot run (decided on the host, nothing dereferenced)
 static int ctc_prefix_ngram_limits(int V, int W, int LM, int n_nodes, int n_arcs) {
-  if (V < 1 || W < 1 || LM < 1 || n_nodes < 1 || n_arcs < V) return AVSR_ERR_ARG;
-  if (V > AVSR_CTC_PREFIX_MAX_V || W > AVSR_CTC_PREFIX_LM_MAX_W || LM > AVSR_CTC_PREFIX_MAX_L) return AVSR_ERR_UNSUPPORTED;
-  if (n_nodes > AVSR_CTC_PREFIX_NGRAM_MAX_NODES || n_arcs > AVSR_CTC_PREFIX_NGRAM_MAX_ARCS) return AVSR_ERR_UNSUPPORTED;
-  if (cpn_lds_bytes(V, W, LM) > CPL_LDS_MAX_BYTES) return AVSR_ERR_UNSUPPORTED;      // (holds at the three maxima: 70 KiB)
-  return AVSR_OK;
+  const bool bad = n_nodes < 1 || n_arcs < V;
+  const bool big = n_nodes > AVSR_CTC_PREFIX_NGRAM_MAX_NODES || n_arcs > AVSR_CTC_PREFIX_NGRAM_MAX_ARCS;
+  return cp_limits(V, W, LM, AVSR_CTC_PREFIX_LM_MAX_W, true, cpn_step::extra(W), bad, big);        // (LDS at the three maxima: 70 KiB)
 }
 
 }  // namespace avsr
@@ -104,27 +99,13 @@ extern "C" int avsr_ctc_prefix_ngram_supported(int32_t V, int32_t beam_width, in
 
 extern "C" int avsr_ctc_prefix_search_ngram(const avsr_ctc_prefix_args* a, const avsr_ctc_prefix_ngram* ng, void* stream) {
   using namespace avsr;
-  if (!a || !ng || !a->z || !a->in_len || !a->ids || !a->lens || !a->score) return AVSR_ERR_ARG;
-  if (a->B <= 0 || a->T <= 0 || a->ld < (int64_t)a->V + 1) return AVSR_ERR_ARG;
-  const int ntr = (a->trace_parent != 0) + (a->trace_sym != 0) + (a->trace_pb != 0) + (a->trace_pnb != 0);
-  if (ntr != 0 && ntr != 4) return AVSR_ERR_ARG;
-  if (ng->V != a->V || ng->go_id < 0 || ng->go_id >= a->V || ng->eos_id < 0 || ng->eos_id >= a->V) return AVSR_ERR_ARG;
-  if (!(ng->weight >= 0.f) || ng->weight == INFINITY || !(ng->bonus == ng->bonus) || ng->bonus == INFINITY || ng->bonus == -INFINITY)
-    return AVSR_ERR_ARG;
-  const int rc = ctc_prefix_ngram_limits(a->V, a->beam_width, a->L_max, ng->n_nodes, ng->n_arcs);
+  if (!ng) return AVSR_ERR_ARG;
+  int rc = cp_check_args(a);
+  if (!rc) rc = cp_check_terms(a->V, ng->V, ng->go_id, ng->eos_id, ng->weight, ng->bonus);
+  if (!rc) rc = ctc_prefix_ngram_limits(a->V, a->beam_width, a->L_max, ng->n_nodes, ng->n_arcs);
   if (rc) return rc;
   if (ng->start < 0 || ng->start >= ng->n_nodes) return AVSR_ERR_ARG;
   if (!ng->bow || !ng->backoff || !ng->arc_begin || !ng->sym || !ng->logp || !ng->next || !ng->s_lm || !ng->lm_steps) return AVSR_ERR_ARG;
-  const size_t lds = cpn_lds_bytes(a->V, a->beam_width, a->L_max);
-  static bool attr_set = false;                                             // (per kernel: the LSTM form sets its own)
-  if (lds > 64 * 1024 && !attr_set) {
-    if (hipFuncSetAttribute((const void*)ctc_prefix_ngram_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, CPL_LDS_MAX_BYTES) != hipSuccess)
-      return AVSR_ERR_HIP;
-    attr_set = true;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope ps(PROF_STEP_LINEAR, s);
-  hipLaunchKernelGGL(ctc_prefix_ngram_kernel, dim3(a->B), dim3(256), lds, s, *a, *ng);
-  AVSR_CHECK_LAUNCH();
-  return AVSR_OK;
+  const size_t lds = sizeof(uint32_t) * cp_lds_words(a->V, a->beam_width, a->L_max, true, cpn_step::extra(a->beam_width));
+  return cp_launch<ctc_prefix_ngram_kernel>(lds, stream, *a, *ng);
 }

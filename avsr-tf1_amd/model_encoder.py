@@ -558,8 +558,8 @@ class EncoderMixin:
 
     def ctc_prefix_beam_search(self, batch, beam_width=10, max_steps=None, nbest=False, lm=None, lm_weight=0.3, length_bonus=0.0,
                                ngram=None):
-        """use_ctc: CTC prefix beam search on the head alone (avsr_ctc_prefix_search, csrc/ctc_prefix.hip; the rule is INTEGRATION.md
-        section 8) -- encoders in evaluation mode, the head, ONE launch for the batch; no decoder step.  max_steps bounds the label
+        """use_ctc: CTC prefix beam search on the head alone (avsr_ctc_prefix_search, csrc/ctc_prefix.hip; the search of all three forms
+        is csrc/ctc_prefix_search.h, the rule is INTEGRATION.md section 8) -- encoders in evaluation mode, the head, ONE launch for the batch; no decoder step.  max_steps bounds the label
         sequences (default: max_label_length).  One id list per utterance, the beam's best; nbest=True: per utterance the whole final
         beam as (ids, score) pairs, best first, score = log p_ctc(ids | x) up to what pruning lost.
         lm: a Seq2SeqModel with architecture='lm' (LSTM) over the same vocabulary -- the model's step runs inside the search's frame
@@ -588,12 +588,15 @@ class EncoderMixin:
                              % (CTC_PREFIX_MAX_V, CTC_PREFIX_MAX_W, CTC_PREFIX_MAX_L, V, W, Lm))
         if lm is not None and ngram is not None:
             raise ValueError("ctc_prefix_beam_search takes one language model: lm (an avsr.LM network) or ngram (back-off tables), not both")
-        if ngram is not None:
+        if lm is not None:
+            self._check_lm(lm)
+        if lm is not None or ngram is not None:
             lm_weight, length_bonus = float(lm_weight), float(length_bonus)
             if not lm_weight >= 0.0 or lm_weight == float("inf"):
                 raise ValueError("ctc_prefix_beam_search: lm_weight must be a finite number >= 0 (got %r)" % (lm_weight,))
             if length_bonus != length_bonus or abs(length_bonus) == float("inf"):
                 raise ValueError("ctc_prefix_beam_search: length_bonus must be finite (got %r)" % (length_bonus,))
+        if ngram is not None:
             if (ngram["V"], ngram["go_id"], ngram["eos_id"]) != (V, cfg.go_id, cfg.eos_id):
                 raise ValueError("ctc_prefix_beam_search: the n-gram tables were compiled for V = %d, GO = %d, EOS = %d; the model has %d, "
                                  "%d, %d" % (ngram["V"], ngram["go_id"], ngram["eos_id"], V, cfg.go_id, cfg.eos_id))
@@ -604,12 +607,6 @@ class EncoderMixin:
                                  % (CTC_PREFIX_LM_MAX_W, CTC_PREFIX_MAX_V, CTC_PREFIX_MAX_L, 1 << 24, 1 << 26, W, V, Lm,
                                     ngram["n_nodes"], ngram["n_arcs"]))
         if lm is not None:
-            self._check_lm(lm)
-            lm_weight, length_bonus = float(lm_weight), float(length_bonus)
-            if not lm_weight >= 0.0 or lm_weight == float("inf"):
-                raise ValueError("ctc_prefix_beam_search: lm_weight must be a finite number >= 0 (got %r)" % (lm_weight,))
-            if length_bonus != length_bonus or abs(length_bonus) == float("inf"):
-                raise ValueError("ctc_prefix_beam_search: length_bonus must be finite (got %r)" % (length_bonus,))
             lc = lm.cfg
             nl, H, El = len(lc.decoder_units), lc.decoder_units[0], lc.embedding_size
             if not ops.ctc_prefix_lm_supported(V, W, Lm, nl, H, El, int(lm.onehot is not None)):
@@ -629,20 +626,25 @@ class EncoderMixin:
             E[key] = (torch.zeros(B, W, Lm, dtype=torch.int32, device=dev), torch.zeros(B, W, dtype=torch.int32, device=dev),
                       torch.zeros(B, W, device=dev))
         ids, lens, score = E[key]
+        s_lm = None                                                # (device) with a model: the third column of the n-best
         if ngram is not None:
-            s_lm = self._ctc_prefix_ngram_launch(E, Cc, B, V, W, Lm, ids, lens, score, ngram, lm_weight, length_bonus).cpu().numpy()
-        elif lm is None:
-            ops.ctc_prefix_search(E["ctc_z"], Cc, E["len"], B, E["T"], V, W, Lm, ids, lens, score)
+            s_lm = self._ctc_prefix_ngram_launch(E, Cc, B, V, W, Lm, ids, lens, score, ngram, lm_weight, length_bonus)
+        elif lm is not None:
+            s_lm = self._ctc_prefix_lm_launch(E, Cc, B, V, W, Lm, ids, lens, score, lm, lm_weight, length_bonus)
         else:
-            s_lm = self._ctc_prefix_lm_launch(E, Cc, B, V, W, Lm, ids, lens, score, lm, lm_weight, length_bonus).cpu().numpy()
-        ids, lens, score = ids.cpu().numpy(), lens.cpu().numpy(), score.cpu().numpy()
+            ops.ctc_prefix_search(E["ctc_z"], Cc, E["len"], B, E["T"], V, W, Lm, ids, lens, score)
+        cols = [score.cpu().numpy()] + ([] if s_lm is None else [s_lm.cpu().numpy()])
+        ids, lens = ids.cpu().numpy(), lens.cpu().numpy()
         if not nbest:
             return [[int(s) for s in ids[b, 0, :lens[b, 0]]] for b in range(B)]
-        if lm is not None or ngram is not None:
-            return [[([int(s) for s in ids[b, r, :lens[b, r]]], float(score[b, r]), float(s_lm[b, r])) for r in range(W)
-                     if score[b, r] > float("-inf")] for b in range(B)]
-        return [[([int(s) for s in ids[b, r, :lens[b, r]]], float(score[b, r])) for r in range(W) if score[b, r] > float("-inf")]
-                for b in range(B)]
+        return [[([int(s) for s in ids[b, r, :lens[b, r]]],) + tuple(float(c[b, r]) for c in cols) for r in range(W)
+                 if cols[0][b, r] > float("-inf")] for b in range(B)]
+
+    def _ctc_prefix_model_outputs(self, E, key, B, W):
+        """E[key], the cached buffers of a fused search: s_lm [B, W] and steps [B], made on first use."""
+        if key not in E:
+            E[key] = dict(s_lm=torch.zeros(B, W, device=self.dev), steps=torch.zeros(B, dtype=torch.int32, device=self.dev))
+        return E[key]
 
     def _ctc_prefix_lm_launch(self, E, Cc, B, V, W, Lm, ids, lens, score, lm, lm_weight, length_bonus):
         """avsr_ctc_prefix_search_lm over the language model's own (4-padded) weights; the state workspace, s_lm and lm_steps are
@@ -651,11 +653,9 @@ class EncoderMixin:
         lc, dev = lm.cfg, self.dev
         nl, H = len(lc.decoder_units), lc.decoder_units[0]
         lm._refresh_derived()
-        key = ("ctc_prefix_lm", W, Lm, nl, H)
-        if key not in E:
-            E[key] = dict(ws=torch.zeros(ops.ctc_prefix_lm_ws_bytes(B, W, nl, H) // 4, device=dev), s_lm=torch.zeros(B, W, device=dev),
-                          steps=torch.zeros(B, dtype=torch.int32, device=dev))
-        buf = E[key]
+        buf = self._ctc_prefix_model_outputs(E, ("ctc_prefix_lm", W, Lm, nl, H), B, W)
+        if "ws" not in buf:
+            buf["ws"] = torch.zeros(ops.ctc_prefix_lm_ws_bytes(B, W, nl, H) // 4, device=dev)
         m = CtcPrefixLm()
         m.n_layers, m.H, m.E, m.V, m.one_hot = nl, H, lc.embedding_size, V, int(lm.onehot is not None)
         m.go_id, m.eos_id, m.weight, m.bonus = lc.go_id, lc.eos_id, lm_weight, length_bonus
@@ -682,10 +682,7 @@ class EncoderMixin:
             cache[id(ngram)] = (ngram, {k: torch.as_tensor(np.ascontiguousarray(ngram[k])).to(dev)
                                         for k in ("bow", "backoff", "arc_begin", "sym", "logp", "next")})
         tb = cache[id(ngram)][1]
-        key = ("ctc_prefix_ngram", W, Lm)
-        if key not in E:
-            E[key] = dict(s_lm=torch.zeros(B, W, device=dev), steps=torch.zeros(B, dtype=torch.int32, device=dev))
-        buf = E[key]
+        buf = self._ctc_prefix_model_outputs(E, ("ctc_prefix_ngram", W, Lm), B, W)
         g = CtcPrefixNgram()
         g.n_nodes, g.n_arcs, g.V, g.start = int(ngram["n_nodes"]), int(ngram["n_arcs"]), V, int(ngram["start"])
         g.go_id, g.eos_id, g.weight, g.bonus = int(ngram["go_id"]), int(ngram["eos_id"]), lm_weight, length_bonus

@@ -414,15 +414,21 @@ def ctc_prefix_search_supported(V, beam_width, L_max):
     return bool(_L().avsr_ctc_prefix_search_supported(int(V), int(beam_width), int(L_max)))
 
 
-def ctc_prefix_search(z, ld, in_len, B, T, V, beam_width, L_max, ids, lens, score, trace=None):
-    """avsr_ctc_prefix_search: z [B*T, ld] over V + 1 real classes (blank = V) -> the final beam ids [B, W, L_max] (-1 padded), lens and
-    score [B, W], sorted.  trace: None, or (parent, sym, pb, pnb), each [B, T, W] -- the beam after every frame."""
+def _ctc_prefix_args(z, ld, in_len, B, T, V, beam_width, L_max, ids, lens, score, trace):
+    """The avsr_ctc_prefix_args of the three searches below."""
     from ._lib import CtcPrefixArgs
     a = CtcPrefixArgs()
     a.B, a.T, a.V, a.beam_width, a.L_max, a.ld = int(B), int(T), int(V), int(beam_width), int(L_max), int(ld)
     a.z, a.in_len, a.ids, a.lens, a.score = fptr(z), fptr(in_len), fptr(ids), fptr(lens), fptr(score)
     if trace is not None:
         a.trace_parent, a.trace_sym, a.trace_pb, a.trace_pnb = (fptr(t) for t in trace)
+    return a
+
+
+def ctc_prefix_search(z, ld, in_len, B, T, V, beam_width, L_max, ids, lens, score, trace=None):
+    """avsr_ctc_prefix_search: z [B*T, ld] over V + 1 real classes (blank = V) -> the final beam ids [B, W, L_max] (-1 padded), lens and
+    score [B, W], sorted.  trace: None, or (parent, sym, pb, pnb), each [B, T, W] -- the beam after every frame."""
+    a = _ctc_prefix_args(z, ld, in_len, B, T, V, beam_width, L_max, ids, lens, score, trace)
     check(_L().avsr_ctc_prefix_search(C.byref(a), _s()), "avsr_ctc_prefix_search")
 
 
@@ -438,12 +444,7 @@ def ctc_prefix_lm_ws_bytes(B, beam_width, n_layers, H):
 def ctc_prefix_search_lm(z, ld, in_len, B, T, V, beam_width, L_max, ids, lens, score, lm, trace=None):
     """avsr_ctc_prefix_search_lm: ctc_prefix_search with the language-model term of the descriptor lm (a _lib.CtcPrefixLm with its
     weights, workspace and the outputs s_lm [B, W], lm_steps [B] and, optionally, lm_logp [B, W, V] set).  score holds final."""
-    from ._lib import CtcPrefixArgs
-    a = CtcPrefixArgs()
-    a.B, a.T, a.V, a.beam_width, a.L_max, a.ld = int(B), int(T), int(V), int(beam_width), int(L_max), int(ld)
-    a.z, a.in_len, a.ids, a.lens, a.score = fptr(z), fptr(in_len), fptr(ids), fptr(lens), fptr(score)
-    if trace is not None:
-        a.trace_parent, a.trace_sym, a.trace_pb, a.trace_pnb = (fptr(t) for t in trace)
+    a = _ctc_prefix_args(z, ld, in_len, B, T, V, beam_width, L_max, ids, lens, score, trace)
     check(_L().avsr_ctc_prefix_search_lm(C.byref(a), C.byref(lm), _s()), "avsr_ctc_prefix_search_lm")
 
 
@@ -455,12 +456,7 @@ def ctc_prefix_ngram_supported(V, beam_width, L_max, n_nodes, n_arcs):
 def ctc_prefix_search_ngram(z, ld, in_len, B, T, V, beam_width, L_max, ids, lens, score, ng, trace=None):
     """avsr_ctc_prefix_search_ngram: ctc_prefix_search with the term of the back-off n-gram ng (a _lib.CtcPrefixNgram with its tables
     and the outputs s_lm [B, W], lm_steps [B] and, optionally, lm_logp [B, W, V] set).  score holds final."""
-    from ._lib import CtcPrefixArgs
-    a = CtcPrefixArgs()
-    a.B, a.T, a.V, a.beam_width, a.L_max, a.ld = int(B), int(T), int(V), int(beam_width), int(L_max), int(ld)
-    a.z, a.in_len, a.ids, a.lens, a.score = fptr(z), fptr(in_len), fptr(ids), fptr(lens), fptr(score)
-    if trace is not None:
-        a.trace_parent, a.trace_sym, a.trace_pb, a.trace_pnb = (fptr(t) for t in trace)
+    a = _ctc_prefix_args(z, ld, in_len, B, T, V, beam_width, L_max, ids, lens, score, trace)
     check(_L().avsr_ctc_prefix_search_ngram(C.byref(a), C.byref(ng), _s()), "avsr_ctc_prefix_search_ngram")
 
 

@@ -1,6 +1,6 @@
 """What a back-off n-gram fused into the CTC prefix beam search costs (Seq2SeqModel.ctc_prefix_beam_search(ngram=...),
 csrc/ctc_prefix_ngram.hip) next to the plain search and the LSTM-fused one, and that sharing the search between the two fused kernels
-(csrc/ctc_prefix_fused.h) left the plain and the LSTM-fused search where they were.
+(now csrc/ctc_prefix_search.h) left the plain and the LSTM-fused search where they were.
 
     python tools/ctc_prefix_ngram_cost.py                      # this tree: in ONE process per head the plain, the LSTM-fused and the
                                                                #   n-gram launches (orders 2 and 4) by device events, and decodes/s
