@@ -46,6 +46,12 @@ hypothesis scored by the attention decoder teacher-forced, the best of log p_att
 decode (csrc/rescore.hip).  No language-model term, no length normalisation.
 `AVSR.align` (a `use_ctc` model; not in the reference) returns and writes the forced alignment of every evaluate utterance's labels, or of
 its predictions, on the CTC head: per label the first and last frame and a confidence (csrc/ctc_align.hip).
+`spec_augment` (None = off, or a dict; not in the reference, which only mixes noise offline in its dataset writer) arrives through
+**kwargs and masks the encoders' inputs inside the train step, anew every step: `freq_masks` bands of up to `freq_width` of the
+`freq_bins` bins and `time_masks` spans of up to min(`time_width`, `time_ratio` * length) rows on the audio stream,
+`video_time_masks` / `video_time_width` / `video_time_ratio` spans of frames on the video stream (features or lip crops), filled with
+`mask_value` = 'mean' (the utterance's own column mean) or 'zero'.  Every count defaults to 0 = off; no size is tuned.  Train graph only:
+`evaluate`, every decoding algorithm and `align` never augment (csrc/specaugment.hip).
 """
 import glob
 import os
@@ -265,7 +271,13 @@ class AVSR(object):
                     feats[key] = self._audio_frontend.feat
                     continue
                 feats[key] = shape[0]
+        # SpecAugment in the train step (csrc/specaugment.hip): parsed and refused here, on the host, before any engine is built
+        from .config import spec_augment_fields
+        spec_fields = spec_augment_fields(kwargs.get('spec_augment'), audio=audio_processing is not None, video=video_processing is not None,
+                                          audio_processing=audio_processing, audio_feat=feats.get('audio'),
+                                          num_mel_bins=kwargs.get('num_mel_bins', 30))
         self._cfg = ModelConfig(
+            **spec_fields,
             architecture=architecture, encoder_type=encoder_type, cell_type=cell_type,
             video_units=tuple(encoder_units_per_layer[0]) if video_processing is not None else None,
             audio_units=tuple(encoder_units_per_layer[1]) if audio_processing is not None else None,

@@ -6,10 +6,62 @@ LUONG_TYPES = ("luong", "scaled_luong")
 BAHDANAU_TYPES = ("bahdanau", "normed_bahdanau")
 ATT_CODE = {"luong": 0, "scaled_luong": 1, "bahdanau": 2, "normed_bahdanau": 3}
 CELL_ID_DECODER = 40
+# RNG streams of the SpecAugment draws (csrc/common.h RNG_STREAM_SPEC_*): above every dropout / sampling stream, which are
+# cell_id * 4 + kind with cell ids up to CELL_ID_DECODER + 3 (a four-layer decoder)
+SPEC_STREAM_AUDIO_FREQ, SPEC_STREAM_AUDIO_TIME, SPEC_STREAM_VIDEO_TIME = 200, 201, 202
+SPEC_AUGMENT_KEYS = ("freq_masks", "freq_width", "time_masks", "time_width", "time_ratio", "video_time_masks", "video_time_width",
+                     "video_time_ratio", "freq_bins", "mask_value")
+SPEC_AUGMENT_MAX_MASKS, SPEC_AUGMENT_MAX_T = 8, 65535          # avsr_spec_augment_supported (include/avsr_hip.h)
 
 
 def round4(n: int) -> int:
     return (n + 3) // 4 * 4
+
+
+def spec_augment_fields(spec, audio=True, video=True, audio_processing="features", audio_feat=None, num_mel_bins=30):
+    """The `spec_augment` keyword of avsr.AVSR (None, or a dict over SPEC_AUGMENT_KEYS) -> the ModelConfig fields it sets.  Refuses on
+    the host, naming the key (ValueError): unknown keys, negative or non-integer counts and widths, more masks of a kind than the
+    kernel draws, a ratio outside [0, 1], audio keys without an audio stream, video keys without a video stream, a freq_bins that
+    does not divide the feature width (audio_feat, when given) or contradicts audio_processing='wav', an unknown mask_value."""
+    if spec is None:
+        return {}
+    if not isinstance(spec, dict):
+        raise ValueError("spec_augment must be None or a dict over %s (got %r)" % (", ".join(SPEC_AUGMENT_KEYS), type(spec).__name__))
+    for k in spec:
+        if k not in SPEC_AUGMENT_KEYS:
+            raise ValueError("spec_augment: unknown key %r (the keys are %s)" % (k, ", ".join(SPEC_AUGMENT_KEYS)))
+    out = {}
+    for k in ("freq_masks", "freq_width", "time_masks", "time_width", "video_time_masks", "video_time_width"):
+        v = spec.get(k, 0)
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise ValueError("spec_augment: %s must be a non-negative integer (got %r)" % (k, v))
+        if k.endswith("masks") and v > SPEC_AUGMENT_MAX_MASKS:
+            raise ValueError("spec_augment: %s: avsr_spec_augment draws at most %d masks of a kind (got %d)" % (k, SPEC_AUGMENT_MAX_MASKS, v))
+        out["spec_" + k] = v
+    for k in ("time_ratio", "video_time_ratio"):
+        v = spec.get(k, 1.0)
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not 0.0 <= v <= 1.0:
+            raise ValueError("spec_augment: %s must be a number in [0, 1] (got %r)" % (k, v))
+        out["spec_" + k] = float(v)
+    mv = spec.get("mask_value", "mean")
+    if mv not in ("mean", "zero"):
+        raise ValueError("spec_augment: mask_value must be 'mean' or 'zero' (got %r)" % (mv,))
+    out["spec_mask_value"] = mv
+    for k in spec:
+        if k.startswith("video_") and not video:
+            raise ValueError("spec_augment: %s needs a video stream (video_processing is None)" % k)
+        if k in ("freq_masks", "freq_width", "freq_bins", "time_masks", "time_width", "time_ratio") and not audio:
+            raise ValueError("spec_augment: %s needs an audio stream (audio_processing is None)" % k)
+    fb = spec.get("freq_bins")
+    if fb is not None:
+        if isinstance(fb, bool) or not isinstance(fb, int) or fb < 1:
+            raise ValueError("spec_augment: freq_bins must be a positive integer or None (got %r)" % (fb,))
+        if audio_processing == "wav" and fb != num_mel_bins:
+            raise ValueError("spec_augment: freq_bins is num_mel_bins (%d) with audio_processing='wav' (got %d)" % (num_mel_bins, fb))
+        if audio_processing != "wav" and audio_feat is not None and audio_feat % fb:
+            raise ValueError("spec_augment: freq_bins (%d) must divide the audio feature width (%d)" % (fb, audio_feat))
+        out["spec_freq_bins"] = fb
+    return out
 
 
 def encoder_cell_id(stream, direction, layer):
@@ -74,6 +126,20 @@ class ModelConfig:
     instance_normalisation: bool = False                            # encoder.py:51-55: instance_norm after the batch norm
     highway_encoder: bool = False                                   # cells.py:89-90: HighwayWrapper on encoder layers > 0 (wins over residual)
     residual_encoder: bool = False                                  # cells.py:91-92: ResidualWrapper on encoder layers > 0
+    # SpecAugment on the encoders' inputs in the train graph (not in the reference; csrc/specaugment.hip):
+    # `*_masks` bands / spans of up to `*_width` bins / rows, a span also of at most `*_ratio` of the utterance; every count defaults to
+    # 0 = off, and no size here is tuned.  spec_freq_bins: period of the frequency axis (0 = num_mel_bins with audio_processing='wav',
+    # else the feature width).  spec_augment_fields() turns avsr.AVSR's `spec_augment` dict into these.
+    spec_freq_masks: int = 0
+    spec_freq_width: int = 0
+    spec_freq_bins: int = 0
+    spec_time_masks: int = 0
+    spec_time_width: int = 0
+    spec_time_ratio: float = 1.0
+    spec_video_time_masks: int = 0
+    spec_video_time_width: int = 0
+    spec_video_time_ratio: float = 1.0
+    spec_mask_value: str = "mean"                                   # 'mean' (the utterance's own column mean) | 'zero'
     one_hot_embedding: bool = False      # set by engine(): embedding_size <= 0 -> tf.eye(vocab_size) decoder inputs (decoder_unimodal.py:76-77)
 
     # -- same helpers/validation rules as the reference wiring (error types as in the reference) --
@@ -123,6 +189,27 @@ class ModelConfig:
     def units(self, stream):
         return self.video_units if stream == "video" else self.audio_units
 
+    def spec_augment_args(self, stream: str) -> Optional[dict]:
+        """The draw parameters of avsr_spec_augment for this stream's input in the train graph; None = nothing to launch (the
+        switch is off, or every mask of the stream is empty by construction)."""
+        if stream not in self.streams():
+            return None
+        q16 = lambda r: int(round(r * 65536.0))
+        if stream == "video":
+            a = dict(video=True, time_masks=self.spec_video_time_masks, time_width=self.spec_video_time_width,
+                     ratio_q16=q16(self.spec_video_time_ratio))
+        else:
+            a = dict(video=False, time_masks=self.spec_time_masks, time_width=self.spec_time_width, ratio_q16=q16(self.spec_time_ratio),
+                     freq_masks=self.spec_freq_masks, freq_width=self.spec_freq_width, freq_bins=self.spec_freq_bins)
+            if not (a["freq_masks"] > 0 and a["freq_width"] > 0):
+                a.update(freq_masks=0, freq_width=0, freq_bins=0)
+        if not (a["time_masks"] > 0 and a["time_width"] > 0 and a["ratio_q16"] > 0):
+            a.update(time_masks=0, time_width=0)
+        if not a["time_masks"] and not a.get("freq_masks"):
+            return None
+        a["mean_fill"] = self.spec_mask_value == "mean"
+        return a
+
     def one_hot(self) -> bool:
         """decoder_unimodal.py:76-77: a non-positive embedding_size falls back to one-hot decoder inputs (no embedding variable)."""
         return self.one_hot_embedding or self.embedding_size <= 0
@@ -138,9 +225,13 @@ class ModelConfig:
         `params.embed` / `params.extract` convert between the two layouts; the reference's shapes are what is imported / exported."""
         r = lambda t: None if t is None else tuple(round4(u) for u in t)
         dense = self.input_dense_layers if self.input_dense_layers[0] <= 0 else tuple(round4(u) for u in self.input_dense_layers)
+        # (the period of the SpecAugment bands is settled on the reference's width, before it is padded)
+        bins = self.spec_freq_bins
+        if self.spec_freq_masks and not bins:
+            bins = self.num_mel_bins if self.audio_processing == "wav" else self.audio_feat
         return replace(self, video_units=r(self.video_units), audio_units=r(self.audio_units), decoder_units=r(self.decoder_units),
                        embedding_size=round4(self.emb_width()), video_feat=round4(self.video_feat), audio_feat=round4(self.audio_feat),
-                       input_dense_layers=dense, one_hot_embedding=self.one_hot())
+                       input_dense_layers=dense, one_hot_embedding=self.one_hot(), spec_freq_bins=bins)
 
     def feat(self, stream):
         return self.video_feat if stream == "video" else self.audio_feat
@@ -169,6 +260,35 @@ class ModelConfig:
     def output_attention(self) -> bool:
         mems = self.decoder_memories()
         return bool(mems) and mems[-1][1] in LUONG_TYPES
+
+    def _validate_spec_augment(self):
+        counts = ("spec_freq_masks", "spec_freq_width", "spec_time_masks", "spec_time_width", "spec_video_time_masks",
+                  "spec_video_time_width", "spec_freq_bins")
+        for k in counts:
+            v = getattr(self, k)
+            if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+                raise ValueError("%s must be a non-negative integer (got %r)" % (k, v))
+            if k.endswith("masks") and v > SPEC_AUGMENT_MAX_MASKS:
+                raise ValueError("%s: avsr_spec_augment draws at most %d masks of a kind (got %d)" % (k, SPEC_AUGMENT_MAX_MASKS, v))
+        for k in ("spec_time_ratio", "spec_video_time_ratio"):
+            if not 0.0 <= getattr(self, k) <= 1.0:
+                raise ValueError("%s must lie in [0, 1] (got %r)" % (k, getattr(self, k)))
+        if self.spec_mask_value not in ("mean", "zero"):
+            raise ValueError("spec_mask_value must be 'mean' or 'zero' (got %r)" % (self.spec_mask_value,))
+        if (self.spec_freq_masks or self.spec_time_masks) and self.audio_units is None:
+            raise ValueError("spec_freq_masks / spec_time_masks need an audio stream")
+        if self.spec_video_time_masks and self.video_units is None:
+            raise ValueError("spec_video_time_masks needs a video stream")
+        if self.spec_freq_bins and self.audio_units is not None:
+            P = self.spec_freq_bins
+            if self.audio_processing == "wav":
+                if P != self.num_mel_bins:
+                    raise ValueError("spec_freq_bins is num_mel_bins (%d) with audio_processing='wav' (got %d)" % (self.num_mel_bins, P))
+            # (audio_feat may already be the engine's 4-padded width, as for the waveform front-end's check below: the period
+            # must divide a width that pads to it)
+            elif not any(w % P == 0 for w in range(self.audio_feat, self.audio_feat - 4, -1)
+                         if w >= 1 and (w == self.audio_feat or (self.audio_feat % 4 == 0 and round4(w) == self.audio_feat))):
+                raise ValueError("spec_freq_bins (%d) must divide the audio feature width (%d)" % (P, self.audio_feat))
 
     def validate(self):
         if self.architecture == "lm":                                                 # avsr.LM (lm.py:275-471): labels only, no encoders
@@ -202,6 +322,7 @@ class ModelConfig:
                 raise ValueError("ctc_weight must not be negative")
             if not self.enable_attention:
                 raise NotImplementedError("use_ctc with enable_attention=False is not built")
+        self._validate_spec_augment()
         if self.optimiser not in ("Adam", "Nadam", "AdamW", "Momentum"):
             raise Exception('Unsupported optimiser, try Adam')                            # seq2seq.py:218
         for st in self.streams():                 # the wrapper flags only where the reference applies them (see `wrapped`)

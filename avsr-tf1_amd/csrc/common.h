@@ -34,6 +34,12 @@ __host__ __device__ __forceinline__ float uniform01(uint32_t seed, uint32_t stre
   return (float)(hash_u32(seed, stream, idx) >> 8) * (1.0f / 16777216.0f);
 }
 
+// RNG streams of the SpecAugment draws (csrc/specaugment.hip; config.py names the same three): above every dropout / sampling stream,
+// which are cell_id * 4 + kind with cell ids up to 43 (config.py encoder_cell_id, CELL_ID_DECODER + extra decoder layers)
+#define RNG_STREAM_SPEC_AUDIO_FREQ 200u
+#define RNG_STREAM_SPEC_AUDIO_TIME 201u
+#define RNG_STREAM_SPEC_VIDEO_TIME 202u
+
 // ---- wave64 reductions ------------------------------------------------------------------
 // __shfl_xor butterflies, distances 32 .. 1 (wave_max: the same).  NOT the summation order of wave.h's wave64_sum (DPP rows, then the four
 // row results): swapping the two changes bits, so every user keeps the one it has.

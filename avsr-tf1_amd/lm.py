@@ -95,6 +95,8 @@ class LM(object):
             raise NotImplementedError("precision=%r: the HIP engine computes in float32" % (precision,))
         if cell_type not in ('lstm', 'gru'):
             raise Exception('cell type not supported: {}'.format(cell_type))                      # cells.py:44
+        if kwargs.get('spec_augment') is not None:
+            raise ValueError("spec_augment: the language model has no encoder input to augment")
         reverse = {v: k for k, v in self._unit_dict.items()}
         common = dict(architecture='lm', video_units=None, audio_units=None, cell_type=cell_type,
                       decoder_units=tuple(decoder_units_per_layer), embedding_size=embedding_size,

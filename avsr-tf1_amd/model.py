@@ -228,6 +228,18 @@ class Seq2SeqModel(EncoderMixin, DecoderMixin, RescoreMixin):
                 E["xi"], E["in_mean"], E["in_invstd"], E["in_dg"], E["in_db"] = z(B * T, F), z(B, F), z(B, F), z(B, F), z(B, F)
             if s == "audio" and self.audio_fe is not None:
                 E["wav_x"], E["wav_len"] = z(B, T, F), torch.zeros(B, dtype=torch.int32, device=dev)   # the front-end's features / row counts
+            if not greedy and cfg.spec_augment_args(s) is not None:   # spec_augment: the stream's augmented input (train graph only)
+                cnn_fed = s == "video" and self.use_cnn              # lip crops: a frame is a row of H * W * C columns
+                w_in = int(np.prod(cfg.video_hw)) if cnn_fed else self.cfg_tf.feat(s)
+                sa = cfg.spec_augment_args(s)
+                if not ops.spec_augment_supported(B, T, w_in if cnn_fed else F, sa.get("freq_masks", 0), sa["time_masks"]):
+                    from .config import SPEC_AUGMENT_MAX_MASKS, SPEC_AUGMENT_MAX_T
+                    raise ValueError("spec_augment: avsr_spec_augment covers inputs of up to %d rows, %d masks of a kind and fewer than "
+                                     "2^31 elements (got the %s input [%d, %d, %d])"
+                                     % (SPEC_AUGMENT_MAX_T, SPEC_AUGMENT_MAX_MASKS, s, B, T, w_in if cnn_fed else F))
+                E["sa_in"], E["sa_x"] = w_in, z(B, T, w_in if cnn_fed else F)
+                if cfg.spec_mask_value == "mean":
+                    E["sa_ws"] = z((ops.spec_augment_ws_floats(B, T, w_in) + 3) // 4 * 4)
             if s == "video" and self.use_cnn:
                 if cfg.video_processing == "3dconv_cnn":
                     from .cnn3d import LipCNN3D

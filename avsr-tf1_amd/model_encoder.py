@@ -275,15 +275,31 @@ class EncoderMixin:
         self.audio_fe.forward(x, batch.audio_len, E["wav_x"], E["wav_len"])
         return E["wav_x"], E["wav_len"]
 
+    def _spec_augment(self, E, x, len_t, s):
+        """spec_augment, train graph: x [B, T, >= E["sa_in"]] under this step's key (self.seed) -> the workspace's augmented copy, padding
+        columns and rows beyond each utterance zero (so it stands in for _fit_width); the batch itself is never written."""
+        B, T = E["sa_x"].shape[:2]
+        assert x.shape[:2] == (B, T) and x.is_contiguous() and x.dtype == torch.float32
+        ops.spec_augment(x.view(B, T, -1), E["sa_in"], len_t, self.seed, E["sa_x"], E.get("sa_ws"), **self.cfg.spec_augment_args(s))
+        return E["sa_x"]
+
     def _bn_sync_x(self, batch, s):
         x = batch.video if s == "video" else batch.audio
         F = self.cfg.feat(s)
-        if (s == "audio" and self.audio_fe is not None) or x.shape[-1] != F:
+        aug = self.cfg.spec_augment_args(s) is not None
+        if (s == "audio" and self.audio_fe is not None) or x.shape[-1] != F or aug:
             B, L = batch.labels.shape
             ws = self._get_ws(B, self._audio_rows(batch), batch.video.shape[1] if batch.video is not None else 0, L, False)
+            len_t = batch.video_len if s == "video" else batch.audio_len
             if s == "audio" and self.audio_fe is not None:
-                x, _ = self._wav_features(ws["enc"][s], batch)    # (computed again in _encode: 76 MB of traffic against a collective)
-            else:
+                x, len_t = self._wav_features(ws["enc"][s], batch)    # (computed again in _encode: 76 MB of traffic against a collective)
+            if aug:
+                # the moments are those of the AUGMENTED input under this step's key: forward_train refreshes the key only later, to the
+                # same value (the step counter moves in apply_update alone), and _encode then repeats this launch -- same kernel, same
+                # inputs, same key, no atomics: the same bits
+                ops.add_int(self.step, int(self.seed_offset), self.seed)
+                x = self._spec_augment(ws["enc"][s], x, len_t, s)
+            elif not (s == "audio" and self.audio_fe is not None):
                 x = self._fit_width(ws["enc"][s], x, s)
         assert x.is_contiguous() and x.dtype == torch.float32 and x.shape[-1] == F
         return x, x.shape[0] * x.shape[1], F
@@ -350,11 +366,16 @@ class EncoderMixin:
             len_t = batch.video_len if s == "video" else batch.audio_len
             if s == "audio" and self.audio_fe is not None:             # samples -> the dataset writer's log-mel features
                 x, len_t = self._wav_features(E, batch)
+            aug = training and "sa_x" in E                             # spec_augment: the train graph alone (an evaluation workspace has no buffer)
             if "cnn" in E:                                           # avsr/avsr.py:684-696: frames -> visual features
                 Hh, Ww, Cc = cfg.video_hw
                 assert x.shape == (B, T, Hh, Ww, Cc) and x.is_contiguous() and x.dtype == torch.float32
+                if aug:                                              # (the CNN's weight gradients read what forward was given)
+                    x = self._spec_augment(E, x, len_t, s)
                 x = E["cnn"].forward(x.view(B * T, Hh, Ww, Cc), training).view(B, T, F)
-            if "cnn" not in E:
+            elif aug:
+                x = self._spec_augment(E, x, len_t, s)                # (writes the zero padding columns itself)
+            else:
                 x = self._fit_width(E, x, s)                          # reference-width features: copied next to zero padding columns
             assert x.shape == (B, T, F) and x.is_contiguous() and x.dtype == torch.float32
             E["x"], E["len"] = x, len_t

@@ -873,6 +873,29 @@ def logmel_fwd(spec, tables, wav, wav_len, out, out_len=None):
     check(_L().avsr_logmel_fwd(C.byref(a), _s()), "avsr_logmel_fwd")
 
 
+def spec_augment_supported(B, T, F, freq_masks, time_masks):
+    """Host-side: does avsr_spec_augment run this shape (include/avsr_hip.h AVSR_SPEC_AUGMENT_MAX_*)?"""
+    return bool(_L().avsr_spec_augment_supported(int(B), int(T), int(F), int(freq_masks), int(time_masks)))
+
+
+def spec_augment_ws_floats(B, T, F_in):
+    return int(_L().avsr_spec_augment_ws_floats(int(B), int(T), int(F_in)))
+
+
+def spec_augment(x, F_in, lens, seed, y, ws, video=False, freq_masks=0, freq_width=0, freq_bins=0, time_masks=0, time_width=0,
+                 ratio_q16=65536, mean_fill=True):
+    """avsr_spec_augment: x [B, T, ld] (its first F_in columns are the features) -> y [B, T, F], every element written; lens [B] int32
+    and seed [1] int32 are read on the device.  ws: spec_augment_ws_floats(B, T, F_in) floats (mean_fill only)."""
+    assert x.dim() == 3 and y.dim() == 3 and x.is_contiguous() and y.is_contiguous() and x.dtype == y.dtype == torch.float32
+    assert x.shape[:2] == y.shape[:2] and F_in <= x.shape[2] and F_in <= y.shape[2] and x.data_ptr() != y.data_ptr()
+    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() == x.shape[0] and seed.dtype == torch.int32
+    a = _lib.SpecAugmentArgs(B=x.shape[0], T=x.shape[1], F_in=int(F_in), F=y.shape[2], freq_masks=int(freq_masks), freq_width=int(freq_width),
+                             freq_bins=int(freq_bins), time_masks=int(time_masks), time_width=int(time_width), ratio_q16=int(ratio_q16),
+                             video=int(bool(video)), mean_fill=int(bool(mean_fill)), ld=x.shape[2], x=fptr(x), len=fptr(lens),
+                             seed=fptr(seed), y=fptr(y), ws=fptr(ws), ws_floats=0 if ws is None else ws.numel())
+    check(_L().avsr_spec_augment(C.byref(a), _s()), "avsr_spec_augment")
+
+
 def conv3d_bn_finalize(part, nparts, Cn, count, eps, momentum, mean, invstd, mov_mean, mov_var, gamma=None, beta=None, scale=None, shift=None):
     """avsr_bn_finalize with the biased moving variance of the non-fused (rank-5) batch norm."""
     check(_L().avsr_conv3d_bn_finalize(fptr(part), int(nparts), int(Cn), int(count), float(eps), float(momentum), fptr(mean), fptr(invstd),

@@ -959,6 +959,39 @@ typedef struct avsr_logmel_args {
 } avsr_logmel_args;
 int avsr_logmel_supported(int32_t frame_length, int32_t fft_length, int32_t num_mel_bins, int32_t window, int32_t stride);
 int avsr_logmel_fwd(const avsr_logmel_args* a, void* stream);
+/* ---- SpecAugment on an encoder's input (spec_augment; not in the reference; csrc/specaugment.hip; the rule is INTEGRATION.md
+ * section 8).  x [B, T, F_in] with row stride ld (utterances T * ld apart) -> y [B, T, F] contiguous, F >= F_in, y != x.  EVERY element
+ * of y is written: unmasked elements are copied bit for bit, columns >= F_in and rows >= n_b = clamp(len[b], 0, T) are zero; x is
+ * never written.  All arithmetic of the draw is uint32, h(i) = hash_u32(seed[0], STREAM, i) (seed: DEVICE word, the step's key):
+ *   time mask k < time_masks   cap = min(time_width, (n_b * ratio_q16) >> 16), w = h((b*64 + k)*2) % (cap + 1),
+ *                              t0 = h((b*64 + k)*2 + 1) % (n_b - w + 1): rows t0 <= t < t0 + w
+ *   band k < freq_masks        cap = min(freq_width, P), P = freq_bins, w and f0 likewise with P for n_b: columns with
+ *                              f0 <= c % P < f0 + w (the same bin of every stacked frame)
+ *   STREAM                     video == 0: 200 for the bands, 201 for the time masks; video == 1 (time masks only): 202 -- above every
+ *                              dropout / sampling stream (cell id * 4 + kind, cell ids up to 43)
+ *   fill                       mean_fill == 0: 0.  mean_fill == 1: the utterance's own mean of that column over its n_b rows of x
+ *                              (per-chunk fp32 partial sums, added in chunk order in fp64, rounded once): masks are a plain union
+ * ws: avsr_spec_augment_ws_floats(B, T, F_in) floats, 16-byte aligned (mean_fill == 1 only; may be NULL otherwise).  One launch for
+ * mean_fill == 0, three for 1; no atomics (two launches on the same inputs are bit-identical), no host read, no memset / memcpy:
+ * safe under stream capture.  Covered (avsr_spec_augment_supported): T <= 65535 (the n_b * ratio_q16 product), at most 8 masks of a
+ * kind, B <= 65535, B * T * F < 2^31; otherwise AVSR_ERR_UNSUPPORTED (-3).  ratio_q16 = round(ratio * 65536) in [0, 65536]. */
+#define AVSR_SPEC_AUGMENT_MAX_MASKS 8
+#define AVSR_SPEC_AUGMENT_MAX_T 65535
+typedef struct avsr_spec_augment_args {
+  int32_t B, T, F_in, F;
+  int32_t freq_masks, freq_width, freq_bins, time_masks;
+  int32_t time_width, ratio_q16, video, mean_fill;
+  int64_t ld;
+  const float* x;
+  const int32_t* len;
+  const int32_t* seed;
+  float* y;
+  float* ws;
+  int64_t ws_floats;
+} avsr_spec_augment_args;
+int avsr_spec_augment_supported(int32_t B, int32_t T, int32_t F, int32_t freq_masks, int32_t time_masks);
+int64_t avsr_spec_augment_ws_floats(int32_t B, int32_t T, int32_t F_in);
+int avsr_spec_augment(const avsr_spec_augment_args* a, void* stream);
 /* ---- CTC auxiliary loss on an encoder's outputs (use_ctc; not in the reference; csrc/ctc.hip).  z [B*T, C] with row stride ld are the
  * head's logits, C = vocab_size + 1 and the BLANK IS CLASS C - 1 (tf.nn.ctc_loss's convention); columns >= C of a wider row are never
  * read or written.  Utterance b: target labels[b, :U_b] with U_b = max(min(labels_len[b], L) - 1, 0) (the label row without its EOS),
