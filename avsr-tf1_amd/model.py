@@ -5,6 +5,10 @@ All arithmetic runs in hand-written HIP kernels (csrc/); this file only owns buf
 as containers) and the order of calls.  There is no CPU fallback: without the library / a GPU every
 entry point raises.
 
+The class is assembled from mixins: model_encoder.py (encoders), model_decoder.py (attention block, decoder, greedy and beam-search
+decodes), model_ctc.py (CTC head, its loss and its decodes), model_rescore.py (attention rescoring) and model_base.py (EvalMixin: the
+steps the evaluation decodes share, the persistent kernels' redo path).
+
 Reference call sites mirrored here:
   encoders            avsr/seq2seq.py:30-68  -> avsr/encoder.py:37-55 (BN), :67-143 (uni/bi RNN), :173-189 (AU loss)
   AV-Align            avsr/encoder.py:224-294
@@ -25,13 +29,14 @@ import torch
 from . import ops, params as PR
 from ._lib import AttnRnn, RnnStack
 from .config import ATT_CODE, BAHDANAU_TYPES, CELL_ID_DECODER, LUONG_TYPES, ModelConfig, encoder_cell_id
-from .model_base import Batch, Ref, SeqBuf, _FlagReader, _PtrView, _splitk, desc_steplen  # noqa: F401  (re-exported: the public names live here)
+from .model_base import Batch, EvalMixin, Ref, SeqBuf, _FlagReader, _PtrView, _splitk, desc_steplen  # noqa: F401  (re-exported: the public names live here)
+from .model_ctc import CtcMixin
 from .model_decoder import DecoderMixin
 from .model_encoder import EncoderMixin
 from .model_rescore import RescoreMixin
 
 
-class Seq2SeqModel(EncoderMixin, DecoderMixin, RescoreMixin):
+class Seq2SeqModel(EncoderMixin, DecoderMixin, CtcMixin, RescoreMixin, EvalMixin):
     def __init__(self, cfg: ModelConfig, device="cuda", seed=0, weights: Optional[Dict[str, np.ndarray]] = None):
         cfg.validate()
         if not torch.cuda.is_available():

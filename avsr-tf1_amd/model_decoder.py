@@ -1,5 +1,7 @@
 """Decoder half of the engine (mixin of model.Seq2SeqModel): the attention-wrapped block descriptor (avsr_attn_rnn) shared by the decoder and the AV-Align
 attentive layer, its backward pass, the decoder's initial state, and the evaluation decodes (greedy, beam search, alignment history).
+The steps they share with the CTC decodes and attention rescoring (evaluation prologue, redo wrapper, language-model weights) are
+model_base.EvalMixin's; the CTC head that joint scoring reads is model_ctc.py's.
 Reference: avsr/decoder_unimodal.py, avsr/decoder_bimodal.py, avsr/attention.py:132-191, avsr/encoder.py:224-294."""
 from collections import OrderedDict
 from dataclasses import dataclass
@@ -369,6 +371,14 @@ class DecoderMixin:
             return D["att"].mat(0), D["A"]
         return D["cell_out"].mat(0), D["H"]
 
+    def _set_output_head(self, d):
+        """The output layer inside the step kernels (sampling, greedy, beam search): which vector it consumes, the input table the
+        chosen id is looked up in, the transposed output kernel and its bias."""
+        d.output_attention = int(self.cfg.output_attention())
+        d.embedding = ops.fptr(*self._emb())
+        d.wout_t = ops.fptr(self.derived, self.Tr["dec/out/kernel"].off)
+        d.bout = ops.fptr(self.params, self.P["dec/out/bias"].off)
+
     def _decoder_train_pass(self, ws, D, labels, labels_len, sampling, with_bwd=True, prepare=True, logits=None):
         """The train graph's decoder on the label rows `labels` [B, L] (fed GO-prefixed): embedding, hoisted input products, the
         attention-wrapped block in mode 0 (teacher forcing; mode 2 when `sampling`) and the output layer into `logits` (default: the
@@ -401,15 +411,12 @@ class DecoderMixin:
             self._block_prepare(ws, D)
         D["desc"] = d = self._block_desc(ws, D, labels_len, 2 if sampling else 0, D["h0"], D["c0"], with_bwd=with_bwd)
         if sampling:
-            d.output_attention = int(cfg.output_attention())
+            self._set_output_head(d)
             d.seed = ops.fptr(self.seed)
             d.sampling_prob = cfg.sampling_probability
             if not self._bdrop(D):
                 d.keep_in = d.keep_state = d.keep_out = 1.0
                 d.cell_id = CELL_ID_DECODER
-            d.embedding = ops.fptr(*self._emb())
-            d.wout_t = ops.fptr(self.derived, self.Tr["dec/out/kernel"].off)
-            d.bout = ops.fptr(self.params, self.P["dec/out/bias"].off)
             d.logits, d.xs, d.labels, d.fed = ops.fptr(logits), ops.fptr(D["xemb"]), ops.fptr(labels), ops.fptr(D["fed"])
         ops.attn_rnn_fwd(d, 0, L)
         if not sampling:
@@ -422,10 +429,7 @@ class DecoderMixin:
         results are invalid: check_persistent() has then switched the one-launch paths off and the pass is redone with one launch
         per step (the ids written to .mlf files and error rates never come from a flagged pass); the redo carries `lm` and `ctc_weight`
         along."""
-        out = self._beam_search_decode(*args, **kw)
-        if self.check_persistent():
-            out = self._beam_search_decode(*args, **kw)
-        return out
+        return self._redo_if_flagged(self._beam_search_decode, *args, **kw)
 
     def greedy_decode(self, *args, lm=None, ctc_weight=0.0, **kw):
         """See _greedy_decode; redone through the per-step launches if a persistent kernel flagged its pass (as above)."""
@@ -433,10 +437,7 @@ class DecoderMixin:
             raise ValueError("greedy_decode: language-model fusion is defined on the beam (beam_search_decode(lm=...))")
         if ctc_weight != 0.0:
             raise ValueError("greedy_decode: joint CTC / attention scoring is defined on the beam (beam_search_decode(ctc_weight=...))")
-        out = self._greedy_decode(*args, **kw)
-        if self.check_persistent():
-            out = self._greedy_decode(*args, **kw)
-        return out
+        return self._redo_if_flagged(self._greedy_decode, *args, **kw)
 
     def _beam_search_decode(self, batch: Batch, beam_width: int = 10, length_penalty_weight: Optional[float] = None,
                             max_steps: Optional[int] = None, check_every: int = 8, return_all: bool = False, lm=None,
@@ -449,9 +450,7 @@ class DecoderMixin:
         ctc_weight > 0 (a use_ctc model): joint CTC / attention scoring -- the step score also gets ctc_weight * (psi(g . v) - psi(g)),
         the CTC head's prefix score of the continuation against the beam's (avsr_beam_ctc; csrc/beam_ctc.hip).  0 launches nothing new."""
         cfg, K = self.cfg, int(beam_width)
-        ctc_weight = float(ctc_weight)
-        if not ctc_weight >= 0.0 or ctc_weight == float("inf"):
-            raise ValueError("beam search: ctc_weight must be a finite number >= 0 (got %r)" % (ctc_weight,))
+        ctc_weight = self._require_weight("beam search", "ctc_weight", float(ctc_weight))
         if ctc_weight != 0.0 and not cfg.use_ctc:
             raise ValueError("beam search: ctc_weight needs a model built with use_ctc=True")
         if lm is not None:
@@ -460,14 +459,9 @@ class DecoderMixin:
             # beam_step_kernel keeps the K * V candidates of an utterance in registers, four per thread of one workgroup
             raise ValueError("beam search: beam_width must be in 1..64 with beam_width * vocabulary <= 1024 (got %d x %d); "
                              "the reference's default width 10 fits every shipped unit list" % (K, cfg.vocab_size))
-        B = (batch.audio if batch.audio is not None else batch.video if batch.video is not None else batch.labels).shape[0]
         L = cfg.max_label_length if max_steps is None else max_steps
         w = length_penalty_weight if length_penalty_weight is not None else (0.5 if cfg.architecture == "bimodal" else 0.6)
-        Ta = self._audio_rows(batch)
-        Tv = batch.video.shape[1] if batch.video is not None else 0
-        ws = self._get_ws(B, Ta, Tv, 1, True)                  # encoders at batch B (decoder block of this ws is unused)
-        self._refresh_derived()
-        self._encode(ws, batch, False)
+        ws, B, Ta, Tv = self._eval_encode(batch)               # encoders at batch B (decoder block of this ws is unused)
         # tile_batch (attention.py:100-106): the decoder block runs on B*K rows and the final states are repeated K times; the MEMORIES
         # are not copied -- hypothesis row r attends memory row r // K (avsr_attn_rnn.mem_shared): keys are computed once per
         # utterance and the K hypotheses of an utterance read the same bytes (tiled: K x 75 MB streamed from HBM every step)
@@ -516,33 +510,20 @@ class DecoderMixin:
         self._decoder_init_state(wsb)
         self._block_prepare(wsb, D)
         d = self._block_desc(wsb, D, D["steplen"], 3, D["h0"], D["c0"], with_bwd=False)
-        d.output_attention = int(cfg.output_attention())
-        d.embedding = ops.fptr(*self._emb())
-        d.wout_t = ops.fptr(self.derived, self.Tr["dec/out/kernel"].off)
-        d.bout = ops.fptr(self.params, self.P["dec/out/bias"].off)
+        self._set_output_head(d)
         d.logits, d.tok, d.n_unfinished = ops.fptr(D["logits"]), ops.fptr(D["tok"]), ops.fptr(D["nunf"])
         d.beam_width, d.length_penalty, d.mem_shared = K, float(w), 1
         d.beam_logp, d.beam_fin, d.beam_len = ops.fptr(logp), ops.fptr(fin), ops.fptr(ln)
         d.step_ids, d.parent_ids, d.parent_rows = ops.fptr(sid), ops.fptr(pid), ops.fptr(prow)
-        # steps are launched in chunks of check_every; the "every beam finished" flag of a chunk is read while the NEXT chunk is already
-        # queued (the read would otherwise leave the GPU idle for a host round trip per chunk).  A chunk past the end is harmless:
-        # a beam step whose predecessor left no unfinished beam hands its input state through unchanged (beam_step_kernel), and T
-        # below comes from the per-step counters.
-        fr = self._flag_reader()
-        l, pending = 0, False
-        while l < L:
-            l1 = min(L, l + check_every)
+
+        def launch(l, l1):
             if cd is not None:
                 ops.attn_rnn_fwd_ctc(d, lmd, cd, l, l1)
             elif lmd is None:
                 ops.attn_rnn_fwd(d, l, l1)
             else:
                 ops.attn_rnn_fwd_lm(d, lmd, l, l1)
-            if pending and fr.value() == 0:
-                l = l1
-                break
-            fr.request(D["nunf"][l1 - 1:l1])
-            pending, l = True, l1
+        l = self._run_chunks(L, check_every, launch, lambda l1: D["nunf"][l1 - 1:l1])      # (T below comes from the per-step counters)
         # dynamic_decode stops right after the first step at which every beam is finished
         hist = D["nunf"][:l].cpu().numpy()
         done = np.nonzero(hist == 0)[0]
@@ -570,21 +551,14 @@ class DecoderMixin:
     def _beam_lm_desc(self, lm, lm_weight, X, R):
         """avsr_beam_lm over the language model's own (4-padded) weights; its state ping-pong and log-probability scratch live in the
         cached beam workspace X, keyed by the model's shape."""
-        lc, dev = lm.cfg, self.dev
-        nl, H, E, V = len(lc.decoder_units), lc.decoder_units[0], lc.embedding_size, lc.vocab_size
-        lm._refresh_derived()
+        m, dev = BeamLm(), self.dev
+        self._fill_lm_weights(m, lm)
+        nl, H, V = m.n_layers, m.H, m.V
         key = ("lm", nl, H)
         if key not in X:
             X[key] = dict(c=torch.zeros(2, nl, R, H, device=dev), h=torch.zeros(2, nl, R, H, device=dev), logp=torch.zeros(R, V, device=dev))
         buf = X[key]
-        m = BeamLm()
-        m.n_layers, m.H, m.E, m.V, m.one_hot, m.n_rows, m.lm_weight = nl, H, E, V, int(lm.onehot is not None), R, float(lm_weight)
-        m.embedding = ops.fptr(*lm._emb())
-        for j in range(nl):
-            m.wt[j] = ops.fptr(lm.derived, lm.Tr["dec/l%d/kernel" % j].off)
-            m.bias[j] = ops.fptr(lm.params, lm.P["dec/l%d/bias" % j].off)
-        m.wout_t = ops.fptr(lm.derived, lm.Tr["dec/out/kernel"].off)
-        m.bout = ops.fptr(lm.params, lm.P["dec/out/bias"].off)
+        m.n_rows, m.lm_weight = R, float(lm_weight)
         m.state_c, m.state_h, m.lm_logp = ops.fptr(buf["c"]), ops.fptr(buf["h"]), ops.fptr(buf["logp"])
         if not ops.beam_lm_supported(m):
             raise ValueError("beam search: the language model's shape is outside avsr_beam_lm_supported")
@@ -623,16 +597,29 @@ class DecoderMixin:
             self._fr = _FlagReader(self.dev)
         return self._fr
 
+    def _run_chunks(self, L, check_every, launch, flag):
+        """The step loop of greedy and beam search: launch(l, l1) queues steps l .. l1 - 1 in chunks of check_every, flag(l1) gives the
+        one-element device count of what the chunk left unfinished.  A chunk's count is read while the NEXT chunk is already queued (the
+        read would otherwise leave the GPU idle for a host round trip per chunk).  A chunk past the end is harmless: a beam step whose
+        predecessor left no unfinished beam hands its input state through unchanged (beam_step_kernel); greedy's finished rows are frozen
+        (impute_finished) and its t_out is the longest row.  Returns the number of steps queued."""
+        fr = self._flag_reader()
+        l, pending = 0, False
+        while l < L:
+            l1 = min(L, l + check_every)
+            launch(l, l1)
+            if pending and fr.value() == 0:      # nothing was left unfinished by the end of the previous chunk
+                l = l1
+                break
+            fr.request(flag(l1))
+            pending, l = True, l1
+        return l
+
     def _greedy_decode(self, batch: Batch, max_steps: Optional[int] = None, check_every: int = 8):
         """Eval graph with GreedyEmbeddingHelper (decoder_unimodal.py:176-217): int32 ids [B, T_out], zeros after EOS."""
         cfg = self.cfg
-        B = (batch.audio if batch.audio is not None else batch.video if batch.video is not None else batch.labels).shape[0]
         L = cfg.max_label_length if max_steps is None else max_steps
-        Ta = self._audio_rows(batch)
-        Tv = batch.video.shape[1] if batch.video is not None else 0
-        ws = self._get_ws(B, Ta, Tv, L, True)
-        self._refresh_derived()
-        self._encode(ws, batch, False)
+        ws = self._eval_encode(batch, L)[0]
         D = ws["dec"]
         self._decoder_init_state(ws)
         self._block_prepare(ws, D)
@@ -641,28 +628,17 @@ class DecoderMixin:
         D["ids"].zero_()
         D["logits"].zero_()          # a group of the fused kernel that exits early leaves its later steps unwritten: zeros, not a previous batch's logits
         d = self._block_desc(ws, D, D["steplen"], 1, D["h0"], D["c0"], with_bwd=False)
-        d.output_attention = int(cfg.output_attention())
-        d.embedding = ops.fptr(*self._emb())
-        d.wout_t = ops.fptr(self.derived, self.Tr["dec/out/kernel"].off)
-        d.bout = ops.fptr(self.params, self.P["dec/out/bias"].off)
+        self._set_output_head(d)
         d.logits, d.ids, d.tok, d.n_unfinished = ops.fptr(D["logits"]), ops.fptr(D["ids"]), ops.fptr(D["tok"]), ops.fptr(D["nunf"])
-        # chunks of check_every steps; a chunk's "unfinished" count is read after the next chunk has been queued (no idle GPU while the
-        # host waits).  Steps past the end change nothing: finished rows are frozen (impute_finished) and t_out is the longest row.
         # The fused persistent decode kernel stops by itself, group by group, once every utterance of a group has emitted EOS
         # (dec_persist.hip): all maximum_iterations steps are then ONE launch and the host never looks at the device in between.
         if self.fused_decode and ops.attn_rnn_fused_fwd_active(d):
             check_every = L
-        fr = self._flag_reader()
-        l, pending = 0, False
-        while l < L:
-            l1 = min(L, l + check_every)
-            ops.attn_rnn_fwd(d, l, l1)
-            if pending and fr.value() == 0:      # all utterances had emitted EOS by the end of the previous chunk
-                l = l1
-                break
+
+        def flag(l1):
             ops.copy_(D["nunf_prev"], D["nunf"])                         # this chunk's count (the next call resets the counter)
-            fr.request(D["nunf_prev"])
-            pending, l = True, l1
+            return D["nunf_prev"]
+        l = self._run_chunks(L, check_every, lambda l, l1: ops.attn_rnn_fwd(d, l, l1), flag)
         t_out = min(int(D["steplen"].max().item()), l)   # dynamic_decode stops once every utterance has finished
         self._last_greedy = (ws, t_out)
         self._last_align = None

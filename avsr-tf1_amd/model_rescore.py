@@ -1,11 +1,10 @@
 """Attention rescoring of the CTC n-best (mixin of model.Seq2SeqModel): the two-pass decode of a hybrid CTC / attention model.  The CTC
-head's prefix beam search (csrc/ctc_prefix.hip) proposes, the attention decoder scores every proposal teacher-forced (the train graph's
+head's prefix beam search (csrc/ctc_prefix.hip, model_ctc.py) proposes, the attention decoder scores every proposal teacher-forced (the train graph's
 decoder block, mode 0, evaluation settings), avsr_seq_logprob / avsr_rescore_select (csrc/rescore.hip) score and choose.  The rule is this
 project's own: INTEGRATION.md section 8.  No reference counterpart."""
 import numpy as np
 import torch
 from . import ops
-from ._lib import CTC_PREFIX_MAX_L, CTC_PREFIX_MAX_V, CTC_PREFIX_MAX_W
 
 RESCORE_MAX_BLOCKS = 4        # decoder blocks (one per padded hypothesis length and width) an encoder workspace keeps
 
@@ -26,10 +25,7 @@ class RescoreMixin:
         The label rows are padded to Lh = the batch's longest hypothesis + 1 ROUNDED UP TO A MULTIPLE OF 8, which bounds the number of
         decoder blocks a workspace ever sees (the RESCORE_MAX_BLOCKS most recent are kept).
         A pass a persistent kernel flagged is redone through the per-step launches, as for the other decodes."""
-        out = self._attention_rescoring(batch, beam_width, max_steps, ctc_weight, nbest)
-        if self.check_persistent():
-            out = self._attention_rescoring(batch, beam_width, max_steps, ctc_weight, nbest)
-        return out
+        return self._redo_if_flagged(self._attention_rescoring, batch, beam_width, max_steps, ctc_weight, nbest)
 
     def _attention_rescoring(self, batch, beam_width, max_steps, ctc_weight, nbest):
         cfg, dev = self.cfg, self.dev
@@ -37,30 +33,14 @@ class RescoreMixin:
             raise ValueError("attention_rescoring: architecture='lm' has no encoder, so no CTC head whose n-best could be rescored")
         if not cfg.use_ctc:
             raise ValueError("attention_rescoring needs a model built with use_ctc=True: the hypotheses are the CTC head's n-best")
-        w = float(ctc_weight)
-        if not w >= 0.0 or w == float("inf"):
-            raise ValueError("attention_rescoring: ctc_weight must be a finite number >= 0 (got %r)" % (ctc_weight,))
+        w = self._require_weight("attention_rescoring", "ctc_weight", ctc_weight)
         K, V = int(beam_width), cfg.vocab_size
         Lm = int(cfg.max_label_length if max_steps is None else max_steps)
-        if K < 1 or Lm < 1:
-            raise ValueError("attention_rescoring: beam_width and max_steps must be positive (got %d, %d)" % (K, Lm))
-        if not ops.ctc_prefix_search_supported(V, K, Lm):
-            raise ValueError("attention_rescoring: avsr_ctc_prefix_search covers vocabularies of up to %d symbols, beam widths of up to "
-                             "%d and label sequences of up to %d (got %d, %d, %d)"
-                             % (CTC_PREFIX_MAX_V, CTC_PREFIX_MAX_W, CTC_PREFIX_MAX_L, V, K, Lm))
-        B = (batch.audio if batch.audio is not None else batch.video).shape[0]
-        Ta = self._audio_rows(batch)
-        Tv = batch.video.shape[1] if batch.video is not None else 0
-        ws = self._get_ws(B, Ta, Tv, 1, True)                  # encoders at batch B (the decoder block of this workspace is unused)
-        self._refresh_derived()
-        self._encode(ws, batch, False)
+        self._require_ctc_prefix_shape("attention_rescoring", V, K, Lm)
+        ws, B, Ta, Tv = self._eval_encode(batch)               # encoders at batch B (the decoder block of this workspace is unused)
         # ---- first pass: the head's n-best, as ctc_prefix_beam_search(nbest=True) (same buffers) ---------------------------------
         E, Cc = self._ctc_head(ws)
-        key = ("ctc_prefix", K, Lm)
-        if key not in E:
-            E[key] = (torch.zeros(B, K, Lm, dtype=torch.int32, device=dev), torch.zeros(B, K, dtype=torch.int32, device=dev),
-                      torch.zeros(B, K, device=dev))
-        ids_d, lens_d, s_ctc_d = E[key]
+        ids_d, lens_d, s_ctc_d = self._ctc_nbest_buffers(E, B, K, Lm)
         ops.ctc_prefix_search(E["ctc_z"], Cc, E["len"], B, E["T"], V, K, Lm, ids_d, lens_d, s_ctc_d)
         ids, lens, s_ctc = ids_d.cpu().numpy(), lens_d.cpu().numpy(), s_ctc_d.cpu().numpy()
         real = s_ctc > float("-inf")                           # empty slots are not hypotheses
