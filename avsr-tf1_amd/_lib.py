@@ -198,6 +198,12 @@ class CtcPrefixNgram(C.Structure):
                [(n, C.c_void_p) for n in ("bow", "backoff", "arc_begin", "sym", "logp", "next", "s_lm", "lm_steps", "lm_logp")]
 
 
+class BeamNgram(C.Structure):
+    """avsr_beam_ngram: the automaton of CtcPrefixNgram as beam search's fused model (csrc/beam_ngram.hip)."""
+    _fields_ = [(n, C.c_int32) for n in ("n_nodes", "n_arcs", "V", "start", "n_rows")] + [("lm_weight", C.c_float)] + \
+               [(n, C.c_void_p) for n in ("bow", "backoff", "arc_begin", "sym", "logp", "next", "node", "lm_logp")]
+
+
 CTC_ALIGN_MAX_L = 512                  # AVSR_CTC_ALIGN_MAX_L of include/avsr_hip.h
 
 
@@ -219,7 +225,7 @@ _STRUCTS = {"avsr_dec_layer": DecLayer, "avsr_mat": Mat, "avsr_gemm_desc": GemmD
             "avsr_rnn_launch": RnnLaunch,
             "avsr_conv_desc": ConvDesc, "avsr_conv_launch": ConvLaunch, "avsr_conv3d_desc": Conv3dDesc, "avsr_logmel_args": LogmelArgs, "avsr_spec_augment_args": SpecAugmentArgs, "avsr_ctc_args": CtcArgs, "avsr_attn_mech": AttnMech, "avsr_attn_rnn": AttnRnn, "avsr_transpose_job": TransposeJob,
             "avsr_colsum_job": ColsumJob, "avsr_beam_lm": BeamLm, "avsr_beam_ctc": BeamCtc, "avsr_ctc_prefix_args": CtcPrefixArgs,
-            "avsr_ctc_prefix_lm": CtcPrefixLm, "avsr_ctc_prefix_ngram": CtcPrefixNgram,
+            "avsr_ctc_prefix_lm": CtcPrefixLm, "avsr_ctc_prefix_ngram": CtcPrefixNgram, "avsr_beam_ngram": BeamNgram,
             "avsr_ctc_align_args": CtcAlignArgs}
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -286,6 +292,9 @@ _SIGS = {
     "avsr_beam_search_step_lm": [_vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp,
                                  _vp, _f32, _vp],
     "avsr_attn_rnn_fwd_lm": [C.POINTER(AttnRnn), C.POINTER(BeamLm), _i32, _i32, _vp],
+    "avsr_beam_ngram_supported": [C.POINTER(BeamNgram)],
+    "avsr_beam_ngram_step": [C.POINTER(BeamNgram), _vp, _vp, _i32, _i32, _vp],
+    "avsr_attn_rnn_fwd_ngram": [C.POINTER(AttnRnn), C.POINTER(BeamNgram), C.POINTER(BeamCtc), _i32, _i32, _vp],
     "avsr_beam_ctc_supported": [C.POINTER(BeamCtc)],
     "avsr_beam_ctc_begin": [C.POINTER(BeamCtc), _vp],
     "avsr_beam_ctc_step": [C.POINTER(BeamCtc), _vp, _vp, _vp, _i32, _vp],

@@ -24,6 +24,10 @@ Shallow fusion of a language model into beam search (not in the reference, which
 `lm_checkpoint` (a checkpoint written by `LM.train`), `lm_weight` (0.3: a conventional value, not a tuned one),
 `lm_units_per_layer` ((256,)), `lm_embedding_size` (128), `lm_cell_type` ('lstm') arrive through **kwargs; `evaluate` then scores an
 unfinished beam's continuation with log p_model + lm_weight * log p_lm (csrc/beam_lm.hip).
+`ngram_lm` (the path of an ARPA file over the units, read as `ctc_ngram_lm` below is) fuses a back-off n-gram into beam search instead,
+with the same `lm_weight`: log p_model + lm_weight * lam(v | GO, labels), one table-walk launch per step and no model to train
+(ngram.py, csrc/beam_ngram.hip).  It is refused together with `lm_checkpoint` and under any other `decoding_algorithm`; it works together
+with `ctc_decode_weight`.
 Hybrid CTC / attention training (not in the reference, which only reserves `use_ctc` in its hyper-parameters): `use_ctc` (False),
 `ctc_weight` (0.3: a conventional value, not a tuned one) arrive through **kwargs; a CTC head on the audio (else video) encoder adds
 ctc_weight * CTC loss per label token to the step's loss, and `evaluate` also reports that head's best-path error rate under the key
@@ -194,6 +198,25 @@ class AVSR(object):
                                        kwargs.get('lm_cell_type', 'lstm'))
             lm_weights = _lm.checkpoint_weights(lm_cfg, lm_checkpoint)
 
+        # back-off n-gram fused into beam search (csrc/beam_ngram.hip): parsed and compiled on the host, here, before any engine is built
+        self._ngram = None
+        ngram_lm = kwargs.get('ngram_lm')
+        if ngram_lm is not None:
+            from . import ngram as _ngram
+            from ._lib import CTC_PREFIX_NGRAM_MAX_ARCS, CTC_PREFIX_NGRAM_MAX_NODES
+            if decoding_algorithm != 'beam_search':
+                raise ValueError("ngram_lm needs decoding_algorithm='beam_search': this keyword fuses the n-gram into the attention "
+                                 "decoder's beam ('ctc_prefix_beam_search' takes ctc_ngram_lm; 'greedy' and 'attention_rescoring' take "
+                                 "no language model)")
+            if lm_checkpoint is not None:
+                raise ValueError("ngram_lm and lm_checkpoint are two language models for one search: give one of them")
+            if not self._lm_weight >= 0.0 or self._lm_weight == float('inf'):
+                raise ValueError("lm_weight must be a finite number >= 0 (got %r)" % (kwargs.get('lm_weight'),))
+            self._ngram = _ngram.load_tables(ngram_lm, self._unit_dict)             # ValueError: not an ARPA file, a token that is no unit
+            if self._ngram["n_nodes"] > CTC_PREFIX_NGRAM_MAX_NODES or self._ngram["n_arcs"] > CTC_PREFIX_NGRAM_MAX_ARCS:
+                raise ValueError("ngram_lm: avsr_beam_ngram_supported covers automata of up to %d nodes and %d arcs (got %d, %d)"
+                                 % (CTC_PREFIX_NGRAM_MAX_NODES, CTC_PREFIX_NGRAM_MAX_ARCS, self._ngram["n_nodes"], self._ngram["n_arcs"]))
+
         # language model fused into the CTC prefix search (csrc/ctc_prefix_lm.hip): its own keywords, refused on the host like lm_checkpoint
         self._ctc_lm = None
         self._ctc_lm_weight, self._ctc_lm_bonus = float(kwargs.get('ctc_lm_weight', 0.3)), float(kwargs.get('ctc_lm_length_bonus', 0.0))
@@ -224,7 +247,7 @@ class AVSR(object):
             from ._lib import CTC_PREFIX_LM_MAX_W
             if decoding_algorithm != 'ctc_prefix_beam_search':
                 raise ValueError("ctc_ngram_lm needs decoding_algorithm='ctc_prefix_beam_search': the n-gram is fused into the CTC head's "
-                                 "own search ('beam_search' and 'attention_rescoring' take no n-gram)")
+                                 "own search ('beam_search' takes ngram_lm; 'attention_rescoring' takes no n-gram)")
             if ctc_lm_checkpoint is not None:
                 raise ValueError("ctc_ngram_lm and ctc_lm_checkpoint are two language models for one search: give one of them")
             if beam_width > CTC_PREFIX_LM_MAX_W:
@@ -548,7 +571,8 @@ class AVSR(object):
         """The predictions of one batch under `decoding_algorithm`: rows of ids (a numpy array or a list of id lists)."""
         if self._decoding_algorithm == 'beam_search':     # avsr.py:58-59 default: width 10, first beam returned
             ids = self._model.beam_search_decode(batch, beam_width=self._beam_width, max_steps=self._cfg.max_label_length,
-                                                 lm=self._lm, lm_weight=self._lm_weight if self._lm is not None else 0.0,
+                                                 lm=self._lm, ngram=self._ngram,
+                                                 lm_weight=self._lm_weight if self._lm is not None or self._ngram is not None else 0.0,
                                                  ctc_weight=self._ctc_decode_weight)
         elif self._decoding_algorithm == 'attention_rescoring':        # two passes: the head's n-best, then teacher-forced scoring
             ids = self._model.attention_rescoring(batch, beam_width=self._beam_width, max_steps=self._cfg.max_label_length,

@@ -11,58 +11,29 @@
 // Phase 6 for the M <= 16 kept extensions of a frame (skipped by the search's workgroup-uniform branch when M = 0):
 //   a. thread m < M:  node[new_m] = next[arc], arc = the arc the walk for (node[parent_m], tok_m) ends on        (prologue: node[0] = start)
 //   b. M * V independent walks over the 256 threads: lam[new_m][c] = walk(node[new_m], c)
-// One walk: acc = 0; while the node has no arc for c (binary search among its sorted arcs; the ROOT holds all V classes, so there the arc
-// is index c): acc += bow[node], node = backoff[node]; then acc + logp[arc].  fp32 additions in this fixed order, plain loads and stores.
-// A walk is a chain of dependent L2 reads (arc_begin, ~log2(arcs) probes of sym, bow / backoff per level); the tables are not staged in
-// LDS.  It cannot run away on tables it was not meant for: at most AVSR_CTC_PREFIX_NGRAM_MAX_ORDER - 1 nodes are visited before the root
-// is read directly, and every node id and arc range is clamped into its table.
+// The walk itself (ngram_node / ngram_find / ngram_walk: the bounded, clamped chain of dependent L2 reads) is csrc/ngram_walk.h, shared with
+// beam search's n-gram step (csrc/beam_ngram.hip).
 #include "ctc_prefix_search.h"
+#include "ngram_walk.h"
 
 namespace avsr {
 
-__device__ __forceinline__ int cpn_node(const avsr_ctc_prefix_ngram& G, int n) { return (unsigned)n < (unsigned)G.n_nodes ? n : 0; }
-
-// the arc of class c at node n != 0, or -1
-__device__ __forceinline__ int cpn_find(const avsr_ctc_prefix_ngram& G, int n, int c) {
-  int lo = G.arc_begin[n], end = G.arc_begin[n + 1];
-  lo = lo < 0 ? 0 : lo;
-  end = end > G.n_arcs ? G.n_arcs : end;
-  int hi = end;
-  while (lo < hi) {                                                        // the first arc with sym >= c
-    const int mid = (lo + hi) >> 1;
-    if (G.sym[mid] < c) lo = mid + 1; else hi = mid;
-  }
-  return lo < end && G.sym[lo] == c ? lo : -1;
-}
-
-// lam(c | the context of node n); arc: the arc it ended on
-__device__ __forceinline__ float cpn_walk(const avsr_ctc_prefix_ngram& G, int n, int c, int& arc) {
-  float acc = 0.f;
-  for (int d = 1; d < AVSR_CTC_PREFIX_NGRAM_MAX_ORDER && n != 0; ++d) {
-    const int a = cpn_find(G, n, c);
-    if (a >= 0) { arc = a; return acc + G.logp[a]; }
-    acc += G.bow[n];
-    n = cpn_node(G, G.backoff[n]);
-  }
-  arc = c;                                                                 // the root: one arc per class, c < V <= n_arcs
-  return acc + G.logp[c];
-}
-
 // the n-gram as cp_search's Step: one node id per pool row in LDS
 struct cpn_step {
-  const avsr_ctc_prefix_ngram& G;
+  const ngram_view G;
+  const int V, start;
   int* sNode;                                                              // [2 W]
   static size_t extra(int W) { return 2 * (size_t)W; }
   __device__ __forceinline__ void init(int, int, uint32_t* words) { sNode = reinterpret_cast<int*>(words); }
   __device__ __forceinline__ void prologue(int) {}
   __device__ __forceinline__ void step(int M, const int* sTok, const int* sPar, const int* sNew, float* sLam, bool first) {
-    const int tid = threadIdx.x, V = G.V;
+    const int tid = threadIdx.x;
     if (tid < M) {
-      int node = cpn_node(G, G.start);
+      int node = ngram_node(G, start);
       if (!first) {
         int arc;
-        cpn_walk(G, cpn_node(G, sNode[sPar[tid]]), sTok[tid], arc);
-        node = cpn_node(G, G.next[arc]);
+        ngram_walk(G, ngram_node(G, sNode[sPar[tid]]), sTok[tid], arc);
+        node = ngram_node(G, G.next[arc]);
       }
       sNode[sNew[tid]] = node;
     }
@@ -70,7 +41,7 @@ struct cpn_step {
     for (int e = tid; e < M * V; e += 256) {
       const int m = e / V, c = e - m * V, nw = sNew[m];
       int arc;
-      sLam[nw * V + c] = cpn_walk(G, sNode[nw], c, arc);
+      sLam[nw * V + c] = ngram_walk(G, sNode[nw], c, arc);
     }
     lds_barrier();
   }
@@ -79,7 +50,7 @@ struct cpn_step {
 // dynamic LDS: cp_lds_words(V, W, L_max, true, 2 W) words
 __global__ __launch_bounds__(256) void ctc_prefix_ngram_kernel(const avsr_ctc_prefix_args A, const avsr_ctc_prefix_ngram G) {
   extern __shared__ __attribute__((aligned(16))) uint32_t cpn_smem[];
-  cpn_step step{G, nullptr};
+  cpn_step step{ngram_view_of(G), G.V, G.start, nullptr};
   const cp_terms terms{G.weight, G.bonus, G.go_id, G.eos_id, G.s_lm, G.lm_steps, G.lm_logp};
   cp_search(A, terms, step, cpn_smem);
 }

@@ -191,6 +191,16 @@ class EvalMixin:
             raise ValueError("%s: %s must be a finite number >= 0 (got %r)" % (who, name, value))
         return w
 
+    NGRAM_TABLES = ("bow", "backoff", "arc_begin", "sym", "logp", "next")
+
+    def _ngram_device_tables(self, ngram):
+        """The six arrays of the automaton `ngram` (ngram.compile_tables) on the device: uploaded once per model object and kept with the
+        dict they came from, for every search that fuses it (the CTC prefix search, beam search)."""
+        cache = self.__dict__.setdefault("_ngram_tables", {})
+        if id(ngram) not in cache:
+            cache[id(ngram)] = (ngram, {k: torch.as_tensor(np.ascontiguousarray(ngram[k])).to(self.dev) for k in self.NGRAM_TABLES})
+        return cache[id(ngram)][1]
+
     @staticmethod
     def _fill_lm_weights(m, lm):
         """The language model's own (4-padded) weights into a BeamLm or a CtcPrefixLm: the two descriptors share these field names."""

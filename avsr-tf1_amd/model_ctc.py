@@ -225,17 +225,12 @@ class CtcMixin:
         """avsr_ctc_prefix_search_ngram over the automaton `ngram` (ngram.compile_tables): its six arrays go to the device once per
         model object (kept with the dict they came from); s_lm and lm_steps are cached next to the ("ctc_prefix", W, Lm) buffers.
         Returns s_lm [B, W] (device)."""
-        dev = self.dev
-        cache = self.__dict__.setdefault("_ngram_tables", {})
-        if id(ngram) not in cache:
-            cache[id(ngram)] = (ngram, {k: torch.as_tensor(np.ascontiguousarray(ngram[k])).to(dev)
-                                        for k in ("bow", "backoff", "arc_begin", "sym", "logp", "next")})
-        tb = cache[id(ngram)][1]
+        tb = self._ngram_device_tables(ngram)
         buf = self._ctc_prefix_model_outputs(E, ("ctc_prefix_ngram", W, Lm), B, W)
         g = CtcPrefixNgram()
         g.n_nodes, g.n_arcs, g.V, g.start = int(ngram["n_nodes"]), int(ngram["n_arcs"]), V, int(ngram["start"])
         g.go_id, g.eos_id, g.weight, g.bonus = int(ngram["go_id"]), int(ngram["eos_id"]), lm_weight, length_bonus
-        for k in ("bow", "backoff", "arc_begin", "sym", "logp", "next"):
+        for k in self.NGRAM_TABLES:
             setattr(g, k, ops.fptr(tb[k]))
         g.s_lm, g.lm_steps = ops.fptr(buf["s_lm"]), ops.fptr(buf["steps"])
         ops.ctc_prefix_search_ngram(E["ctc_z"], Cc, E["len"], B, E["T"], V, W, Lm, ids, lens, score, g)

@@ -10,7 +10,7 @@ import os
 import numpy as np
 import torch
 from . import ops, params as PR
-from ._lib import AttnRnn, BEAM_CTC_MAX_T, BEAM_CTC_MAX_V, BeamCtc, BeamLm, MAX_LM_LAYERS, RnnStack
+from ._lib import AttnRnn, BEAM_CTC_MAX_T, BEAM_CTC_MAX_V, BeamCtc, BeamLm, BeamNgram, MAX_LM_LAYERS, RnnStack
 from .config import ATT_CODE, BAHDANAU_TYPES, CELL_ID_DECODER, LUONG_TYPES, ModelConfig, encoder_cell_id
 from .model_base import Batch, Ref, SeqBuf, _FlagReader, _PtrView, _splitk, desc_steplen  # noqa: F401
 
@@ -427,29 +427,42 @@ class DecoderMixin:
     def beam_search_decode(self, *args, **kw):
         """See _beam_search_decode.  If a persistent kernel's bounded wait expired during the pass (workgroups not co-resident) the
         results are invalid: check_persistent() has then switched the one-launch paths off and the pass is redone with one launch
-        per step (the ids written to .mlf files and error rates never come from a flagged pass); the redo carries `lm` and `ctc_weight`
-        along."""
+        per step (the ids written to .mlf files and error rates never come from a flagged pass); the redo carries `lm`, `ngram` and
+        `ctc_weight` along."""
         return self._redo_if_flagged(self._beam_search_decode, *args, **kw)
 
-    def greedy_decode(self, *args, lm=None, ctc_weight=0.0, **kw):
+    def greedy_decode(self, *args, lm=None, ctc_weight=0.0, ngram=None, **kw):
         """See _greedy_decode; redone through the per-step launches if a persistent kernel flagged its pass (as above)."""
         if lm is not None:
             raise ValueError("greedy_decode: language-model fusion is defined on the beam (beam_search_decode(lm=...))")
+        if ngram is not None:
+            raise ValueError("greedy_decode: n-gram fusion is defined on the beam (beam_search_decode(ngram=...))")
         if ctc_weight != 0.0:
             raise ValueError("greedy_decode: joint CTC / attention scoring is defined on the beam (beam_search_decode(ctc_weight=...))")
         return self._redo_if_flagged(self._greedy_decode, *args, **kw)
 
     def _beam_search_decode(self, batch: Batch, beam_width: int = 10, length_penalty_weight: Optional[float] = None,
                             max_steps: Optional[int] = None, check_every: int = 8, return_all: bool = False, lm=None,
-                            lm_weight: float = 0.0, ctc_weight: float = 0.0):
+                            lm_weight: float = 0.0, ctc_weight: float = 0.0, ngram=None):
         """Eval graph with BeamSearchDecoder (decoder_unimodal.py:222-271, decoder_bimodal.py:328-381): ids of beam 0,
         int32 [B, T_out]; positions after the first EOS hold EOS (gather_tree).  length_penalty_weight defaults to the
         reference's 0.6 (unimodal / av_align) or 0.5 (bimodal).
         lm: a Seq2SeqModel with architecture='lm' (LSTM) over the same vocabulary -- shallow fusion: an unfinished beam's step score is
         log_softmax(logits)[v] + lm_weight * log_softmax(lm logits)[v] (include/avsr_hip.h avsr_beam_lm; csrc/beam_lm.hip).
         ctc_weight > 0 (a use_ctc model): joint CTC / attention scoring -- the step score also gets ctc_weight * (psi(g . v) - psi(g)),
-        the CTC head's prefix score of the continuation against the beam's (avsr_beam_ctc; csrc/beam_ctc.hip).  0 launches nothing new."""
+        the CTC head's prefix score of the continuation against the beam's (avsr_beam_ctc; csrc/beam_ctc.hip).  0 launches nothing new.
+        ngram: instead of lm, the tables of a back-off n-gram (ngram.compile_tables / ngram.load_tables) -- the same rule with
+        lam(v | GO, labels) read from the automaton: lm_weight * lam on every symbol of an unfinished beam, EOS included, one table-walk
+        launch per step (avsr_beam_ngram; csrc/beam_ngram.hip).  The tables are uploaded once per model object; lm and ngram together
+        are refused.  It works together with ctc_weight."""
         cfg, K = self.cfg, int(beam_width)
+        if lm is not None and ngram is not None:
+            raise ValueError("beam search takes one language model: lm (an avsr.LM network) or ngram (back-off tables), not both")
+        if ngram is not None:
+            lm_weight = self._require_weight("beam search", "lm_weight", lm_weight)
+            if (ngram["V"], ngram["go_id"], ngram["eos_id"]) != (cfg.vocab_size, cfg.go_id, cfg.eos_id):
+                raise ValueError("beam search: the n-gram tables were compiled for V = %d, GO = %d, EOS = %d; the model has %d, %d, %d"
+                                 % (ngram["V"], ngram["go_id"], ngram["eos_id"], cfg.vocab_size, cfg.go_id, cfg.eos_id))
         ctc_weight = self._require_weight("beam search", "ctc_weight", float(ctc_weight))
         if ctc_weight != 0.0 and not cfg.use_ctc:
             raise ValueError("beam search: ctc_weight needs a model built with use_ctc=True")
@@ -506,7 +519,8 @@ class DecoderMixin:
         prow.copy_(X["prow0"])
         ops.zero_multi([fin, ln])
         lmd = self._beam_lm_desc(lm, lm_weight, X, R) if lm is not None else None
-        cd = self._beam_ctc_desc(ws, ctc_weight, X, B, K, lmd) if ctc_weight != 0.0 else None
+        ngd = self._beam_ngram_desc(ngram, lm_weight, X, R) if ngram is not None else None
+        cd = self._beam_ctc_desc(ws, ctc_weight, X, B, K, lmd if ngd is None else ngd) if ctc_weight != 0.0 else None
         self._decoder_init_state(wsb)
         self._block_prepare(wsb, D)
         d = self._block_desc(wsb, D, D["steplen"], 3, D["h0"], D["c0"], with_bwd=False)
@@ -517,7 +531,9 @@ class DecoderMixin:
         d.step_ids, d.parent_ids, d.parent_rows = ops.fptr(sid), ops.fptr(pid), ops.fptr(prow)
 
         def launch(l, l1):
-            if cd is not None:
+            if ngd is not None:
+                ops.attn_rnn_fwd_ngram(d, ngd, cd, l, l1)
+            elif cd is not None:
                 ops.attn_rnn_fwd_ctc(d, lmd, cd, l, l1)
             elif lmd is None:
                 ops.attn_rnn_fwd(d, l, l1)
@@ -564,9 +580,28 @@ class DecoderMixin:
             raise ValueError("beam search: the language model's shape is outside avsr_beam_lm_supported")
         return m
 
+    def _beam_ngram_desc(self, ngram, lm_weight, X, R):
+        """avsr_beam_ngram over the automaton `ngram` (its six arrays on the device once per model object, shared with the CTC prefix
+        search: _ngram_device_tables); the node ping-pong and the log-probability scratch live in the cached beam workspace X."""
+        tb, V = self._ngram_device_tables(ngram), self.cfg.vocab_size
+        if "ngram" not in X:
+            X["ngram"] = dict(node=torch.zeros(2, R, dtype=torch.int32, device=self.dev), logp=torch.zeros(R, V, device=self.dev))
+        buf = X["ngram"]
+        g = BeamNgram()
+        g.n_nodes, g.n_arcs, g.V, g.start = int(ngram["n_nodes"]), int(ngram["n_arcs"]), V, int(ngram["start"])
+        g.n_rows, g.lm_weight = R, float(lm_weight)
+        for k in self.NGRAM_TABLES:
+            setattr(g, k, ops.fptr(tb[k]))
+        g.node, g.lm_logp = ops.fptr(buf["node"]), ops.fptr(buf["logp"])
+        if not ops.beam_ngram_supported(g):
+            raise ValueError("beam search: the n-gram tables (%d nodes, %d arcs, start %d over %d symbols) are outside "
+                             "avsr_beam_ngram_supported" % (g.n_nodes, g.n_arcs, g.start, V))
+        return g
+
     def _beam_ctc_desc(self, ws, weight, X, B, K, lmd):
         """avsr_beam_ctc over the head's logits of this batch (_ctc_head, encoders in evaluation mode); log-probabilities, the state
-        ping-pong, term and the pre-combined buffer live in the cached beam workspace X.  Queues avsr_beam_ctc_begin."""
+        ping-pong, term and the pre-combined buffer live in the cached beam workspace X.  Queues avsr_beam_ctc_begin.  lmd: the fused
+        model's descriptor (a BeamLm or a BeamNgram: both carry lm_logp and lm_weight), or None."""
         cfg, dev = self.cfg, self.dev
         E, Cc = self._ctc_head(ws)
         T, V, R = E["T"], cfg.vocab_size, B * K

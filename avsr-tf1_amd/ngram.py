@@ -1,6 +1,6 @@
 """Back-off n-gram language models over the unit vocabulary, host side (numpy only; importable without a GPU): the ARPA text format in
 and out, a small estimator, and the compiler of the device automaton that the CTC prefix beam search walks inside its frame loop
-(csrc/ctc_prefix_ngram.hip; the rule is INTEGRATION.md section 8).
+(csrc/ctc_prefix_ngram.hip) and beam search walks once per decode step (csrc/beam_ngram.hip); the rules are INTEGRATION.md section 8.
 
 The model of order N over the classes 0 .. V-1 (MASK = 0, the units, EOS = V-2, GO = V-1 -- io_utils.create_unit_dict):
     context   h = the last N-1 symbols of (GO, g_0 .. g_{n-1}); empty for N = 1

@@ -212,6 +212,21 @@ def beam_lm_step(desc, tok, parent_rows, n_rows, step):
     check(_L().avsr_beam_lm_step(C.byref(desc), fptr(tok), fptr(parent_rows), int(n_rows), int(step), _s()), "avsr_beam_lm_step")
 
 
+def beam_ngram_supported(desc):
+    """Host-side: does avsr_beam_ngram_step run this descriptor (a _lib.BeamNgram)?"""
+    return bool(_L().avsr_beam_ngram_supported(C.byref(desc)))
+
+
+def beam_ngram_step(desc, tok, parent_rows, n_rows, step):
+    """One back-off n-gram step over the hypothesis rows (include/avsr_hip.h avsr_beam_ngram): writes desc.lm_logp and the other half of desc.node."""
+    check(_L().avsr_beam_ngram_step(C.byref(desc), fptr(tok), fptr(parent_rows), int(n_rows), int(step), _s()), "avsr_beam_ngram_step")
+
+
+def attn_rnn_fwd_ngram(desc, ng_desc, ctc_desc, l_begin, l_end):
+    check(_L().avsr_attn_rnn_fwd_ngram(C.byref(desc), C.byref(ng_desc), C.byref(ctc_desc) if ctc_desc is not None else None, int(l_begin),
+                                       int(l_end), _s()), "avsr_attn_rnn_fwd_ngram")
+
+
 def beam_ctc_supported(desc):
     return bool(_L().avsr_beam_ctc_supported(C.byref(desc)))
 

@@ -626,7 +626,8 @@ int avsr_ctc_prefix_search_lm(const avsr_ctc_prefix_args* a, const avsr_ctc_pref
  * One value: acc = 0; while the node has no arc for c: acc += bow[node], node = backoff[node]; then lam = acc + logp[arc] -- fp32
  * additions in exactly this order, so a host restatement in fp32 gives the same bits.  The walk visits at most
  * AVSR_CTC_PREFIX_NGRAM_MAX_ORDER - 1 nodes before it looks at the root, whatever the tables hold, and every index it reads is clamped
- * into its table.  The label sequence () has node `start` (the node of (GO), or 0); an extension by c moves its node along next.
+ * into its table (the walk is csrc/ngram_walk.h, shared with avsr_beam_ngram below).  The label sequence () has node `start` (the node
+ * of (GO), or 0); an extension by c moves its node along next.
  * No workspace: the state is one node id per pool row, in LDS.
  * Limits: avsr_ctc_prefix_search's on V and L_max, 1 <= beam_width <= AVSR_CTC_PREFIX_LM_MAX_W, 1 <= n_nodes <=
  * AVSR_CTC_PREFIX_NGRAM_MAX_NODES, V <= n_arcs <= AVSR_CTC_PREFIX_NGRAM_MAX_ARCS; V == a->V, 0 <= go_id, eos_id < V, 0 <= start <
@@ -652,6 +653,46 @@ typedef struct avsr_ctc_prefix_ngram {
 int avsr_ctc_prefix_ngram_supported(int32_t V, int32_t beam_width, int32_t L_max, int32_t n_nodes, int32_t n_arcs);
 /* AVSR_ERR_ARG for a NULL / non-positive / inconsistent argument, AVSR_ERR_UNSUPPORTED outside the limits: both before any launch. */
 int avsr_ctc_prefix_search_ngram(const avsr_ctc_prefix_args* a, const avsr_ctc_prefix_ngram* ng, void* stream);
+
+/* Shallow fusion of the same back-off N-GRAM into BEAM SEARCH (csrc/beam_ngram.hip; the rule is this project's own, INTEGRATION.md
+ * section 8), the counterpart of avsr_beam_lm with the automaton above as the model:
+ *   step_logp[k][v] = log_softmax(logits_am[k])[v] + lm_weight * lam(v | GO, g_k)  (+ the CTC term of avsr_beam_ctc)     (unfinished beam k)
+ * lam is exactly the value of avsr_ctc_prefix_ngram: context = the last N-1 symbols of GO, g_k, back-off, the finite floor for a class
+ * the model lacks -- so the term is always finite.  EOS gets its term like any other symbol; a finished beam continues with EOS at 0 and
+ * no term; lm_weight == 0 reproduces the search without a model bit for bit.  No length bonus: beam search has its length penalty.
+ * The six tables are avsr_ctc_prefix_ngram's (ngram.py compile_tables), read by the one walk both kernels share (csrc/ngram_walk.h): fp32
+ * additions in its fixed order, at most AVSR_CTC_PREFIX_NGRAM_MAX_ORDER - 1 nodes before the root, every index clamped into its table.
+ * State: one node id per hypothesis row in a ping-pong node [2][n_rows] like avsr_beam_lm's -- step s reads node[s & 1][parent_rows[r]]
+ * and writes node[(s + 1) & 1][r]; step 0 puts every row at `start` and reads neither tok nor the other half.  A row whose tok is EOS
+ * transitions like any other; its values are never read.  tok / parent_rows outside [0, V) / [0, n_rows) are clamped.
+ * Limits: 1 <= n_nodes <= AVSR_CTC_PREFIX_NGRAM_MAX_NODES, 2 <= V <= n_arcs <= AVSR_CTC_PREFIX_NGRAM_MAX_ARCS, 0 <= start < n_nodes,
+ * n_rows >= 1 (n_rows * V < 2^31), lm_weight finite and >= 0.  No beam-width limit of its own: beam search's hold (K <= 64, K * V <= 1024). */
+typedef struct avsr_beam_ngram {
+  int32_t n_nodes, n_arcs, V, start;
+  int32_t n_rows;
+  float lm_weight;
+  const float* bow;
+  const int32_t* backoff;
+  const int32_t* arc_begin;
+  const int32_t* sym;
+  const float* logp;
+  const int32_t* next;
+  int32_t* node;       /* [2][n_rows] */
+  float* lm_logp;      /* [n_rows][V] */
+} avsr_beam_ngram;
+/* 1 if avsr_beam_ngram_step runs this descriptor, else 0 (decided on the host; nothing is dereferenced). */
+int avsr_beam_ngram_supported(const avsr_beam_ngram* ng);
+/* One n-gram step over n_rows (== ng->n_rows) hypothesis rows: the transition into the other half of node, then lm_logp[r][c] =
+ * lam(c | row r's context) for every c < V.  One launch, plain loads and vector stores, no atomics: two launches are bit-identical.
+ * AVSR_ERR_ARG for a NULL / non-positive / inconsistent argument, AVSR_ERR_UNSUPPORTED outside the limits: both before any launch. */
+int avsr_beam_ngram_step(const avsr_beam_ngram* ng, const int32_t* tok, const int32_t* parent_rows, int32_t n_rows, int32_t step, void* stream);
+/* avsr_attn_rnn_fwd in mode 3 with avsr_beam_ngram_step ahead of every selection (ng->n_rows == d->B, ng->V == d->V), under every
+ * avsr_attn_rnn_set_beam_kernel setting.  ctc != NULL: avsr_beam_ctc_step runs after it and the selection reads ctc->extra with weight 1,
+ * exactly as avsr_attn_rnn_fwd_ctc does with an LSTM (ctc->lm_logp must be ng->lm_logp; the caller has run avsr_beam_ctc_begin;
+ * ctc->weight == 0: no CTC launch).  A step queued after the search has ended (tok = EOS, parent_rows = identity) advances the nodes
+ * harmlessly and its output is not read.  An LSTM and an n-gram in one search are not built. */
+int avsr_attn_rnn_fwd_ngram(const avsr_attn_rnn* d, const avsr_beam_ngram* ng, const avsr_beam_ctc* ctc, int32_t l_begin, int32_t l_end,
+                            void* stream);
 
 /* CTC forced alignment (csrc/ctc_align.hip; the rule is this project's own): the single most probable
  * alignment (Viterbi path) of a GIVEN label row to the frames of the head.  z [B * T][ld] are the head's logits over V + 1 real classes,
