@@ -163,6 +163,15 @@ class SpecAugmentArgs(C.Structure):
                [(n, C.c_void_p) for n in ("x", "len", "seed", "y", "ws")] + [("ws_floats", C.c_int64)]
 
 
+VIDEO_AUGMENT_MAX_T, VIDEO_AUGMENT_MAX_C = 65535, 64            # AVSR_VIDEO_AUGMENT_MAX_* of include/avsr_hip.h
+
+
+class VideoAugmentArgs(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("B", "T", "H", "W", "C", "max_shift", "flip_q24", "pad_")] + \
+               [("contrast", C.c_float), ("brightness", C.c_float)] + \
+               [(n, C.c_void_p) for n in ("x", "len", "seed", "y", "ws")] + [("ws_floats", C.c_int64)]
+
+
 class CtcArgs(C.Structure):
     _fields_ = [("B", C.c_int32), ("T", C.c_int32), ("L", C.c_int32), ("C", C.c_int32), ("ld", C.c_int64)] + \
                [(n, C.c_void_p) for n in ("z", "labels", "labels_len", "in_len", "denom")] + [("weight", C.c_float), ("pad_", C.c_int32)] + \
@@ -223,7 +232,7 @@ class TransposeJob(C.Structure):
 
 _STRUCTS = {"avsr_dec_layer": DecLayer, "avsr_mat": Mat, "avsr_gemm_desc": GemmDesc, "avsr_rnn_layer": RnnLayer, "avsr_rnn_stack": RnnStack,
             "avsr_rnn_launch": RnnLaunch,
-            "avsr_conv_desc": ConvDesc, "avsr_conv_launch": ConvLaunch, "avsr_conv3d_desc": Conv3dDesc, "avsr_logmel_args": LogmelArgs, "avsr_spec_augment_args": SpecAugmentArgs, "avsr_ctc_args": CtcArgs, "avsr_attn_mech": AttnMech, "avsr_attn_rnn": AttnRnn, "avsr_transpose_job": TransposeJob,
+            "avsr_conv_desc": ConvDesc, "avsr_conv_launch": ConvLaunch, "avsr_conv3d_desc": Conv3dDesc, "avsr_logmel_args": LogmelArgs, "avsr_spec_augment_args": SpecAugmentArgs, "avsr_video_augment_args": VideoAugmentArgs, "avsr_ctc_args": CtcArgs, "avsr_attn_mech": AttnMech, "avsr_attn_rnn": AttnRnn, "avsr_transpose_job": TransposeJob,
             "avsr_colsum_job": ColsumJob, "avsr_beam_lm": BeamLm, "avsr_beam_ctc": BeamCtc, "avsr_ctc_prefix_args": CtcPrefixArgs,
             "avsr_ctc_prefix_lm": CtcPrefixLm, "avsr_ctc_prefix_ngram": CtcPrefixNgram, "avsr_beam_ngram": BeamNgram,
             "avsr_ctc_align_args": CtcAlignArgs}
@@ -271,6 +280,8 @@ _SIGS = {
     "avsr_logmel_fwd": [C.POINTER(LogmelArgs), _vp],
     "avsr_spec_augment_supported": [_i32, _i32, _i32, _i32, _i32],
     "avsr_spec_augment": [C.POINTER(SpecAugmentArgs), _vp],
+    "avsr_video_augment_supported": [_i32, _i32, _i32, _i32, _i32, _i32],
+    "avsr_video_augment": [C.POINTER(VideoAugmentArgs), _vp],
     "avsr_ctc_loss": [C.POINTER(CtcArgs), _vp],
     "avsr_ctc_best_path": [_vp, _i64, _vp, _i32, _i32, _i32, _vp, _vp],
     "avsr_ctc_prefix_search_supported": [_i32, _i32, _i32],
@@ -354,9 +365,10 @@ _SIGS = {
     "avsr_prof_begin": [_i32],
     "avsr_prof_end": [C.POINTER(_i32), C.POINTER(_f32), C.POINTER(C.c_double)],
 }
-# every symbol the library must export: the table above plus the eight whose return type load() sets on its own
+# every symbol the library must export: the table above plus the nine whose return type load() sets on its own
 EXPORTS = ["avsr_abi_version", "avsr_sizeof", "avsr_attn_rnn_fused_ws_floats", "avsr_conv3d_wgrad_scratch_floats", "avsr_ctc_ws_floats",
-           "avsr_ctc_align_ws_bytes", "avsr_ctc_prefix_lm_ws_bytes", "avsr_spec_augment_ws_floats"] + list(_SIGS)
+           "avsr_ctc_align_ws_bytes", "avsr_ctc_prefix_lm_ws_bytes", "avsr_spec_augment_ws_floats",
+           "avsr_video_augment_ws_floats"] + list(_SIGS)
 
 _lib = None
 
@@ -397,6 +409,8 @@ def load():
     lib.avsr_ctc_ws_floats.restype = C.c_int64
     lib.avsr_spec_augment_ws_floats.argtypes = [_i32, _i32, _i32]
     lib.avsr_spec_augment_ws_floats.restype = C.c_int64
+    lib.avsr_video_augment_ws_floats.argtypes = [_i32, _i32, _i32, _i32, _i32]
+    lib.avsr_video_augment_ws_floats.restype = C.c_int64
     lib.avsr_ctc_align_ws_bytes.argtypes = [_i32, _i32, _i32]
     lib.avsr_ctc_align_ws_bytes.restype = C.c_int64
     lib.avsr_ctc_prefix_lm_ws_bytes.argtypes = [_i32, _i32, _i32, _i32]

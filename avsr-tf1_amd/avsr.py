@@ -56,6 +56,13 @@ its predictions, on the CTC head: per label the first and last frame and a confi
 `video_time_masks` / `video_time_width` / `video_time_ratio` spans of frames on the video stream (features or lip crops), filled with
 `mask_value` = 'mean' (the utterance's own column mean) or 'zero'.  Every count defaults to 0 = off; no size is tuned.  Train graph only:
 `evaluate`, every decoding algorithm and `align` never augment (csrc/specaugment.hip).
+`video_augment` (None = off, or a dict; the reference only lists the intent, commented out, at the top of its resnet_cnn()) arrives
+through **kwargs and augments the lip crops of `video_processing='resnet_cnn'` / `'3dconv_cnn'` inside the train step, anew every step
+and the same for all frames of an utterance: `flip` (probability of a horizontal flip), `max_shift` (a shift of up to that many pixels
+per axis, edges replicated), `contrast` (a factor 1 +- contrast about the utterance's own channel means), `brightness` (an offset of
++- brightness; no clipping).  Every value defaults to 0 = off; none is tuned.  Action-unit targets (`regress_aus`) are left as they are.
+With `spec_augment` video time masks on as well, the masks fall on the augmented crops.  Train graph only, as above (INTEGRATION.md
+section 8, csrc/video_augment.hip).
 """
 import glob
 import os
@@ -299,6 +306,9 @@ class AVSR(object):
         spec_fields = spec_augment_fields(kwargs.get('spec_augment'), audio=audio_processing is not None, video=video_processing is not None,
                                           audio_processing=audio_processing, audio_feat=feats.get('audio'),
                                           num_mel_bins=kwargs.get('num_mel_bins', 30))
+        # lip-crop augmentation in the train step (csrc/video_augment.hip): likewise
+        from .config import video_augment_fields
+        spec_fields.update(video_augment_fields(kwargs.get('video_augment'), video_processing, video_hw))
         self._cfg = ModelConfig(
             **spec_fields,
             architecture=architecture, encoder_type=encoder_type, cell_type=cell_type,

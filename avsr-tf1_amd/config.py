@@ -12,6 +12,9 @@ SPEC_STREAM_AUDIO_FREQ, SPEC_STREAM_AUDIO_TIME, SPEC_STREAM_VIDEO_TIME = 200, 20
 SPEC_AUGMENT_KEYS = ("freq_masks", "freq_width", "time_masks", "time_width", "time_ratio", "video_time_masks", "video_time_width",
                      "video_time_ratio", "freq_bins", "mask_value")
 SPEC_AUGMENT_MAX_MASKS, SPEC_AUGMENT_MAX_T = 8, 65535          # avsr_spec_augment_supported (include/avsr_hip.h)
+# ... and of the lip-crop augmentation's draws (csrc/common.h RNG_STREAM_VIDEO_AUG_*): flip and shifts; contrast and brightness
+VIDEO_AUG_STREAM_GEOMETRY, VIDEO_AUG_STREAM_PHOTOMETRIC = 203, 204
+VIDEO_AUGMENT_KEYS = ("flip", "max_shift", "contrast", "brightness")
 
 
 def round4(n: int) -> int:
@@ -62,6 +65,40 @@ def spec_augment_fields(spec, audio=True, video=True, audio_processing="features
             raise ValueError("spec_augment: freq_bins (%d) must divide the audio feature width (%d)" % (fb, audio_feat))
         out["spec_freq_bins"] = fb
     return out
+
+
+def _video_augment_check(flip, max_shift, contrast, brightness, video_hw, name=lambda k: k):
+    """The ranges of the four values; `name` turns a key into what the message calls it."""
+    num = lambda v: not isinstance(v, bool) and isinstance(v, (int, float))
+    if not num(flip) or not 0.0 <= flip <= 1.0:
+        raise ValueError("%s must be a probability in [0, 1] (got %r)" % (name("flip"), flip))
+    if isinstance(max_shift, bool) or not isinstance(max_shift, int) or not 0 <= max_shift < min(video_hw[0], video_hw[1]):
+        raise ValueError("%s must be an integer with 0 <= max_shift < min(H, W) = %d (got %r)"
+                         % (name("max_shift"), min(video_hw[0], video_hw[1]), max_shift))
+    if not num(contrast) or not 0.0 <= contrast < 1.0:
+        raise ValueError("%s must be a number in [0, 1) (got %r)" % (name("contrast"), contrast))
+    if not num(brightness) or not 0.0 <= brightness < float("inf"):
+        raise ValueError("%s must be a finite number >= 0 (got %r)" % (name("brightness"), brightness))
+
+
+def video_augment_fields(spec, video_processing="resnet_cnn", video_hw=(36, 36, 3)):
+    """The `video_augment` keyword of avsr.AVSR (None, or a dict over VIDEO_AUGMENT_KEYS) -> the ModelConfig fields it sets.  Refuses on
+    the host, naming the key (ValueError): not a dict, unknown keys, a value outside its range (bools are no numbers), a video stream
+    that holds no pixels (video_processing None or 'features')."""
+    if spec is None:
+        return {}
+    if not isinstance(spec, dict):
+        raise ValueError("video_augment must be None or a dict over %s (got %r)" % (", ".join(VIDEO_AUGMENT_KEYS), type(spec).__name__))
+    for k in spec:
+        if k not in VIDEO_AUGMENT_KEYS:
+            raise ValueError("video_augment: unknown key %r (the keys are %s)" % (k, ", ".join(VIDEO_AUGMENT_KEYS)))
+    if video_processing not in ("resnet_cnn", "3dconv_cnn"):
+        raise ValueError("video_augment needs lip crops (video_processing='resnet_cnn' or '3dconv_cnn'; got %r): there are no pixels"
+                         % (video_processing,))
+    v = {k: spec.get(k, 0) for k in VIDEO_AUGMENT_KEYS}
+    _video_augment_check(video_hw=video_hw, name=lambda k: "video_augment: " + k, **v)
+    return dict(vaug_flip_q24=int(round(v["flip"] * 16777216.0)), vaug_max_shift=v["max_shift"], vaug_contrast=float(v["contrast"]),
+                vaug_brightness=float(v["brightness"]))
 
 
 def encoder_cell_id(stream, direction, layer):
@@ -140,6 +177,14 @@ class ModelConfig:
     spec_video_time_width: int = 0
     spec_video_time_ratio: float = 1.0
     spec_mask_value: str = "mean"                                   # 'mean' (the utterance's own column mean) | 'zero'
+    # Lip-crop augmentation in the train graph (not in the reference, which lists the intent at the top of its resnet_cnn();
+    # csrc/video_augment.hip), per utterance: a horizontal flip with probability vaug_flip_q24 / 2^24, a shift of
+    # up to vaug_max_shift pixels per axis, a contrast factor 1 +- vaug_contrast, a brightness offset +- vaug_brightness.  Every value
+    # defaults to 0 = off, and none is tuned.  video_augment_fields() turns avsr.AVSR's `video_augment` dict into these.
+    vaug_flip_q24: int = 0
+    vaug_max_shift: int = 0
+    vaug_contrast: float = 0.0
+    vaug_brightness: float = 0.0
     one_hot_embedding: bool = False      # set by engine(): embedding_size <= 0 -> tf.eye(vocab_size) decoder inputs (decoder_unimodal.py:76-77)
 
     # -- same helpers/validation rules as the reference wiring (error types as in the reference) --
@@ -209,6 +254,14 @@ class ModelConfig:
             return None
         a["mean_fill"] = self.spec_mask_value == "mean"
         return a
+
+    def video_augment_args(self) -> Optional[dict]:
+        """The parameters of avsr_video_augment for the lip crops in the train graph; None = nothing to launch (every value is 0, or
+        the video stream holds no pixels)."""
+        if self.video_units is None or self.video_processing not in ("resnet_cnn", "3dconv_cnn"):
+            return None
+        a = dict(flip_q24=self.vaug_flip_q24, max_shift=self.vaug_max_shift, contrast=self.vaug_contrast, brightness=self.vaug_brightness)
+        return a if any(a.values()) else None
 
     def one_hot(self) -> bool:
         """decoder_unimodal.py:76-77: a non-positive embedding_size falls back to one-hot decoder inputs (no embedding variable)."""
@@ -290,6 +343,16 @@ class ModelConfig:
                          if w >= 1 and (w == self.audio_feat or (self.audio_feat % 4 == 0 and round4(w) == self.audio_feat))):
                 raise ValueError("spec_freq_bins (%d) must divide the audio feature width (%d)" % (P, self.audio_feat))
 
+    def _validate_video_augment(self):
+        q = self.vaug_flip_q24
+        if isinstance(q, bool) or not isinstance(q, int) or not 0 <= q <= 1 << 24:
+            raise ValueError("vaug_flip_q24 must be an integer in [0, 2^24] (got %r)" % (q,))
+        _video_augment_check(0.0, self.vaug_max_shift, self.vaug_contrast, self.vaug_brightness, self.video_hw, name=lambda k: "vaug_" + k)
+        if q or self.vaug_max_shift or self.vaug_contrast or self.vaug_brightness:
+            if self.video_units is None or self.video_processing not in ("resnet_cnn", "3dconv_cnn"):
+                raise ValueError("vaug_* need lip crops (a video stream with video_processing='resnet_cnn' or '3dconv_cnn'): "
+                                 "there are no pixels")
+
     def validate(self):
         if self.architecture == "lm":                                                 # avsr.LM (lm.py:275-471): labels only, no encoders
             if self.video_units is not None or self.audio_units is not None:
@@ -323,6 +386,7 @@ class ModelConfig:
             if not self.enable_attention:
                 raise NotImplementedError("use_ctc with enable_attention=False is not built")
         self._validate_spec_augment()
+        self._validate_video_augment()
         if self.optimiser not in ("Adam", "Nadam", "AdamW", "Momentum"):
             raise Exception('Unsupported optimiser, try Adam')                            # seq2seq.py:218
         for st in self.streams():                 # the wrapper flags only where the reference applies them (see `wrapped`)

@@ -39,6 +39,9 @@ __host__ __device__ __forceinline__ float uniform01(uint32_t seed, uint32_t stre
 #define RNG_STREAM_SPEC_AUDIO_FREQ 200u
 #define RNG_STREAM_SPEC_AUDIO_TIME 201u
 #define RNG_STREAM_SPEC_VIDEO_TIME 202u
+// ... and of the lip-crop augmentation's draws (csrc/video_augment.hip; config.py VIDEO_AUG_STREAM_*): flip and shifts, contrast and brightness
+#define RNG_STREAM_VIDEO_AUG_GEOMETRY 203u
+#define RNG_STREAM_VIDEO_AUG_PHOTOMETRIC 204u
 
 // ---- wave64 reductions ------------------------------------------------------------------
 // __shfl_xor butterflies, distances 32 .. 1 (wave_max: the same).  NOT the summation order of wave.h's wave64_sum (DPP rows, then the four

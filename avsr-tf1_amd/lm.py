@@ -97,6 +97,8 @@ class LM(object):
             raise Exception('cell type not supported: {}'.format(cell_type))                      # cells.py:44
         if kwargs.get('spec_augment') is not None:
             raise ValueError("spec_augment: the language model has no encoder input to augment")
+        if kwargs.get('video_augment') is not None:
+            raise ValueError("video_augment: the language model has no lip crops to augment")
         if kwargs.get('ngram_lm') is not None:
             raise ValueError("ngram_lm: an n-gram is fused into the recogniser's beam search (AVSR(ngram_lm=...)); the language model "
                              "trains and scores alone")

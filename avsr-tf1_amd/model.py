@@ -245,6 +245,17 @@ class Seq2SeqModel(EncoderMixin, DecoderMixin, CtcMixin, RescoreMixin, EvalMixin
                 E["sa_in"], E["sa_x"] = w_in, z(B, T, w_in if cnn_fed else F)
                 if cfg.spec_mask_value == "mean":
                     E["sa_ws"] = z((ops.spec_augment_ws_floats(B, T, w_in) + 3) // 4 * 4)
+            if not greedy and s == "video" and self.use_cnn and cfg.video_augment_args() is not None:
+                # video_augment: the augmented lip crops (train graph only); spec_augment's video time masks then read this buffer
+                Hh, Ww, Cc = cfg.video_hw
+                if not ops.video_augment_supported(B, T, Hh, Ww, Cc, cfg.vaug_max_shift):
+                    from ._lib import VIDEO_AUGMENT_MAX_C, VIDEO_AUGMENT_MAX_T
+                    raise ValueError("video_augment: avsr_video_augment covers lip crops of up to %d frames, %d utterances, %d channels "
+                                     "and fewer than 2^31 elements (got the video input [%d, %d, %d, %d, %d])"
+                                     % (VIDEO_AUGMENT_MAX_T, 65535, VIDEO_AUGMENT_MAX_C, B, T, Hh, Ww, Cc))
+                E["va_x"] = z(B, T, Hh, Ww, Cc)
+                if cfg.vaug_contrast > 0.0:
+                    E["va_ws"] = z((ops.video_augment_ws_floats(B, T, Hh, Ww, Cc) + 3) // 4 * 4)
             if s == "video" and self.use_cnn:
                 if cfg.video_processing == "3dconv_cnn":
                     from .cnn3d import LipCNN3D

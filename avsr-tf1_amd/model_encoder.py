@@ -366,6 +366,9 @@ class EncoderMixin:
             if "cnn" in E:                                           # avsr/avsr.py:684-696: frames -> visual features
                 Hh, Ww, Cc = cfg.video_hw
                 assert x.shape == (B, T, Hh, Ww, Cc) and x.is_contiguous() and x.dtype == torch.float32
+                if training and "va_x" in E:                         # video_augment: flip / shift / contrast / brightness, per utterance
+                    ops.video_augment(x, len_t, self.seed, E["va_x"], E.get("va_ws"), **cfg.video_augment_args())
+                    x = E["va_x"]                                    # (the batch itself is never written)
                 if aug:                                              # (the CNN's weight gradients read what forward was given)
                     x = self._spec_augment(E, x, len_t, s)
                 x = E["cnn"].forward(x.view(B * T, Hh, Ww, Cc), training).view(B, T, F)

@@ -911,6 +911,28 @@ def spec_augment(x, F_in, lens, seed, y, ws, video=False, freq_masks=0, freq_wid
     check(_L().avsr_spec_augment(C.byref(a), _s()), "avsr_spec_augment")
 
 
+def video_augment_supported(B, T, H, W, Cc, max_shift):
+    """Host-side: does avsr_video_augment run this shape (include/avsr_hip.h AVSR_VIDEO_AUGMENT_MAX_*)?"""
+    return bool(_L().avsr_video_augment_supported(int(B), int(T), int(H), int(W), int(Cc), int(max_shift)))
+
+
+def video_augment_ws_floats(B, T, H, W, Cc):
+    return int(_L().avsr_video_augment_ws_floats(int(B), int(T), int(H), int(W), int(Cc)))
+
+
+def video_augment(x, lens, seed, y, ws, flip_q24=0, max_shift=0, contrast=0.0, brightness=0.0):
+    """avsr_video_augment: lip crops x [B, T, H, W, C] -> y of the same shape, every element written; lens [B] int32 and seed [1] int32
+    are read on the device.  ws: video_augment_ws_floats(B, T, H, W, C) floats (contrast > 0 only)."""
+    assert x.dim() == 5 and x.shape == y.shape and x.is_contiguous() and y.is_contiguous() and x.dtype == y.dtype == torch.float32
+    assert x.data_ptr() != y.data_ptr()
+    assert lens.dtype == torch.int32 and lens.is_contiguous() and lens.numel() == x.shape[0] and seed.dtype == torch.int32
+    B, T, H, W, Cc = x.shape
+    a = _lib.VideoAugmentArgs(B=B, T=T, H=H, W=W, C=Cc, max_shift=int(max_shift), flip_q24=int(flip_q24), pad_=0, contrast=float(contrast),
+                              brightness=float(brightness), x=fptr(x), len=fptr(lens), seed=fptr(seed), y=fptr(y), ws=fptr(ws),
+                              ws_floats=0 if ws is None else ws.numel())
+    check(_L().avsr_video_augment(C.byref(a), _s()), "avsr_video_augment")
+
+
 def conv3d_bn_finalize(part, nparts, Cn, count, eps, momentum, mean, invstd, mov_mean, mov_var, gamma=None, beta=None, scale=None, shift=None):
     """avsr_bn_finalize with the biased moving variance of the non-fused (rank-5) batch norm."""
     check(_L().avsr_conv3d_bn_finalize(fptr(part), int(nparts), int(Cn), int(count), float(eps), float(momentum), fptr(mean), fptr(invstd),

@@ -1033,6 +1033,40 @@ typedef struct avsr_spec_augment_args {
 int avsr_spec_augment_supported(int32_t B, int32_t T, int32_t F, int32_t freq_masks, int32_t time_masks);
 int64_t avsr_spec_augment_ws_floats(int32_t B, int32_t T, int32_t F_in);
 int avsr_spec_augment(const avsr_spec_augment_args* a, void* stream);
+/* ---- Lip-crop augmentation (video_augment; not in the reference; csrc/video_augment.hip; the rule is INTEGRATION.md section 8).
+ * x [B, T, H, W, C] contiguous -> y of the same shape, y != x.  EVERY element of y is written, frames t >= n_b = clamp(len[b], 0, T) as
+ * zeros; x is never written.  All draws are uint32 and PER UTTERANCE, h_s(i) = hash_u32(seed[0], s, i) (seed: DEVICE word, the step's
+ * key), streams 203 (geometry) and 204 (photometric), u(h) = (h >> 8) * 2^-24:
+ *   flip    iff (h_203(4b) >> 8) < flip_q24, flip_q24 = round(flip * 2^24) in [0, 2^24]
+ *   shift   dx = h_203(4b+1) % (2S+1) - S, dy = h_203(4b+2) % (2S+1) - S, S = max_shift
+ *   source  of output pixel (i, j, c) of frame t < n_b: x[t, ii, flip ? W-1-jj : jj, c] with jj = clamp(j - dx, 0, W-1),
+ *           ii = clamp(i - dy, 0, H-1): the flip first, the shift second, edges replicated
+ *   cf = 1 + contrast * (2 u(h_204(2b)) - 1), d = brightness * (2 u(h_204(2b+1)) - 1), every fp32 operation rounded on its own
+ *   contrast > 0: y = cf * (v - m_c) + (m_c + d), m_c the utterance's mean of channel c over its n_b frames of x (0 when n_b = 0):
+ *           fp32 partial sums of fc * H * W terms per chunk of fc frames, added in chunk order in fp64, / (n_b H W), rounded once;
+ *           fc = max(4, ceil(T / min(128, ceil(1024 / B))) rounded down to a multiple of 4)
+ *   contrast == 0, brightness > 0: y = v + d.  Both 0: bit copies.  No clipping.
+ * ws: avsr_video_augment_ws_floats(B, T, H, W, C) floats, 16-byte aligned (contrast > 0 only; may be NULL otherwise): the partial sums
+ * [B][ceil(T / fc)][C], then the means [B][C].  One launch, or three with contrast > 0; no atomics (two launches on the same inputs are
+ * bit-identical), no host read, no memset / memcpy: safe under stream capture.  Covered (avsr_video_augment_supported): T <= 65535,
+ * B <= 65535, C <= 64, 0 <= max_shift < min(H, W), B * T * H * W * C < 2^31; otherwise AVSR_ERR_UNSUPPORTED (-3).  contrast in [0, 1),
+ * brightness finite and >= 0, else AVSR_ERR_ARG. */
+#define AVSR_VIDEO_AUGMENT_MAX_T 65535
+#define AVSR_VIDEO_AUGMENT_MAX_C 64
+typedef struct avsr_video_augment_args {
+  int32_t B, T, H, W;
+  int32_t C, max_shift, flip_q24, pad_;
+  float contrast, brightness;
+  const float* x;
+  const int32_t* len;
+  const int32_t* seed;
+  float* y;
+  float* ws;
+  int64_t ws_floats;
+} avsr_video_augment_args;
+int avsr_video_augment_supported(int32_t B, int32_t T, int32_t H, int32_t W, int32_t C, int32_t max_shift);
+int64_t avsr_video_augment_ws_floats(int32_t B, int32_t T, int32_t H, int32_t W, int32_t C);
+int avsr_video_augment(const avsr_video_augment_args* a, void* stream);
 /* ---- CTC auxiliary loss on an encoder's outputs (use_ctc; not in the reference; csrc/ctc.hip).  z [B*T, C] with row stride ld are the
  * head's logits, C = vocab_size + 1 and the BLANK IS CLASS C - 1 (tf.nn.ctc_loss's convention); columns >= C of a wider row are never
  * read or written.  Utterance b: target labels[b, :U_b] with U_b = max(min(labels_len[b], L) - 1, 0) (the label row without its EOS),
