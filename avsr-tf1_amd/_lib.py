@@ -112,6 +112,12 @@ class AttnRnn(C.Structure):
                 ("fused_ws", C.c_void_p), ("fused_ws_floats", C.c_int64)]
 
 
+class AttnRnnLaunch(C.Structure):
+    """avsr_attn_rnn_launch: the record of avsr_attn_rnn_plan."""
+    _fields_ = [(n, C.c_int32) for n in ("form", "variant", "rows_per_group", "v64", "launches", "pad_")] + \
+               [("quarter", C.c_int32 * MAX_MECH), ("lds_bytes", C.c_int64)]
+
+
 MAX_LM_LAYERS = 4
 
 
@@ -233,6 +239,7 @@ class TransposeJob(C.Structure):
 _STRUCTS = {"avsr_dec_layer": DecLayer, "avsr_mat": Mat, "avsr_gemm_desc": GemmDesc, "avsr_rnn_layer": RnnLayer, "avsr_rnn_stack": RnnStack,
             "avsr_rnn_launch": RnnLaunch,
             "avsr_conv_desc": ConvDesc, "avsr_conv_launch": ConvLaunch, "avsr_conv3d_desc": Conv3dDesc, "avsr_logmel_args": LogmelArgs, "avsr_spec_augment_args": SpecAugmentArgs, "avsr_video_augment_args": VideoAugmentArgs, "avsr_ctc_args": CtcArgs, "avsr_attn_mech": AttnMech, "avsr_attn_rnn": AttnRnn, "avsr_transpose_job": TransposeJob,
+            "avsr_attn_rnn_launch": AttnRnnLaunch,
             "avsr_colsum_job": ColsumJob, "avsr_beam_lm": BeamLm, "avsr_beam_ctc": BeamCtc, "avsr_ctc_prefix_args": CtcPrefixArgs,
             "avsr_ctc_prefix_lm": CtcPrefixLm, "avsr_ctc_prefix_ngram": CtcPrefixNgram, "avsr_beam_ngram": BeamNgram,
             "avsr_ctc_align_args": CtcAlignArgs}
@@ -252,6 +259,7 @@ _SIGS = {
     "avsr_attn_rnn_fused_eligible": [C.POINTER(AttnRnn)],
     "avsr_attn_rnn_fused_fwd_active": [C.POINTER(AttnRnn)],
     "avsr_attn_rnn_set_fused": [_i32],
+    "avsr_attn_rnn_plan": [C.POINTER(AttnRnn), _i32, C.POINTER(AttnRnnLaunch)],
     "avsr_attn_rnn_set_beam_kernel": [_i32],
     "avsr_conv_set_mfma": [_i32],
     "avsr_conv_supported": [C.POINTER(ConvDesc)],

@@ -231,6 +231,46 @@ static int validate(const avsr_attn_rnn* d) {
   return AVSR_OK;
 }
 
+// What avsr_attn_rnn_fwd checks of its arguments after validate(), before any launch.
+static int fwd_check(const avsr_attn_rnn& d) {
+  const int B = d.B, A = d.n_mech * d.H;
+  if (d.mode == 1 && (!d.embedding || !d.wout_t || !d.logits || !d.ids || !d.tok || !d.n_unfinished)) return AVSR_ERR_ARG;
+  if (d.mode == 2 && (!d.embedding || !d.wout_t || !d.logits || !d.xs || !d.labels || !d.fed || !d.seed)) return AVSR_ERR_ARG;
+  if (d.mode == 3 && (!d.embedding || !d.wout_t || !d.logits || !d.tok || !d.n_unfinished || d.beam_width <= 0 || B % d.beam_width ||
+                      !d.beam_logp || !d.beam_fin || !d.beam_len || !d.step_ids || !d.parent_ids || !d.parent_rows)) return AVSR_ERR_ARG;
+  if (d.mode == 3 && (!beam_step_fits(d.beam_width, d.V) || d.beam_width > 64)) return AVSR_ERR_UNSUPPORTED;
+  if (d.cell == 1 && (!d.wt2 || !d.rh_seq)) return AVSR_ERR_ARG;
+  const bool drop = d.seed && d.mode != 1 && (d.keep_in < 1.f || d.keep_state < 1.f || d.keep_out < 1.f);
+  if (drop && (!d.hs_seq || (A > 0 && !d.attd))) return AVSR_ERR_ARG;
+  if (drop)
+    for (int j = 0; j < d.n_extra; ++j)
+      if (!d.extra[j].hs_seq || !d.extra[j].xin_seq) return AVSR_ERR_ARG;
+  return AVSR_OK;
+}
+
+// What avsr_attn_rnn_bwd checks of its arguments after validate(), before any launch; counts the mechanisms of either family.
+static int bwd_check(const avsr_attn_rnn& d, int* n_bah_out, int* n_luong_out) {
+  if (!d.w || !d.dgates || !d.dstate) return AVSR_ERR_ARG;
+  if (d.n_mech > 0 && !d.datt) return AVSR_ERR_ARG;
+  int n_bah = 0, n_luong = 0;
+  for (int m = 0; m < d.n_mech; ++m) {
+    const avsr_attn_mech& M = d.mech[m];
+    if (!M.watt || !M.dscores || !M.dctx || !M.pdq) return AVSR_ERR_ARG;
+    if (is_bahdanau(M)) { if (!M.wq || !M.dpq) return AVSR_ERR_ARG; ++n_bah; } else ++n_luong;
+  }
+  if (1 + d.n_mech + n_bah > STEP_MAX_SRC) return AVSR_ERR_UNSUPPORTED;
+  if (d.cell == 1 && (!d.w2 || !d.dgates2)) return AVSR_ERR_ARG;
+  if (((n_luong > 0) || d.dcell_ext) && !d.dq) return AVSR_ERR_ARG;
+  if (d.n_extra > 0 && (d.dh_final || d.dc_final)) return AVSR_ERR_UNSUPPORTED;     // final-state gradients: single-cell blocks only
+  for (int j = 0; j < d.n_extra; ++j)
+    if (!d.extra[j].w || !d.extra[j].dgates || !d.extra[j].dstate) return AVSR_ERR_ARG;
+  *n_bah_out = n_bah; *n_luong_out = n_luong;
+  return AVSR_OK;
+}
+
+// Which blocks avsr_attn_rnn_bwd offers to the fused BPTT launch first (Luong blocks, and one-memory Bahdanau blocks).
+static inline bool bwd_tries_fused(const avsr_attn_rnn& d) { return d.n_mech > 0 && d.cell != 1 && d.n_extra == 0; }
+
 static void fill_attn_launch(const avsr_attn_rnn& d, int l, AttnLaunch& AL) {
   const int B = d.B, H = d.H, L = d.L;
   AL = AttnLaunch{};
@@ -275,19 +315,10 @@ static int attn_rnn_fwd_impl(const avsr_attn_rnn* dp, const avsr_beam_lm* lm, co
   hipStream_t s = (hipStream_t)stream;
   const int B = d.B, H = d.H, L = d.L, E = d.E, A = d.n_mech * H, KW = E + A + H;
   if (l_begin < 0 || l_end > L || l_begin > l_end) return AVSR_ERR_ARG;
-  if (d.mode == 1 && (!d.embedding || !d.wout_t || !d.logits || !d.ids || !d.tok || !d.n_unfinished)) return AVSR_ERR_ARG;
-  if (d.mode == 2 && (!d.embedding || !d.wout_t || !d.logits || !d.xs || !d.labels || !d.fed || !d.seed)) return AVSR_ERR_ARG;
-  if (d.mode == 3 && (!d.embedding || !d.wout_t || !d.logits || !d.tok || !d.n_unfinished || d.beam_width <= 0 || B % d.beam_width ||
-                      !d.beam_logp || !d.beam_fin || !d.beam_len || !d.step_ids || !d.parent_ids || !d.parent_rows)) return AVSR_ERR_ARG;
-  if (d.mode == 3 && (!beam_step_fits(d.beam_width, d.V) || d.beam_width > 64)) return AVSR_ERR_UNSUPPORTED;
+  if ((rc = fwd_check(d))) return rc;
   const bool feed = (d.mode == 1 || d.mode == 3);      // inputs come from the embedding of the previous prediction
   const bool gru = d.cell == 1;
-  if (gru && (!d.wt2 || !d.rh_seq)) return AVSR_ERR_ARG;
   const bool drop = d.seed && d.mode != 1 && (d.keep_in < 1.f || d.keep_state < 1.f || d.keep_out < 1.f);
-  if (drop && (!d.hs_seq || (A > 0 && !d.attd))) return AVSR_ERR_ARG;
-  if (drop)
-    for (int j = 0; j < d.n_extra; ++j)
-      if (!d.extra[j].hs_seq || !d.extra[j].xin_seq) return AVSR_ERR_ARG;
   const uint32_t cid4 = (uint32_t)d.cell_id * 4;
   const size_t bh = sizeof(float) * B * H;
 
@@ -586,19 +617,11 @@ extern "C" int avsr_attn_rnn_bwd(const avsr_attn_rnn* dp, void* stream) {
   const avsr_attn_rnn& d = *dp;
   hipStream_t s = (hipStream_t)stream;
   const int B = d.B, H = d.H, L = d.L, E = d.E, A = d.n_mech * H;
-  if (!d.w || !d.dgates || !d.dstate) return AVSR_ERR_ARG;
-  if (A > 0 && !d.datt) return AVSR_ERR_ARG;
   int n_bah = 0, n_luong = 0;
-  for (int m = 0; m < d.n_mech; ++m) {
-    const avsr_attn_mech& M = d.mech[m];
-    if (!M.watt || !M.dscores || !M.dctx || !M.pdq) return AVSR_ERR_ARG;
-    if (is_bahdanau(M)) { if (!M.wq || !M.dpq) return AVSR_ERR_ARG; ++n_bah; } else ++n_luong;
-  }
-  if (1 + d.n_mech + n_bah > STEP_MAX_SRC) return AVSR_ERR_UNSUPPORTED;
+  if ((rc = bwd_check(d, &n_bah, &n_luong))) return rc;
   const bool drop = d.seed && (d.keep_in < 1.f || d.keep_state < 1.f || d.keep_out < 1.f);
   const uint32_t cid4 = (uint32_t)d.cell_id * 4;
   const bool gru = d.cell == 1;
-  if (gru && (!d.w2 || !d.dgates2)) return AVSR_ERR_ARG;
   const int G = gru ? 2 : 4;      // gate pre-activations per unit
   // GRU dstate: dGg rolling [2][B][2H] | d(cand pre-act) rolling [2][B][H] | carry [2][B][H] | tmp du | tmp dh*u
   auto g_dgg = [&](int p) { return d.dstate + (long)p * B * 2 * H; };
@@ -606,16 +629,11 @@ extern "C" int avsr_attn_rnn_bwd(const avsr_attn_rnn* dp, void* stream) {
   auto g_carry = [&](int p) { return d.dstate + (long)(6 + p) * B * H; };
   auto g_tmp = [&](int w) { return d.dstate + (long)(8 + w) * B * H; };
   const bool use_dq = (n_luong > 0) || d.dcell_ext;
-  if (use_dq && !d.dq) return AVSR_ERR_ARG;
   const size_t bh = sizeof(float) * B * H;
   const int NX = d.n_extra;
-  if (NX > 0 && (d.dh_final || d.dc_final)) return AVSR_ERR_UNSUPPORTED;     // final-state gradients: single-cell blocks only
   {
     avsr::DevBatch db(s);                            // the zeroed rolling state of every layer: one launch
-    for (int j = 0; j < NX; ++j) {
-      if (!d.extra[j].w || !d.extra[j].dgates || !d.extra[j].dstate) return AVSR_ERR_ARG;
-      db.zero(d.extra[j].dstate, 12 * bh);
-    }
+    for (int j = 0; j < NX; ++j) db.zero(d.extra[j].dstate, 12 * bh);
     db.zero(d.dstate, 12 * bh);
     if (db.flush() != hipSuccess) return AVSR_ERR_HIP;
     // ... then the final-state gradients into their slots of it (a second launch: they overwrite part of what the first zeroes)
@@ -629,7 +647,7 @@ extern "C" int avsr_attn_rnn_bwd(const avsr_attn_rnn* dp, void* stream) {
   static thread_local SlabLaunch BL;
   // the whole loop as one persistent launch where the fused kernel covers the block (csrc/dec_persist_bwd.hip)
   bool fused = false;
-  if (A > 0 && !gru && NX == 0) {                 // (Luong blocks, and one-memory Bahdanau blocks)
+  if (bwd_tries_fused(d)) {
     const int frc = avsr_dec_persist_bwd(dp, stream);
     if (frc == AVSR_OK) fused = true;
     else if (frc != AVSR_ERR_UNSUPPORTED) return frc;
@@ -812,5 +830,28 @@ extern "C" int avsr_attn_rnn_bwd(const avsr_attn_rnn* dp, void* stream) {
     if ((rc = avsr_step_launch_raw(&SL, stream))) return rc;
   }
   if (!gru && d.dc0 && avsr::dev_copy(d.dc0, dcbuf(d, 0), bh, s) != hipSuccess) return AVSR_ERR_HIP;
+  return AVSR_OK;
+}
+
+// The dry path of the two calls above: their argument checks, then the question they put to the fused launches first.
+extern "C" int avsr_attn_rnn_plan(const avsr_attn_rnn* dp, int32_t bwd, avsr_attn_rnn_launch* out) {
+  using namespace avsr;
+  int rc = validate(dp);
+  if (rc) return rc;
+  if (!out || bwd < 0 || bwd > 1) return AVSR_ERR_ARG;
+  const avsr_attn_rnn& d = *dp;
+  int prc = AVSR_ERR_UNSUPPORTED;
+  if (!bwd) {
+    if ((rc = fwd_check(d))) return rc;
+    prc = avsr_dec_persist_fwd_plan(dp, out);
+  } else {
+    int n_bah = 0, n_luong = 0;
+    if ((rc = bwd_check(d, &n_bah, &n_luong))) return rc;
+    if (bwd_tries_fused(d)) prc = avsr_dec_persist_bwd_plan(dp, out);
+  }
+  if (prc == AVSR_OK) return AVSR_OK;
+  if (prc != AVSR_ERR_UNSUPPORTED) return prc;
+  *out = avsr_attn_rnn_launch{};
+  out->form = AVSR_ATTN_FORM_PER_STEP; out->variant = -1; out->launches = d.L;
   return AVSR_OK;
 }

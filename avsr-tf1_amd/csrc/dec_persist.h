@@ -62,6 +62,12 @@ __device__ __forceinline__ float dot4(const f32x4 a, const f32x4 b) { return a[0
 
 // Fills L for the descriptor; AVSR_ERR_UNSUPPORTED when the fused kernels do not cover it (dec_persist.hip).
 int dp_plan(const avsr_attn_rnn& d, DPLaunch& L, int* variant, size_t* lds_bytes);
+// rows of one launch (a slice): one group per XCD; and which output-layer template a (mode, V) takes -- one copy each for the plan,
+// the launches and the record avsr_attn_rnn_plan reports
+inline int dp_slice_rows(int R) { return 8 * R; }
+inline bool dp_v64(int mode, int V) { return mode >= 1 && V > 32; }
+// The avsr_attn_rnn_plan record of a fused launch of plan F (dec_persist.hip).
+void dp_describe(const avsr_attn_rnn& d, const DPLaunch& F, int variant, size_t lds_bytes, bool v64, avsr_attn_rnn_launch* out);
 extern int g_dec_fused;
 
 }  // namespace avsr
@@ -69,5 +75,8 @@ extern int g_dec_fused;
 // the fused launches the per-step scheduler (attn_rnn.hip) tries first (AVSR_ERR_UNSUPPORTED: run the per-step path), their workspace regions
 int avsr_dec_persist_fwd(const avsr_attn_rnn* d, int32_t l_begin, int32_t l_end, void* stream);   // dec_persist.hip
 int avsr_dec_persist_bwd(const avsr_attn_rnn* d, void* stream);                                      // dec_persist_bwd.hip
+// their dry paths (avsr_attn_rnn_plan): the same decisions up to the launch, the record filled instead
+int avsr_dec_persist_fwd_plan(const avsr_attn_rnn* d, avsr_attn_rnn_launch* out);                  // dec_persist.hip
+int avsr_dec_persist_bwd_plan(const avsr_attn_rnn* d, avsr_attn_rnn_launch* out);                  // dec_persist_bwd.hip
 int64_t avsr_dec_persist_fwd_ws_floats(int32_t B, int32_t n_mech, int32_t Dmax);                     // dec_persist.hip
 int64_t avsr_dec_persist_bwd_ws_floats(int32_t B, int32_t n_mech);                                   // dec_persist_bwd.hip

@@ -850,7 +850,7 @@ int dp_plan(const avsr_attn_rnn& d, DPLaunch& L, int* variant, size_t* lds_bytes
     X.lds_off = lds_off; lds_off += X.ch * M.D;
     X.ppm = ws; ws += 4L * B; X.ppl = ws; ws += 4L * B; X.ppctx = ws; ws += 4L * B * M.D;
   }
-  const bool v64 = d.mode >= 1 && d.V > 32;                                        // output-kernel rows round4(V) wide, scores in the input-row buffer
+  const bool v64 = dp_v64(d.mode, d.V);                                            // output-kernel rows round4(V) wide, scores in the input-row buffer
   const size_t bytes = sizeof(float) * ((size_t)(L.R == 16 ? DP_MISC16 : DP_MISC + (v64 ? 16 * ((d.V + 3) & ~3) - 512 - 256 : 0)) + lds_off);
   if (bytes > DP_LDS_BYTES) return AVSR_ERR_UNSUPPORTED;
   *lds_bytes = bytes;
@@ -873,7 +873,34 @@ static constexpr long DP_SYNC_WORDS = P_HDR + 8 + 8 * 4 * 32;
 // the run-time conditions the fused forward declines on besides the plan (dp_plan)
 static bool dp_fwd_enabled() { return g_dec_fused != 0 && g_dec_fused != 3 && g_sync && DP_SYNC_WORDS <= g_sync_ints; }
 
+// everything avsr_dec_persist_fwd decides before it launches: the run-time switches, then the plan
+static int dp_fwd_plan(const avsr_attn_rnn& d, DPLaunch& L, int* variant, size_t* lds_bytes) {
+  if (!dp_fwd_enabled()) return AVSR_ERR_UNSUPPORTED;
+  return dp_plan(d, L, variant, lds_bytes);
+}
+
+// the record avsr_attn_rnn_plan reports for a fused launch of this plan (forward and BPTT slice the batch the same way)
+void dp_describe(const avsr_attn_rnn& d, const DPLaunch& F, int variant, size_t lds_bytes, bool v64, avsr_attn_rnn_launch* out) {
+  *out = avsr_attn_rnn_launch{};
+  out->form = AVSR_ATTN_FORM_FUSED; out->variant = variant; out->rows_per_group = F.R; out->v64 = v64 ? 1 : 0;
+  const int slice = dp_slice_rows(F.R);
+  out->launches = (d.B + slice - 1) / slice;
+  for (int m = 0; m < d.n_mech; ++m) out->quarter[m] = F.m[m].ch;
+  out->lds_bytes = (int64_t)lds_bytes;
+}
+
 }  // namespace avsr
+
+// the dry path of avsr_dec_persist_fwd (avsr_attn_rnn_plan): same decisions, no launch
+int avsr_dec_persist_fwd_plan(const avsr_attn_rnn* dp, avsr_attn_rnn_launch* out) {
+  using namespace avsr;
+  static thread_local DPLaunch L;
+  int variant = 0; size_t lds = 0;
+  const int rc = dp_fwd_plan(*dp, L, &variant, &lds);
+  if (rc) return rc;
+  dp_describe(*dp, L, variant, lds, dp_v64(L.mode, L.V), out);
+  return AVSR_OK;
+}
 
 // forward region of the fused workspace (the backward kernel's partials follow it)
 int64_t avsr_dec_persist_fwd_ws_floats(int32_t B, int32_t n_mech, int32_t Dmax) {
@@ -909,8 +936,7 @@ int avsr_dec_persist_fwd(const avsr_attn_rnn* dp, int32_t l_begin, int32_t l_end
   using namespace avsr;
   static thread_local DPLaunch L;
   int variant = 0; size_t lds = 0;
-  if (!dp_fwd_enabled()) return AVSR_ERR_UNSUPPORTED;
-  const int rc = dp_plan(*dp, L, &variant, &lds);
+  const int rc = dp_fwd_plan(*dp, L, &variant, &lds);
   if (rc) return rc;
   if (l_begin >= l_end) return AVSR_OK;
   hipStream_t s = (hipStream_t)stream;
@@ -928,14 +954,14 @@ int avsr_dec_persist_fwd(const avsr_attn_rnn* dp, int32_t l_begin, int32_t l_end
   L.err = sync; L.claim = sync + P_HDR; L.flags = sync + P_HDR + 8;
   if (L.mode == 1 && avsr::dev_zero(L.n_unfinished, sizeof(int32_t), s) != hipSuccess) return AVSR_ERR_HIP;
   const int B = L.B;
-  const int slice = 8 * L.R;                       // utterances per launch: one group per XCD
+  const int slice = dp_slice_rows(L.R);            // utterances per launch: one group per XCD
   for (int b0 = 0; b0 < B; b0 += slice) {
     L.b0 = b0; L.ngroups = ((B - b0 < slice ? B - b0 : slice) + L.R - 1) / L.R;
     if (avsr::dev_zero(sync + P_HDR, sizeof(int32_t) * (words - P_HDR), s) != hipSuccess) return AVSR_ERR_HIP;
     {
       ProfScope ps(dp->prof_tag == 1 ? PROF_ALIGN_PERSIST_FWD : PROF_DEC_PERSIST_FWD, s);
       void* args[] = {(void*)&L};
-      if (hipLaunchKernel(dp_kernel(variant, L.mode, L.V > 32), dim3(8 * DP_NW), dim3(DP_NT), args, lds, s) != hipSuccess) return AVSR_ERR_HIP;
+      if (hipLaunchKernel(dp_kernel(variant, L.mode, dp_v64(L.mode, L.V)), dim3(8 * DP_NW), dim3(DP_NT), args, lds, s) != hipSuccess) return AVSR_ERR_HIP;
     }
     AVSR_CHECK_LAUNCH();
   }

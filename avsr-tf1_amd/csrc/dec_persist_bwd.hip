@@ -604,14 +604,15 @@ int64_t avsr_dec_persist_bwd_ws_floats(int32_t B, int32_t n_mech) {
   return rows * DP_NW * DB_PART + (int64_t)n_mech * 4 * B * 256;
 }
 
-// The whole backward loop of avsr_attn_rnn_bwd as one persistent launch per 64-row slice.  The caller has zeroed dstate and copied
-// the final-state gradients into it exactly as for the per-step path, and runs its d h0 / d c0 tail afterwards.
-int avsr_dec_persist_bwd(const avsr_attn_rnn* dp, void* stream) {
-  using namespace avsr;
-  static thread_local DPLaunch F;
-  static thread_local DBLaunch L;
+namespace avsr {
+
+// sync words of one fused BPTT launch: header, per-XCD slot claims, flags
+static constexpr long DB_SYNC_WORDS = P_HDR + 8 + 8 * 3 * 32;
+
+// Everything avsr_dec_persist_bwd decides before it launches: the forward's plan F (variant, groups, quarters), then this kernel's own
+// declines -- its LDS figure, the 2^31 sizes, more than 64 recorded chunks, the sync words -- and the launch descriptor L.
+static int db_plan(const avsr_attn_rnn& d, DPLaunch& F, DBLaunch& L, int* variant_out, size_t* lds_out) {
   int variant = 0; size_t lds = 0;
-  const avsr_attn_rnn& d = *dp;
   if (g_dec_fused == 2) return AVSR_ERR_UNSUPPORTED;
   int rc = dp_plan(d, F, &variant, &lds);
   if (rc) return rc;
@@ -650,10 +651,38 @@ int avsr_dec_persist_bwd(const avsr_attn_rnn* dp, void* stream) {
     X.T = M.T; X.D = M.D; X.type = M.type; X.nc_rec = F.m[m].nc_rec; X.ch = F.m[m].ch; X.lds_off = F.m[m].lds_off;
     if ((long)d.B * d.L * M.D * 4 >= (1L << 31) || (long)d.B * d.L * M.T * 4 >= (1L << 31) || X.nc_rec > 64) return AVSR_ERR_UNSUPPORTED;
   }
+  if (DB_SYNC_WORDS > g_sync_ints) return AVSR_ERR_UNSUPPORTED;
+  *variant_out = variant; *lds_out = lds;
+  return AVSR_OK;
+}
+
+}  // namespace avsr
+
+// the dry path of avsr_dec_persist_bwd (avsr_attn_rnn_plan): same decisions, no launch
+int avsr_dec_persist_bwd_plan(const avsr_attn_rnn* dp, avsr_attn_rnn_launch* out) {
+  using namespace avsr;
+  static thread_local DPLaunch F;
+  static thread_local DBLaunch L;
+  int variant = 0; size_t lds = 0;
+  const int rc = db_plan(*dp, F, L, &variant, &lds);
+  if (rc) return rc;
+  dp_describe(*dp, F, variant, lds, false, out);
+  return AVSR_OK;
+}
+
+// The whole backward loop of avsr_attn_rnn_bwd as one persistent launch per 64-row slice.  The caller has zeroed dstate and copied
+// the final-state gradients into it exactly as for the per-step path, and runs its d h0 / d c0 tail afterwards.
+int avsr_dec_persist_bwd(const avsr_attn_rnn* dp, void* stream) {
+  using namespace avsr;
+  static thread_local DPLaunch F;
+  static thread_local DBLaunch L;
+  int variant = 0; size_t lds = 0;
+  const avsr_attn_rnn& d = *dp;
+  const int rc = db_plan(d, F, L, &variant, &lds);
+  if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   int32_t* sync = g_sync;
-  const long words = P_HDR + 8 + 8 * 3 * 32;
-  if (words > g_sync_ints) return AVSR_ERR_UNSUPPORTED;
+  const long words = DB_SYNC_WORDS;
   static bool attr_set = false;
   if (!attr_set) {
     for (int v = 0; v < 5; ++v)
@@ -661,7 +690,7 @@ int avsr_dec_persist_bwd(const avsr_attn_rnn* dp, void* stream) {
     attr_set = true;
   }
   L.err = sync; L.claim = sync + P_HDR; L.flags = sync + P_HDR + 8;
-  const int slice = 8 * F.R;
+  const int slice = dp_slice_rows(F.R);
   for (int b0 = 0; b0 < d.B; b0 += slice) {
     L.b0 = b0; L.ngroups = ((d.B - b0 < slice ? d.B - b0 : slice) + F.R - 1) / F.R;
     if (avsr::dev_zero(sync + P_HDR, sizeof(int32_t) * (words - P_HDR), s) != hipSuccess) return AVSR_ERR_HIP;

@@ -666,6 +666,20 @@ def attn_rnn_set_fused(on):
     check(_L().avsr_attn_rnn_set_fused(int(on)), "avsr_attn_rnn_set_fused")   # 0 off, 1 / True both, 2 forward only, 3 backward only
 
 
+def attn_rnn_plan(desc, bwd=False):
+    """avsr_attn_rnn_plan: what attn_rnn_fwd / attn_rnn_bwd (bwd=True) would launch for this AttnRnn descriptor under the current
+    attn_rnn_set_fused setting and registered sync scratch, decided by the library's host code without touching HIP (no GPU needed;
+    descriptor pointers are only tested for NULL).  A dict with the fields of avsr_attn_rnn_launch: `form` "per_step" / "fused",
+    `quarter` a tuple of desc.n_mech widths."""
+    from ._lib import AttnRnnLaunch
+    out = AttnRnnLaunch()
+    check(_L().avsr_attn_rnn_plan(C.byref(desc), int(bool(bwd)), C.byref(out)), "avsr_attn_rnn_plan")
+    rec = {f: getattr(out, f) for f, _ in AttnRnnLaunch._fields_ if f not in ("pad_", "quarter")}
+    rec["form"] = ("per_step", "fused")[out.form]
+    rec["quarter"] = tuple(out.quarter[m] for m in range(desc.n_mech))
+    return rec
+
+
 def attn_rnn_set_beam_kernel(on):
     """Beam search kernels: 1 / True all beam-shaped kernels (default), 2 the K-hypotheses-per-workgroup attention kernel only, 0 the
     general kernels everywhere (include/avsr_hip.h)."""

@@ -246,7 +246,8 @@ int avsr_rnn_plan(const avsr_rnn_stack* stacks, int32_t n_stacks, int32_t bwd, i
  *   state scratch 4*B*H.
  *   per mechanism: scores [B][L][T] raw scores (Luong: un-scaled), ctx [B][L][D], pq [B][L][H]
  *   (Bahdanau), pstat [L][2][nchunk][B], pctx scratch [nchunk][B][D], with nchunk = ceil(T / chunk).
- * Backward adds: dgates [B][L][H][4], dstate scratch 12*B*H, datt [B][L][A], dq [B][L][H];
+ * Backward adds: dgates [B][L][H][4], dstate scratch 12*B*H, datt [B][L][A], dq scratch [B][L][H]
+ *   (required with a Luong mechanism or dcell_ext; a staging buffer of the per-step path, not an output: most forms never write it);
  *   per mechanism dscores [B][L][T], dctx [B][L][D], dpq [B][L][H] (Bahdanau), pdq scratch
  *   [nchunk][B][H].  Inputs datt_ext [B][L][A] / dcell_ext [B][L][H]: gradient of the loss wrt the
  *   emitted attention / cell output of every step (from the output layer, or from the consumer of the
@@ -408,6 +409,28 @@ int avsr_attn_rnn_fused_fwd_active(const avsr_attn_rnn* d);
  * under the same conditions.  Process-wide switch: 0 per-step launches, 1 (default) fused forward and backward, 2 forward only,
  * 3 backward only; the path also needs avsr_rnn_set_persistent's sync scratch. */
 int avsr_attn_rnn_set_fused(int32_t on);
+/* Read-only plan query: what avsr_attn_rnn_fwd (bwd == 0, any step range) or avsr_attn_rnn_bwd (bwd == 1) WOULD launch for this descriptor
+ * under the current avsr_attn_rnn_set_fused setting and the sync scratch registered with avsr_rnn_set_persistent.  Decided by the same
+ * host code as the calls on its dry path: the descriptor's pointers are only tested for NULL, never dereferenced, nothing is launched and
+ * no HIP call is made (runs without a GPU).  Returns AVSR_OK and one record, or the AVSR_ERR_ARG / AVSR_ERR_UNSUPPORTED the call's own
+ * argument checks would return.
+ *   form            AVSR_ATTN_FORM_*
+ *   variant         fused: 0 one Luong memory (<= 128 frames per quarter), 1 two memories (<= 32, <= 128), 2 two memories (<= 128, <= 32),
+ *                   3 the attentive layer in 16-row groups (one memory, <= 64 frames per half), 4 one (normed) Bahdanau memory; per-step: -1
+ *   rows_per_group  batch rows of a group (8 or 16; 0 per-step)
+ *   v64             1 = the 33..64-symbol template of the forward kernel (always 0 for the BPTT: it has no output layer)
+ *   launches        fused: kernel launches = slices of 8 groups, ceil(B / (8 * rows_per_group)); per-step: cell launches = L
+ *   quarter[m]      frames of memory m resident in one workgroup: ceil(T_m / (32 / rows_per_group)) (0 per-step and for m >= n_mech)
+ *   lds_bytes       dynamic LDS of a launch (the BPTT kernel has its own figure; 0 per-step) */
+#define AVSR_ATTN_FORM_PER_STEP 0         /* one launch per step and phase (csrc/attn_rnn.hip) */
+#define AVSR_ATTN_FORM_FUSED 1            /* dec_persist_kernel / dec_persist_bwd_kernel, one launch per slice */
+typedef struct avsr_attn_rnn_launch {
+  int32_t form, variant, rows_per_group, v64;
+  int32_t launches, pad_;
+  int32_t quarter[AVSR_MAX_MECH];
+  int64_t lds_bytes;
+} avsr_attn_rnn_launch;
+int avsr_attn_rnn_plan(const avsr_attn_rnn* d, int32_t bwd, avsr_attn_rnn_launch* out);
 /* Beam search (mode 3): which kernels run the B * K-row steps.  1 (default) = all beam-shaped kernels: the per-step attention
  * as one workgroup per (utterance, chunk) serving all K hypotheses over the shared memories, scores and contexts on the matrix
  * pipe with the hypotheses as one MFMA row tile (attn_fwd_beam_mfma_kernel), and the LSTM cell / attention layers as 64 x 64-tiled products with row-gathered operands
