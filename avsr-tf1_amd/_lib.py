@@ -149,6 +149,11 @@ class ConvLaunch(C.Structure):
                                          "slab", "pad_")]
 
 
+class BnPlan(C.Structure):
+    """avsr_bn_plan: the launch geometry avsr_batchnorm_plan reports."""
+    _fields_ = [(n, C.c_int32) for n in ("blocks", "rows_per_block", "G", "vec", "direct", "apply_grid", "err", "pad_")]
+
+
 class Conv3dDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("B", "T", "H", "W", "Ci", "Co", "kt", "kh", "kw", "stride", "pad_f", "pad_t", "pad_l", "Ho", "Wo",
                                          "relu")] + [("scale", C.c_void_p), ("shift", C.c_void_p)]
@@ -238,7 +243,7 @@ class TransposeJob(C.Structure):
 
 _STRUCTS = {"avsr_dec_layer": DecLayer, "avsr_mat": Mat, "avsr_gemm_desc": GemmDesc, "avsr_rnn_layer": RnnLayer, "avsr_rnn_stack": RnnStack,
             "avsr_rnn_launch": RnnLaunch,
-            "avsr_conv_desc": ConvDesc, "avsr_conv_launch": ConvLaunch, "avsr_conv3d_desc": Conv3dDesc, "avsr_logmel_args": LogmelArgs, "avsr_spec_augment_args": SpecAugmentArgs, "avsr_video_augment_args": VideoAugmentArgs, "avsr_ctc_args": CtcArgs, "avsr_attn_mech": AttnMech, "avsr_attn_rnn": AttnRnn, "avsr_transpose_job": TransposeJob,
+            "avsr_conv_desc": ConvDesc, "avsr_conv_launch": ConvLaunch, "avsr_bn_plan": BnPlan, "avsr_conv3d_desc": Conv3dDesc, "avsr_logmel_args": LogmelArgs, "avsr_spec_augment_args": SpecAugmentArgs, "avsr_video_augment_args": VideoAugmentArgs, "avsr_ctc_args": CtcArgs, "avsr_attn_mech": AttnMech, "avsr_attn_rnn": AttnRnn, "avsr_transpose_job": TransposeJob,
             "avsr_attn_rnn_launch": AttnRnnLaunch,
             "avsr_colsum_job": ColsumJob, "avsr_beam_lm": BeamLm, "avsr_beam_ctc": BeamCtc, "avsr_ctc_prefix_args": CtcPrefixArgs,
             "avsr_ctc_prefix_lm": CtcPrefixLm, "avsr_ctc_prefix_ngram": CtcPrefixNgram, "avsr_beam_ngram": BeamNgram,
@@ -271,6 +276,7 @@ _SIGS = {
     "avsr_conv_bwd_weight_bn": [C.POINTER(ConvDesc), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _i64, _vp],
     "avsr_conv_bwd_weight_bn_supported": [C.POINTER(ConvDesc)],
     "avsr_conv_plan": [C.POINTER(ConvDesc), _i32, _i32, _i64, C.POINTER(ConvLaunch), _i32],
+    "avsr_batchnorm_plan": [_i32, _i64, _i32, _i64, _i32, C.POINTER(BnPlan)],
     "avsr_bn_bwd_finalize": [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp],
     "avsr_bn_bwd_apply": [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _vp],
     "avsr_bn_bwd_stage1": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, C.POINTER(_i32), _vp],

@@ -38,7 +38,7 @@ namespace {
 // B*T rows including zero padding.  Stage 1: partial sums.  Stage 2: partial centred squares.  Stage 3:
 // normalise (+ moving-average update and saved mean / inv-std by block 0).
 // Thread layout of the row-walking BN kernels: G = 256 / F row sub-groups of F columns (F < 256), so narrow feature
-// vectors (80 audio / 128 video) still use the whole block; partials are per (block, sub-group).
+// vectors (80 audio / 128 video) still use the whole block; the sub-groups are combined in LDS, one partial row per block.
 __global__ void bn_partial_sum_kernel(const float* x, float* part, int rows, int F, int rows_per_blk) {
   __shared__ float red[256];
   const int G = F < 256 ? 256 / F : 1;
@@ -57,7 +57,7 @@ __global__ void bn_partial_sum_kernel(const float* x, float* part, int rows, int
   }
 }
 
-// mean[f] = sum of partials / rows   (one launch, one block per 32 columns; npart = nblk * G)
+// mean[f] = sum of partials / rows   (one launch, one block per 32 columns; npart = nblk: a block emits ONE partial row whatever G is)
 // total != nullptr: the divisor is the (all-reduced) row count total[0] instead of `rows` (sync batch-norm).
 __global__ __launch_bounds__(1024) void bn_mean_kernel(const float* part, int npart, float* mean, int rows, int F,
                                                        const float* total = nullptr) {
@@ -154,14 +154,14 @@ __global__ void bn_xhat_kernel(const float* x, const float* mean, const float* i
   }
 }
 
-// partial rows of the row-walking statistic passes: 64 rows per block, at most 2048 blocks (the merge stays one short launch), fewer
-// when the scratch cannot hold one row [F] per block.  Returns the block count (0: the scratch holds none), *rpb_out = rows per block.
-int bn_blocks(int rows, int F, int64_t scratch_floats, int* rpb_out) {
+// partial rows of the row-walking passes: 64 rows per block, at most 2048 blocks (the merge stays one short launch), fewer when the
+// scratch cannot hold one row [width] per block.  Returns the block count (0: the scratch holds none), *rpb_out = rows per block.
+int bn_blocks(int rows, int width, int64_t scratch_floats, int* rpb_out) {
   const int maxblk = 2048;
   int rpb = rows > 64 * maxblk ? (rows + maxblk - 1) / maxblk : 64;
   int nblk = (rows + rpb - 1) / rpb;
-  if ((long)nblk * F > scratch_floats) {
-    nblk = (int)(scratch_floats / F);
+  if ((long)nblk * width > scratch_floats) {
+    nblk = scratch_floats < width ? 0 : (int)(scratch_floats / width);
     if (nblk < 1) return 0;
     rpb = (rows + nblk - 1) / nblk;
     nblk = (rows + rpb - 1) / rpb;
@@ -170,16 +170,96 @@ int bn_blocks(int rows, int F, int64_t scratch_floats, int* rpb_out) {
   return nblk;
 }
 
+// grid of the flat float4 passes: one float4 per thread-iteration, at most `cap` blocks of 256
+int bn_flat_grid(long n4, int cap) {
+  long b = (n4 + 255) / 256;
+  return (int)(b > cap ? cap : b);
+}
+
+// The launch geometry of every entry point of this file whose grid depends on its arguments (avsr_batchnorm_plan reports it, the entry
+// points launch by it: the two cannot drift apart).  Pointers are the callers' business; the argument checks on rows, F and the scratch
+// are here.  Returns p->err.
+int bn_plan(int op, int64_t rows, int F, int64_t scratch_floats, int flags, avsr_bn_plan* p) {
+  *p = avsr_bn_plan{0, 0, 0, 0, 0, 0, AVSR_ERR_ARG, 0};
+  const bool stage = op == AVSR_BN_PLAN_BWD_STAGE1 || op == AVSR_BN_PLAN_BWD_APPLY;
+  if (op < AVSR_BN_PLAN_FWD || op > AVSR_BN_PLAN_BWD_APPLY || rows <= 0 || F <= 0 || (!stage && rows > 0x7fffffffL)) return p->err;
+  p->G = F < 256 ? 256 / F : 1;
+  switch (op) {
+    case AVSR_BN_PLAN_FWD:                               // scratch: partials [blocks][F] | mean [F] | invstd [F]
+    case AVSR_BN_PLAN_SYNC_SUM:                          // scratch: partials [blocks][F]
+    case AVSR_BN_PLAN_SYNC_SQSUM: {
+      if (F % 4) return p->err;
+      p->blocks = bn_blocks((int)rows, F, op == AVSR_BN_PLAN_FWD ? scratch_floats - 2 * F : scratch_floats, &p->rows_per_block);
+      if (!p->blocks) return p->err;
+      if (op == AVSR_BN_PLAN_FWD) p->apply_grid = bn_flat_grid(rows * F / 4, 4096);
+      break;
+    }
+    case AVSR_BN_PLAN_BWD: {                             // scratch: partials [blocks][2F] | sums [2F]
+      const long n = rows * F;
+      p->blocks = bn_blocks((int)rows, 2 * F, scratch_floats - 2 * F, &p->rows_per_block);
+      if (!p->blocks) return p->err;
+      p->vec = F >= 4 && 1024 % F == 0 && (flags & AVSR_BN_PLAN_ALIGNED) && rows >= 4096;
+      if (p->vec) {                                      // the float4 kernels stride the flat map: no rows per block
+        int vb = bn_flat_grid(n / 4, 1024);
+        if ((long)vb * 2 * F + 2 * F > scratch_floats) vb = (int)((scratch_floats - 2 * F) / (2L * F));
+        if (vb < 1) return p->err;
+        p->blocks = vb;
+        p->rows_per_block = 0;
+      }
+      p->direct = (flags & AVSR_BN_PLAN_DIRECT) != 0;
+      if (flags & AVSR_BN_PLAN_DX) p->apply_grid = p->vec ? bn_flat_grid(n / 4, 4096) : blocks_for(n, 256, 8192);
+      break;
+    }
+    case AVSR_BN_PLAN_SYNC_MOMENTS: {                    // scratch: fp64 partials [blocks][2F]
+      int nblk = (int)((rows + 63) / 64);
+      if (nblk > 1024) nblk = 1024;
+      while (nblk > 1 && (long)nblk * 2 * F * 2 > scratch_floats) nblk /= 2;
+      if ((long)nblk * 2 * F * 2 > scratch_floats) return p->err;
+      p->rows_per_block = (int)((rows + nblk - 1) / nblk);
+      p->blocks = (int)((rows + p->rows_per_block - 1) / p->rows_per_block);
+      p->G = 1;
+      break;
+    }
+    case AVSR_BN_PLAN_BWD_STAGE1: {                      // G: the row lanes RL of a block
+      if (F % 4 || F > 1024) return p->err;
+      const int RL = 256 / (F / 4);
+      long per = (rows + 511) / 512;
+      if (per < 8L * RL) per = 8L * RL;                  // at least eight passes of a block's row lanes
+      if (per > 0x7fffffffL) return p->err;
+      p->G = RL;
+      p->rows_per_block = (int)per;
+      p->blocks = (int)((rows + per - 1) / per);
+      break;
+    }
+    default: {                                           // AVSR_BN_PLAN_BWD_APPLY
+      if (F % 4) return p->err;
+      const long n4 = rows * (F / 4);
+      long blocks = (n4 + 256 * 8 - 1) / (256 * 8);
+      if (blocks > 2048) blocks = 2048;
+      p->G = 0;
+      p->apply_grid = (int)blocks;
+      break;
+    }
+  }
+  return p->err = AVSR_OK;
+}
+
 }  // namespace
+
+extern "C" int avsr_batchnorm_plan(int32_t op, int64_t rows, int32_t F, int64_t scratch_floats, int32_t flags, avsr_bn_plan* out) {
+  if (!out) return AVSR_ERR_ARG;
+  const int rc = bn_plan(op, rows, F, scratch_floats, flags, out);
+  if (rc) *out = avsr_bn_plan{0, 0, 0, 0, 0, 0, rc, 0};   // a refused call launches nothing
+  return rc;
+}
 
 extern "C" int avsr_batchnorm_fwd_ex(const float* x, float* y, int32_t rows, int32_t F, const float* gamma, const float* beta,
                                      float* moving_mean, float* moving_var, float* save_mean, float* save_invstd, int32_t training,
                                      float eps, float momentum, int32_t relu, int32_t bessel, float* scratch, int64_t scratch_floats, void* stream) {
-  if (!x || !y || !gamma || !beta || rows <= 0 || F <= 0 || !scratch) return AVSR_ERR_ARG;
-  if (F % 4) return AVSR_ERR_ARG;
-  int rpb;
-  const int nblk = bn_blocks(rows, F, scratch_floats - 2 * F, &rpb);      // 2*F floats of the scratch hold mean | invstd
-  if (!nblk) return AVSR_ERR_ARG;
+  if (!x || !y || !gamma || !beta || rows <= 0 || F <= 0 || !scratch || (!moving_mean != !moving_var)) return AVSR_ERR_ARG;
+  avsr_bn_plan pl;
+  if (bn_plan(AVSR_BN_PLAN_FWD, rows, F, scratch_floats, 0, &pl)) return pl.err;      // 2*F floats of the scratch hold mean | invstd
+  const int nblk = pl.blocks, rpb = pl.rows_per_block;
   // scratch: partials [nblk][F] | mean [F] | invstd [F]  (mean / invstd go to save_mean / save_invstd when given)
   float* part = scratch;
   float* mean_v = save_mean ? save_mean : scratch + (long)nblk * F;
@@ -198,9 +278,7 @@ extern "C" int avsr_batchnorm_fwd_ex(const float* x, float* y, int32_t rows, int
     return AVSR_ERR_ARG;
   }
   const long n4 = (long)rows * F / 4;
-  int blocks = (int)((n4 + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(bn_apply_kernel, dim3(blocks), dim3(256), 0, S_(stream), x, mean_v, invstd_v, moving_mean, moving_var, gamma, beta, y,
+  hipLaunchKernelGGL(bn_apply_kernel, dim3(pl.apply_grid), dim3(256), 0, S_(stream), x, mean_v, invstd_v, moving_mean, moving_var, gamma, beta, y,
                      n4, F, training, eps, relu);
   AVSR_CHECK_LAUNCH();
   return AVSR_OK;
@@ -218,9 +296,7 @@ extern "C" int avsr_batchnorm_apply(const float* x, float* y, int32_t rows, int3
                                     const float* invstd, int32_t relu, void* stream) {
   if (!x || !y || !gamma || !beta || !mean || !invstd || rows <= 0 || F <= 0 || F % 4) return AVSR_ERR_ARG;
   const long n4 = (long)rows * F / 4;
-  int blocks = (int)((n4 + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(bn_apply_kernel, dim3(blocks), dim3(256), 0, S_(stream), x, mean, invstd, nullptr, nullptr, gamma, beta, y, n4, F, 1, 0.f, relu);
+  hipLaunchKernelGGL(bn_apply_kernel, dim3(bn_flat_grid(n4, 4096)), dim3(256), 0, S_(stream), x, mean, invstd, nullptr, nullptr, gamma, beta, y, n4, F, 1, 0.f, relu);
   AVSR_CHECK_LAUNCH();
   return AVSR_OK;
 }
@@ -349,45 +425,33 @@ extern "C" int avsr_batchnorm_bwd(const float* x, const float* dy, const float* 
                                   const float* invstd, float* dx, float* dgamma, float* dbeta, int32_t rows, int32_t F, int32_t relu,
                                   float dx_beta, float* scratch, int64_t scratch_floats, void* stream) {
   if (!x || !dy || !gamma || !beta || !mean || !invstd || !scratch || rows <= 0 || F <= 0) return AVSR_ERR_ARG;
-  const int maxblk = 2048;
-  int rpb = rows > 64 * maxblk ? (rows + maxblk - 1) / maxblk : 64;
-  int nblk = (rows + rpb - 1) / rpb;
-  if ((long)nblk * 2 * F + 2 * F > scratch_floats) {
-    nblk = (int)((scratch_floats - 2 * F) / (2L * F));
-    if (nblk < 1) return AVSR_ERR_ARG;
-    rpb = (rows + nblk - 1) / nblk;
-    nblk = (rows + rpb - 1) / rpb;
-  }
   float* part = scratch;
   const long n = (long)rows * F;
   auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-  const bool vec = F >= 4 && 1024 % F == 0 && al16(x) && al16(dy) && (!dx || al16(dx)) && al16(gamma) && al16(beta) && al16(mean) && al16(invstd) &&
-                   al16(scratch) && rows >= 4096;
-  if (vec) {
-    int vb = (int)((n / 4 + 255) / 256);
-    if (vb > 1024) vb = 1024;
-    if ((long)vb * 2 * F + 2 * F > scratch_floats) vb = (int)((scratch_floats - 2 * F) / (2L * F));
-    if (vb < 1) return AVSR_ERR_ARG;
-    nblk = vb;
-  }
+  // what the plan takes from the pointers: every operand on 16 bytes (the float4 kernels), both sums wanted on 16 bytes (written
+  // where the caller wants them), a dx to write
+  const bool aligned = al16(x) && al16(dy) && (!dx || al16(dx)) && al16(gamma) && al16(beta) && al16(mean) && al16(invstd) && al16(scratch);
+  const bool direct = dbeta && dgamma && al16(dbeta) && al16(dgamma);
+  avsr_bn_plan pl;
+  if (bn_plan(AVSR_BN_PLAN_BWD, rows, F, scratch_floats, (aligned ? AVSR_BN_PLAN_ALIGNED : 0) | (direct ? AVSR_BN_PLAN_DIRECT : 0) | (dx ? AVSR_BN_PLAN_DX : 0), &pl))
+    return pl.err;
+  const int nblk = pl.blocks, rpb = pl.rows_per_block;
+  const bool vec = pl.vec != 0;
   float* sums = scratch + (long)nblk * 2 * F;          // [2F]: sum dy' | sum dy' xhat
   if (vec) hipLaunchKernelGGL(bn_bwd_partial4_kernel, dim3(nblk), dim3(256), 0, S_(stream), x, dy, gamma, beta, mean, invstd, part, n / 4, F, relu);
   else hipLaunchKernelGGL(bn_bwd_partial_kernel, dim3(nblk), dim3(256), 0, S_(stream), x, dy, gamma, beta, mean, invstd, part, rows, F, rpb, relu);
   AVSR_CHECK_LAUNCH();
   // the reduced sums ARE d beta | d gamma: one reduction launch writes them where the caller wants them and the apply pass reads
   // them from there (16-byte aligned destinations for the vector kernel; else through the scratch + two copies)
-  const bool direct = dbeta && dgamma && al16(dbeta) && al16(dgamma);
   float* const s1 = direct ? dbeta : sums;
   float* const s2 = direct ? dgamma : sums + F;
   { const int rc = avsr_colsum_final_launch_split(part, 2L * F, nblk, s1, s2, F, 2 * F, 1.0f, 0.0f, stream); if (rc) return rc; }
   if (dx) {
     if (vec) {
-      int ab = (int)((n / 4 + 255) / 256);
-      if (ab > 4096) ab = 4096;
-      hipLaunchKernelGGL(bn_bwd_apply4_kernel, dim3(ab), dim3(256), 0, S_(stream), x, dy, gamma, beta, mean, invstd, s1, s2, dx, n / 4, rows, F, relu,
+      hipLaunchKernelGGL(bn_bwd_apply4_kernel, dim3(pl.apply_grid), dim3(256), 0, S_(stream), x, dy, gamma, beta, mean, invstd, s1, s2, dx, n / 4, rows, F, relu,
                          dx_beta);
     } else {
-      hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(blocks_for(n, 256, 8192)), dim3(256), 0, S_(stream), x, dy, gamma, beta, mean, invstd, s1, s2, dx, n, rows,
+      hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(pl.apply_grid), dim3(256), 0, S_(stream), x, dy, gamma, beta, mean, invstd, s1, s2, dx, n, rows,
                          F, relu, dx_beta);
     }
     AVSR_CHECK_LAUNCH();
@@ -403,9 +467,9 @@ extern "C" int avsr_batchnorm_bwd(const float* x, const float* dy, const float* 
 extern "C" int avsr_batchnorm_sync_sum(const float* x, int32_t rows, int32_t F, float* sum_out, float* scratch,
                                        int64_t scratch_floats, void* stream) {
   if (!x || !sum_out || !scratch || rows <= 0 || F <= 0 || F % 4) return AVSR_ERR_ARG;
-  int rpb;
-  const int nblk = bn_blocks(rows, F, scratch_floats, &rpb);
-  if (!nblk) return AVSR_ERR_ARG;
+  avsr_bn_plan pl;
+  if (bn_plan(AVSR_BN_PLAN_SYNC_SUM, rows, F, scratch_floats, 0, &pl)) return pl.err;
+  const int nblk = pl.blocks, rpb = pl.rows_per_block;
   hipLaunchKernelGGL(bn_partial_sum_kernel, dim3(nblk), dim3(256), 0, S_(stream), x, scratch, rows, F, rpb);
   AVSR_CHECK_LAUNCH();
   hipLaunchKernelGGL(bn_mean_kernel, dim3((F + 31) / 32), dim3(1024), 0, S_(stream), scratch, nblk, sum_out, 1, F, nullptr);
@@ -417,9 +481,9 @@ extern "C" int avsr_batchnorm_sync_sqsum(const float* x, int32_t rows, int32_t F
                                          const float* total_rows, float* mean_out, float* sq_out, float* scratch,
                                          int64_t scratch_floats, void* stream) {
   if (!x || !sum_global || !total_rows || !mean_out || !sq_out || !scratch || rows <= 0 || F <= 0 || F % 4) return AVSR_ERR_ARG;
-  int rpb;
-  const int nblk = bn_blocks(rows, F, scratch_floats, &rpb);
-  if (!nblk) return AVSR_ERR_ARG;
+  avsr_bn_plan pl;
+  if (bn_plan(AVSR_BN_PLAN_SYNC_SQSUM, rows, F, scratch_floats, 0, &pl)) return pl.err;
+  const int nblk = pl.blocks, rpb = pl.rows_per_block;
   hipLaunchKernelGGL(bn_mean_kernel, dim3((F + 31) / 32), dim3(1024), 0, S_(stream), sum_global, 1, mean_out, 1, F, total_rows);
   AVSR_CHECK_LAUNCH();
   hipLaunchKernelGGL(bn_partial_sq_kernel, dim3(nblk), dim3(256), 0, S_(stream), x, mean_out, scratch, rows, F, rpb);
@@ -433,15 +497,14 @@ extern "C" int avsr_batchnorm_sync_apply(const float* x, float* y, int32_t rows,
                                          const float* beta, float* moving_mean, float* moving_var, const float* mean,
                                          const float* sq_global, const float* total_rows, float* invstd_out, float eps,
                                          float momentum, int32_t relu, void* stream) {
-  if (!x || !y || !gamma || !beta || !mean || !sq_global || !total_rows || !invstd_out || rows <= 0 || F <= 0 || F % 4)
+  if (!x || !y || !gamma || !beta || !mean || !sq_global || !total_rows || !invstd_out || rows <= 0 || F <= 0 || F % 4 ||
+      (!moving_mean != !moving_var))
     return AVSR_ERR_ARG;
   hipLaunchKernelGGL(bn_var_kernel, dim3((F + 31) / 32), dim3(1024), 0, S_(stream), sq_global, 1, mean, invstd_out, moving_mean,
                      moving_var, 1, F, eps, momentum, 0, total_rows);
   AVSR_CHECK_LAUNCH();
   const long n4 = (long)rows * F / 4;
-  int blocks = (int)((n4 + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(bn_apply_kernel, dim3(blocks), dim3(256), 0, S_(stream), x, mean, invstd_out, moving_mean, moving_var, gamma, beta, y,
+  hipLaunchKernelGGL(bn_apply_kernel, dim3(bn_flat_grid(n4, 4096)), dim3(256), 0, S_(stream), x, mean, invstd_out, moving_mean, moving_var, gamma, beta, y,
                      n4, F, 1, eps, relu);
   AVSR_CHECK_LAUNCH();
   return AVSR_OK;
@@ -472,12 +535,9 @@ __global__ __launch_bounds__(256) void bn_moments_final_kernel(const double* __r
 extern "C" int avsr_batchnorm_sync_moments(const float* x, int32_t rows, int32_t F, double* out64, float* scratch, int64_t scratch_floats,
                                            void* stream) {
   if (!x || !out64 || !scratch || rows <= 0 || F <= 0 || ((uintptr_t)scratch & 7)) return AVSR_ERR_ARG;
-  int nblk = (rows + 63) / 64;
-  if (nblk > 1024) nblk = 1024;
-  while (nblk > 1 && (long)nblk * 2 * F * 2 > scratch_floats) nblk /= 2;
-  if ((long)nblk * 2 * F * 2 > scratch_floats) return AVSR_ERR_ARG;
-  const int rpb = (rows + nblk - 1) / nblk;
-  nblk = (rows + rpb - 1) / rpb;
+  avsr_bn_plan pl;
+  if (bn_plan(AVSR_BN_PLAN_SYNC_MOMENTS, rows, F, scratch_floats, 0, &pl)) return pl.err;
+  const int nblk = pl.blocks, rpb = pl.rows_per_block;
   double* part = reinterpret_cast<double*>(scratch);
   hipLaunchKernelGGL(bn_moments_partial_kernel, dim3(nblk), dim3(256), 0, S_(stream), x, part, rows, F, rpb);
   AVSR_CHECK_LAUNCH();
@@ -646,7 +706,8 @@ __global__ __launch_bounds__(256) void bn_bwd_coef_apply_kernel(const float* __r
 extern "C" int avsr_bn_finalize(const float* part, int32_t nparts, int32_t C, int64_t count, float eps, float momentum, float* mean,
                                 float* invstd, float* mov_mean, float* mov_var, const float* gamma, const float* beta, float* scale,
                                 float* shift, void* stream) {
-  if (!part || nparts <= 0 || C <= 0 || count <= 0 || !mean || !invstd || (scale && (!gamma || !beta || !shift))) return AVSR_ERR_ARG;
+  if (!part || nparts <= 0 || C <= 0 || count <= 0 || !mean || !invstd || (scale && (!gamma || !beta || !shift)) || (!mov_mean != !mov_var))
+    return AVSR_ERR_ARG;
   hipLaunchKernelGGL(bn_finalize_kernel<true>, dim3((C + 15) / 16), dim3(1024), 0, S_(stream), part, nparts, C, (double)count, eps, momentum, mean,
                      invstd, mov_mean, mov_var, gamma, beta, scale, shift);
   AVSR_CHECK_LAUNCH();
@@ -676,10 +737,10 @@ extern "C" int avsr_bn_eval_affine(const float* gamma, const float* beta, const 
 extern "C" int avsr_bn_bwd_stage1(const float* dy, const float* x, const float* scale, const float* shift, const float* y, float* dz, int64_t rows,
                                   int32_t C, float* part, int32_t* nparts, void* stream) {
   if (!dy || !x || !dz || !part || !nparts || rows <= 0 || C <= 0 || C % 4 || C > 1024 || (!scale && !y) || (scale && !shift)) return AVSR_ERR_ARG;
-  const int RL = 256 / (C / 4);
-  long per = (rows + 511) / 512;
-  if (per < 8L * RL) per = 8L * RL;                          // at least eight passes of a block's row lanes
-  const int blocks = (int)((rows + per - 1) / per);
+  avsr_bn_plan pl;
+  if (bn_plan(AVSR_BN_PLAN_BWD_STAGE1, rows, C, 0, 0, &pl)) return pl.err;
+  const int blocks = pl.blocks;
+  const long per = pl.rows_per_block;
   *nparts = blocks;
   hipLaunchKernelGGL(bn_bwd_stage1_kernel, dim3(blocks), dim3(256), 0, S_(stream), dy, x, scale, shift, y, dz, (long)rows, C, per, part);
   AVSR_CHECK_LAUNCH();
@@ -697,11 +758,10 @@ extern "C" int avsr_bn_bwd_finalize(const float* part, int32_t nparts, int32_t C
 
 extern "C" int avsr_bn_bwd_apply(const float* dz, const float* x, const float* k, float* dx, int64_t rows, int32_t C, float beta, void* stream) {
   if (!dz || !x || !k || !dx || rows <= 0 || C <= 0 || C % 4) return AVSR_ERR_ARG;
+  avsr_bn_plan pl;
+  if (bn_plan(AVSR_BN_PLAN_BWD_APPLY, rows, C, 0, 0, &pl)) return pl.err;
   const long n4 = rows * (C / 4);
-  long blocks = (n4 + 256 * 8 - 1) / (256 * 8);
-  if (blocks > 2048) blocks = 2048;
-  if (blocks < 1) blocks = 1;
-  hipLaunchKernelGGL(bn_bwd_coef_apply_kernel, dim3((int)blocks), dim3(256), 0, S_(stream), dz, x, k, dx, n4, C / 4, C, beta);
+  hipLaunchKernelGGL(bn_bwd_coef_apply_kernel, dim3(pl.apply_grid), dim3(256), 0, S_(stream), dz, x, k, dx, n4, C / 4, C, beta);
   AVSR_CHECK_LAUNCH();
   return AVSR_OK;
 }
@@ -741,7 +801,7 @@ extern "C" int avsr_bn_partials_f64(const float* part, int32_t nparts, int32_t C
 }
 extern "C" int avsr_bn_finalize_f64(const double* sums, int32_t C, float eps, float momentum, float* mean, float* invstd, float* mov_mean,
                                     float* mov_var, const float* gamma, const float* beta, float* scale, float* shift, void* stream) {
-  if (!sums || C <= 0 || !mean || !invstd || (scale && (!gamma || !beta || !shift))) return AVSR_ERR_ARG;
+  if (!sums || C <= 0 || !mean || !invstd || (scale && (!gamma || !beta || !shift)) || (!mov_mean != !mov_var)) return AVSR_ERR_ARG;
   hipLaunchKernelGGL(bn_finalize_f64_kernel, dim3((C + 63) / 64), dim3(64), 0, S_(stream), sums, C, eps, momentum, mean, invstd, mov_mean, mov_var,
                      gamma, beta, scale, shift);
   AVSR_CHECK_LAUNCH();

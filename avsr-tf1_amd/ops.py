@@ -703,6 +703,22 @@ def batchnorm_bwd(x, dy, gamma, beta, mean, invstd, dx, dgamma, dbeta, rows, F, 
                                   rows, F, int(relu), float(dx_beta), fptr(scratch), scratch.numel(), _s()), "avsr_batchnorm_bwd")
 
 
+BN_PLAN_OPS = {"fwd": 0, "bwd": 1, "sync_sum": 2, "sync_sqsum": 3, "sync_moments": 4, "bwd_stage1": 5, "bwd_apply": 6}
+BN_PLAN_FLAGS = {"aligned": 1, "direct": 2, "dx": 4}
+
+
+def batchnorm_plan(op, rows, F, scratch_floats=1 << 40, flags=()):
+    """avsr_batchnorm_plan: the launch geometry one normalisation call would take, as a dict of the fields of avsr_bn_plan, decided by the
+    host function the entry points launch by (no GPU needed).  op: a name of BN_PLAN_OPS; flags: names of BN_PLAN_FLAGS (what
+    avsr_batchnorm_bwd derives from its pointers).  A call the library would refuse is reported in "err", not raised."""
+    from ._lib import BnPlan
+    bits = flags if isinstance(flags, int) else sum(BN_PLAN_FLAGS[f] for f in set(flags))
+    out = BnPlan()
+    rc = _L().avsr_batchnorm_plan(BN_PLAN_OPS[op] if isinstance(op, str) else int(op), int(rows), int(F), int(scratch_floats), bits, C.byref(out))
+    assert rc == out.err
+    return {f: getattr(out, f) for f, _ in BnPlan._fields_ if f != "pad_"}
+
+
 def im2col(x, col, N, H, W, Cc, kh, kw, stride, pad_t, pad_l, Ho, Wo):
     check(_L().avsr_im2col(fptr(x), fptr(col), N, H, W, Cc, kh, kw, stride, pad_t, pad_l, Ho, Wo, _s()), "avsr_im2col")
 

@@ -796,8 +796,9 @@ int avsr_colsum(const avsr_mat* a, const avsr_mat* b, int32_t rows, int32_t F, f
 /* tf.layers.batch_normalization(axis=-1, momentum=.99, eps=1e-3) over `rows` = B*T rows incl. padding
  * (avsr/encoder.py:44-50).  training=1: batch statistics + moving-average update; 0: moving statistics.
  * The input is rank 3, so TF 1.13 drops `fused=True` and the moving variance takes the BIASED batch variance.
- * moving_mean / moving_var may be NULL in training (no update: seq2seq.py:241-250 runs UPDATE_OPS only under
- * batch_normalisation=True). */
+ * moving_mean / moving_var may be NULL in training, both of them (no update: seq2seq.py:241-250 runs UPDATE_OPS only under
+ * batch_normalisation=True); one without the other is AVSR_ERR_ARG at every door that updates them (avsr_batchnorm_fwd[_ex],
+ * avsr_batchnorm_sync_apply, avsr_bn_finalize[_f64], avsr_conv3d_bn_finalize). */
 int avsr_batchnorm_fwd(const float* x, float* y, int32_t rows, int32_t F, const float* gamma, const float* beta,
                        float* moving_mean, float* moving_var, float* save_mean, float* save_invstd, int32_t training,
                        float* scratch, int64_t scratch_floats, void* stream);
@@ -818,8 +819,8 @@ int avsr_batchnorm_sync_sum(const float* x, int32_t rows, int32_t F, float* sum_
 int avsr_batchnorm_sync_sqsum(const float* x, int32_t rows, int32_t F, const float* sum_global, const float* total_rows,
                               float* mean_out, float* sq_out, float* scratch, int64_t scratch_floats, void* stream);
 /* Data-parallel step, ONE small collective (the loss normalisers and the sync-batch-norm statistics fused):
- *   avsr_batchnorm_sync_moments: out64[0..F) = sum x, out64[F..2F) = sum x^2 over this rank's rows, fp64 (scratch 8-byte aligned,
- *     >= 4*F*min(1024, ceil(rows/64)) floats); the caller packs them with its row count and the two loss normalisers into one fp64
+ *   avsr_batchnorm_sync_moments: out64[0..F) = sum x, out64[F..2F) = sum x^2 over this rank's rows, fp64 (scratch 8-byte aligned; fp64
+ *     partial rows of min(1024, ceil(rows/64)) blocks, 4*F floats each, the block count halved until they fit: at least 4*F floats); the caller packs them with its row count and the two loss normalisers into one fp64
  *     buffer and all-reduces that (sum);
  *   avsr_dp_sync_unpack: the reduced buffer -> dp_norm[0..1] and per stream mean / centred squares (sum x^2 - rows*mean^2, fp64) /
  *     rows as the float32 operands avsr_batchnorm_sync_apply and the loss kernels read.  encoder.py:44-50 statistics over the GLOBAL
@@ -833,10 +834,38 @@ int avsr_batchnorm_sync_apply(const float* x, float* y, int32_t rows, int32_t F,
 /* Gradient of batch normalisation with training statistics (tf.gradients through fused batch norm), optionally through
  * the ReLU after it: dy' = dy * [gamma*xhat + beta > 0];  dbeta = sum dy';  dgamma = sum dy'*xhat;
  * dx = gamma*invstd*(dy' - (sum dy' + xhat*sum dy'*xhat)/rows), written as dx = that + dx_beta*dx.  dx / dgamma / dbeta may
- * be NULL.  scratch >= (rows/64 + 1) * max(1, 256/F) * 2F + 2F floats. */
+ * be NULL.  scratch: partial rows [blocks][2F] and the sums [2F] behind them; blocks = ceil(rows / 64), at most 2048 (the float4 kernels:
+ * ceil(rows*F / 1024), at most 1024), fewer when the scratch holds fewer: any scratch of at least one partial row and the sums, 4F floats,
+ * works, and one float less is AVSR_ERR_ARG.  The float4 kernels run when rows >= 4096, F divides 1024 and every operand is 16-byte
+ * aligned; the sums are written straight to dgamma / dbeta when both are given and 16-byte aligned, else through the scratch. */
 int avsr_batchnorm_bwd(const float* x, const float* dy, const float* gamma, const float* beta, const float* mean,
                        const float* invstd, float* dx, float* dgamma, float* dbeta, int32_t rows, int32_t F, int32_t relu,
                        float dx_beta, float* scratch, int64_t scratch_floats, void* stream);
+/* Read-only plan query of the normalisations whose launch geometry depends on their arguments: decided by the same host function the
+ * entry points launch by -- nothing is dereferenced or launched, no HIP call is made (runs without a GPU).
+ *   op: AVSR_BN_PLAN_FWD avsr_batchnorm_fwd(_ex), _BWD avsr_batchnorm_bwd, _SYNC_SUM / _SYNC_SQSUM / _SYNC_MOMENTS the avsr_batchnorm_sync_*
+ *       entries, _BWD_STAGE1 avsr_bn_bwd_stage1 and _BWD_APPLY avsr_bn_bwd_apply (rows and F = C of their maps; no scratch).
+ *   flags (avsr_batchnorm_bwd only): what the call derives from its pointers -- _ALIGNED: x, dy, dx (when given), gamma, beta, mean, invstd
+ *       and scratch all 16-byte aligned; _DIRECT: dgamma and dbeta both given and 16-byte aligned; _DX: dx given.
+ *   out: blocks = workgroups of the partial-sum launch(es) (= partial rows; stage 1: *nparts), rows_per_block (0 for the float4 kernels,
+ *       which stride the flat map), G = row sub-groups of a block (256 / F below 256 columns, else 1; stage 1: its row lanes
+ *       256 / (C/4); 0 for avsr_bn_bwd_apply), vec = the float4 kernels, direct = the sums go straight to dgamma / dbeta, apply_grid =
+ *       workgroups of the pass that writes y / dx (0: none), err = the AVSR_* code the call would return on these arguments.
+ * Returns err. */
+#define AVSR_BN_PLAN_FWD 0
+#define AVSR_BN_PLAN_BWD 1
+#define AVSR_BN_PLAN_SYNC_SUM 2
+#define AVSR_BN_PLAN_SYNC_SQSUM 3
+#define AVSR_BN_PLAN_SYNC_MOMENTS 4
+#define AVSR_BN_PLAN_BWD_STAGE1 5
+#define AVSR_BN_PLAN_BWD_APPLY 6
+#define AVSR_BN_PLAN_ALIGNED 1
+#define AVSR_BN_PLAN_DIRECT 2
+#define AVSR_BN_PLAN_DX 4
+typedef struct avsr_bn_plan {
+  int32_t blocks, rows_per_block, G, vec, direct, apply_grid, err, pad_;
+} avsr_bn_plan;
+int avsr_batchnorm_plan(int32_t op, int64_t rows, int32_t F, int64_t scratch_floats, int32_t flags, avsr_bn_plan* out);
 
 /* ---- lip-crop CNN front-end (avsr/video.py:143-195 resnet_cnn): convolutions are im2col + avsr_gemm ----
  * im2col over NHWC maps with TF "SAME"/"VALID" geometry given explicitly: col[(n,ho,wo)][(i,j,c)] =
