@@ -218,6 +218,16 @@ class CtcPrefixNgram(C.Structure):
                [(n, C.c_void_p) for n in ("bow", "backoff", "arc_begin", "sym", "logp", "next", "s_lm", "lm_steps", "lm_logp")]
 
 
+class CtcPrefixWordNgram(C.Structure):
+    """avsr_ctc_prefix_word_ngram: a word automaton (CtcPrefixNgram's six tables over word ids) and the lexicon trie over its spellings
+    (csrc/ctc_prefix_word_ngram.hip)."""
+    _fields_ = [(n, C.c_int32) for n in ("n_nodes", "n_arcs", "Vw", "start", "eos_w", "unk_id", "n_trie_nodes", "n_trie_arcs", "V",
+                                         "space_id", "go_id", "eos_id")] + \
+               [("weight", C.c_float), ("bonus", C.c_float), ("oov", C.c_float), ("pad_", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("bow", "backoff", "arc_begin", "sym", "logp", "next", "t_begin", "t_sym", "t_next", "t_word",
+                                          "s_lm", "lm_steps", "lm_logp")]
+
+
 class BeamNgram(C.Structure):
     """avsr_beam_ngram: the automaton of CtcPrefixNgram as beam search's fused model (csrc/beam_ngram.hip)."""
     _fields_ = [(n, C.c_int32) for n in ("n_nodes", "n_arcs", "V", "start", "n_rows")] + [("lm_weight", C.c_float)] + \
@@ -246,7 +256,8 @@ _STRUCTS = {"avsr_dec_layer": DecLayer, "avsr_mat": Mat, "avsr_gemm_desc": GemmD
             "avsr_conv_desc": ConvDesc, "avsr_conv_launch": ConvLaunch, "avsr_bn_plan": BnPlan, "avsr_conv3d_desc": Conv3dDesc, "avsr_logmel_args": LogmelArgs, "avsr_spec_augment_args": SpecAugmentArgs, "avsr_video_augment_args": VideoAugmentArgs, "avsr_ctc_args": CtcArgs, "avsr_attn_mech": AttnMech, "avsr_attn_rnn": AttnRnn, "avsr_transpose_job": TransposeJob,
             "avsr_attn_rnn_launch": AttnRnnLaunch,
             "avsr_colsum_job": ColsumJob, "avsr_beam_lm": BeamLm, "avsr_beam_ctc": BeamCtc, "avsr_ctc_prefix_args": CtcPrefixArgs,
-            "avsr_ctc_prefix_lm": CtcPrefixLm, "avsr_ctc_prefix_ngram": CtcPrefixNgram, "avsr_beam_ngram": BeamNgram,
+            "avsr_ctc_prefix_lm": CtcPrefixLm, "avsr_ctc_prefix_ngram": CtcPrefixNgram, "avsr_ctc_prefix_word_ngram": CtcPrefixWordNgram,
+            "avsr_beam_ngram": BeamNgram,
             "avsr_ctc_align_args": CtcAlignArgs}
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -304,6 +315,8 @@ _SIGS = {
     "avsr_ctc_prefix_search_lm": [C.POINTER(CtcPrefixArgs), C.POINTER(CtcPrefixLm), _vp],
     "avsr_ctc_prefix_ngram_supported": [_i32, _i32, _i32, _i32, _i32],
     "avsr_ctc_prefix_search_ngram": [C.POINTER(CtcPrefixArgs), C.POINTER(CtcPrefixNgram), _vp],
+    "avsr_ctc_prefix_word_ngram_supported": [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32],
+    "avsr_ctc_prefix_search_word_ngram": [C.POINTER(CtcPrefixArgs), C.POINTER(CtcPrefixWordNgram), _vp],
     "avsr_ctc_align_supported": [_i32, _i32],
     "avsr_ctc_align": [C.POINTER(CtcAlignArgs), _vp],
     "avsr_seq_logprob": [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp],

@@ -45,6 +45,13 @@ of up to 16).  `lm_checkpoint` itself stays a 'beam_search' option.
 `ctc_ngram_lm` (the path of an ARPA file over the units: <s> = GO, </s> = EOS, <space> = ' ', every other token a unit's string) fuses a
 back-off n-gram into the same search instead, with the same two weights (ngram.py, csrc/ctc_prefix_ngram.hip): a table walk per kept
 extension, no weight-matrix product.  It is refused together with `ctc_lm_checkpoint` and under any other `decoding_algorithm`.
+`ctc_word_ngram_lm` (the path of an ARPA file over WORDS: <s>, </s>, optionally <unk>, every other token a word spelled by its own
+characters) fuses a word-level back-off n-gram into the same search of a model over single-character units, again with the same two
+weights: a trie over the spellings follows the word being written, and the word model is consulted when a space or the end closes it
+(ngram.py compile_word_tables, csrc/ctc_prefix_word_ngram.hip; the rule is INTEGRATION.md section 8).  `ctc_word_oov_score` (-10.0,
+natural log: a conventional value, not a tuned one) is paid once by a word that leaves the lexicon.  Refused together with
+`ctc_lm_checkpoint` or `ctc_ngram_lm`, under any other `decoding_algorithm`, with `beam_width` > 16, and for unit files without ' ' or
+with multi-character units.  Nothing was trained with it: no error rate is claimed.
 `decoding_algorithm='attention_rescoring'` (a `use_ctc` model; not in the reference) is the two-pass decode: that search's n-best, every
 hypothesis scored by the attention decoder teacher-forced, the best of log p_att + ctc_decode_weight * log p_ctc kept -- no step-by-step
 decode (csrc/rescore.hip).  No language-model term, no length normalisation.
@@ -266,6 +273,30 @@ class AVSR(object):
                 raise ValueError("ctc_ngram_lm: avsr_ctc_prefix_ngram_supported covers automata of up to %d nodes and %d arcs (got %d, %d)"
                                  % (CTC_PREFIX_NGRAM_MAX_NODES, CTC_PREFIX_NGRAM_MAX_ARCS, self._ctc_ngram["n_nodes"],
                                     self._ctc_ngram["n_arcs"]))
+
+        # word-level n-gram behind a lexicon trie, fused into the CTC prefix search (csrc/ctc_prefix_word_ngram.hip): parsed, compiled and
+        # refused on the host, here; without the keyword nothing is read
+        self._ctc_word_ngram = None
+        ctc_word_ngram_lm = kwargs.get('ctc_word_ngram_lm')
+        if ctc_word_ngram_lm is not None:
+            from . import ngram as _ngram
+            from ._lib import CTC_PREFIX_LM_MAX_W, CTC_PREFIX_NGRAM_MAX_ARCS, CTC_PREFIX_NGRAM_MAX_NODES
+            if decoding_algorithm != 'ctc_prefix_beam_search':
+                raise ValueError("ctc_word_ngram_lm needs decoding_algorithm='ctc_prefix_beam_search': the word model is fused into the "
+                                 "CTC head's own search (no other decoding algorithm takes a word-level model)")
+            if ctc_lm_checkpoint is not None or ctc_ngram_lm is not None:
+                raise ValueError("ctc_word_ngram_lm and %s are two language models for one search: give one of them"
+                                 % ("ctc_lm_checkpoint" if ctc_lm_checkpoint is not None else "ctc_ngram_lm"))
+            if beam_width > CTC_PREFIX_LM_MAX_W:
+                raise ValueError("ctc_word_ngram_lm: avsr_ctc_prefix_word_ngram_supported covers beam widths of up to %d (got beam_width "
+                                 "%d)" % (CTC_PREFIX_LM_MAX_W, beam_width))
+            # ValueError: not an ARPA file, units that cannot spell (no ' ', multi-character units), no spellable word, a bad oov score
+            g = self._ctc_word_ngram = _ngram.load_word_tables(ctc_word_ngram_lm, self._unit_dict, kwargs.get('ctc_word_oov_score', -10.0))
+            if max(g["n_nodes"], g["n_trie_nodes"]) > CTC_PREFIX_NGRAM_MAX_NODES or max(g["n_arcs"], g["n_trie_arcs"]) > CTC_PREFIX_NGRAM_MAX_ARCS:
+                raise ValueError("ctc_word_ngram_lm: avsr_ctc_prefix_word_ngram_supported covers word automata and lexicon tries of up to "
+                                 "%d nodes and %d arcs each (got %d, %d and %d, %d)"
+                                 % (CTC_PREFIX_NGRAM_MAX_NODES, CTC_PREFIX_NGRAM_MAX_ARCS, g["n_nodes"], g["n_arcs"], g["n_trie_nodes"],
+                                    g["n_trie_arcs"]))
 
         # joint CTC / attention scoring in beam search: an evaluate-time weight, held like _lm_weight; 0 = off, nothing new is launched
         self._ctc_decode_weight = float(kwargs.get('ctc_decode_weight', 0.0))
@@ -590,7 +621,8 @@ class AVSR(object):
         elif self._decoding_algorithm == 'ctc_prefix_beam_search':     # the head's own search: the attention decoder never runs
             ids = self._model.ctc_prefix_beam_search(batch, beam_width=self._beam_width, max_steps=self._cfg.max_label_length,
                                                      lm=self._ctc_lm, lm_weight=self._ctc_lm_weight, length_bonus=self._ctc_lm_bonus,
-                                                     ngram=self._ctc_ngram)
+                                                     ngram=self._ctc_ngram,
+                                                     **({} if self._ctc_word_ngram is None else dict(word_ngram=self._ctc_word_ngram)))
         else:
             ids = self._model.greedy_decode(batch, max_steps=self._cfg.max_label_length)
         if not isinstance(ids, list):

@@ -1,9 +1,10 @@
 // The CTC prefix beam search, written ONCE: the frame-synchronous search on the head's logits that sums over
 // alignments, with no decoder step, optionally with a language-model term fused into the frame loop.  fp32, gfx950, no atomics: two
-// launches on the same inputs are bit-identical.  Three kernels instantiate cp_search:
+// launches on the same inputs are bit-identical.  Four kernels instantiate cp_search:
 //   csrc/ctc_prefix.hip         no model (cp_no_model): the plain search, beam widths up to 64
 //   csrc/ctc_prefix_lm.hip      an avsr.LM LSTM; per-row state (c, h) in a global workspace
 //   csrc/ctc_prefix_ngram.hip   a back-off n-gram automaton; per-row state one node id in LDS (the `extra` words below)
+//   csrc/ctc_prefix_word_ngram.hip   a word-level n-gram behind a lexicon trie; per-row state five words in LDS
 // The no-model case is a compile-time policy: that kernel holds no term, no pool rows, no phase 6 and no re-sort.
 //
 // ONE launch per batch, one 256-thread workgroup per utterance, the whole frame loop inside: the dependent chain is T_b frames long and

@@ -193,12 +193,12 @@ class EvalMixin:
 
     NGRAM_TABLES = ("bow", "backoff", "arc_begin", "sym", "logp", "next")
 
-    def _ngram_device_tables(self, ngram):
+    def _ngram_device_tables(self, ngram, names=NGRAM_TABLES):
         """The six arrays of the automaton `ngram` (ngram.compile_tables) on the device: uploaded once per model object and kept with the
         dict they came from, for every search that fuses it (the CTC prefix search, beam search)."""
         cache = self.__dict__.setdefault("_ngram_tables", {})
         if id(ngram) not in cache:
-            cache[id(ngram)] = (ngram, {k: torch.as_tensor(np.ascontiguousarray(ngram[k])).to(self.dev) for k in self.NGRAM_TABLES})
+            cache[id(ngram)] = (ngram, {k: torch.as_tensor(np.ascontiguousarray(ngram[k])).to(self.dev) for k in names})
         return cache[id(ngram)][1]
 
     @staticmethod

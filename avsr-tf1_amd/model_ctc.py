@@ -1,11 +1,11 @@
 """CTC half of the engine (mixin of model.Seq2SeqModel): the CTC head on the encoder memory, its loss term in the train graph, and the
 decodes that need the head alone -- best path, forced alignment, prefix beam search (plain, with a fused avsr.LM network, with a fused
-back-off n-gram).  Kernels: csrc/ctc.hip, csrc/ctc_align.hip, csrc/ctc_prefix*.hip; the rules are INTEGRATION.md section 8."""
+back-off n-gram over the units or over words behind a lexicon trie).  Kernels: csrc/ctc.hip, csrc/ctc_align.hip, csrc/ctc_prefix*.hip; the rules are INTEGRATION.md section 8."""
 import numpy as np
 import torch
 from . import ops
 from ._lib import (CTC_ALIGN_MAX_L, CTC_PREFIX_LM_MAX_W, CTC_PREFIX_MAX_L, CTC_PREFIX_MAX_V, CTC_PREFIX_MAX_W, MAX_LM_LAYERS, CtcPrefixLm,
-                   CtcPrefixNgram)
+                   CtcPrefixNgram, CtcPrefixWordNgram)
 
 
 class CtcMixin:
@@ -115,7 +115,7 @@ class CtcMixin:
         return out
 
     def ctc_prefix_beam_search(self, batch, beam_width=10, max_steps=None, nbest=False, lm=None, lm_weight=0.3, length_bonus=0.0,
-                               ngram=None):
+                               ngram=None, *, word_ngram=None):
         """use_ctc: CTC prefix beam search on the head alone (avsr_ctc_prefix_search, csrc/ctc_prefix.hip; the search of all three forms
         is csrc/ctc_prefix_search.h, the rule is INTEGRATION.md section 8) -- encoders in evaluation mode, the head, ONE launch for the batch; no decoder step.  max_steps bounds the label
         sequences (default: max_label_length).  One id list per utterance, the beam's best; nbest=True: per utterance the whole final
@@ -126,10 +126,18 @@ class CtcMixin:
         (ids, final, s_lm) triples, s_lm = log p_lm(labels, EOS).  Without lm the plain kernel runs and nothing new is allocated.
         ngram: instead of lm, the tables of a back-off n-gram (ngram.compile_tables / ngram.load_tables) -- the same rule and the same
         outputs with lam read from the automaton (avsr_ctc_prefix_search_ngram, csrc/ctc_prefix_ngram.hip); the tables are uploaded
-        once per model object.  lm and ngram together are refused."""
-        return self._redo_if_flagged(self._ctc_prefix_beam_search, batch, beam_width, max_steps, nbest, lm, lm_weight, length_bonus, ngram)
+        once per model object.  lm and ngram together are refused.
+        word_ngram (keyword only): instead of either, the tables of a WORD-level back-off n-gram behind a lexicon trie
+        (ngram.compile_word_tables / ngram.load_word_tables) for a model over single-character units -- the same rule and outputs with
+        lam formed from the trie while a word is written and from the word automaton when a space or EOS closes it
+        (avsr_ctc_prefix_search_word_ngram, csrc/ctc_prefix_word_ngram.hip); uploaded once per model object.  Refused together with
+        lm or ngram."""
+        kw = {} if word_ngram is None else dict(word_ngram=word_ngram)
+        return self._redo_if_flagged(self._ctc_prefix_beam_search, batch, beam_width, max_steps, nbest, lm, lm_weight, length_bonus, ngram,
+                                     **kw)
 
-    def _ctc_prefix_beam_search(self, batch, beam_width, max_steps, nbest, lm=None, lm_weight=0.3, length_bonus=0.0, ngram=None):
+    def _ctc_prefix_beam_search(self, batch, beam_width, max_steps, nbest, lm=None, lm_weight=0.3, length_bonus=0.0, ngram=None,
+                                word_ngram=None):
         cfg = self.cfg
         if not cfg.use_ctc:
             raise ValueError("ctc_prefix_beam_search needs a model built with use_ctc=True")
@@ -138,9 +146,12 @@ class CtcMixin:
         self._require_ctc_prefix_shape("ctc_prefix_beam_search", V, W, Lm)
         if lm is not None and ngram is not None:
             raise ValueError("ctc_prefix_beam_search takes one language model: lm (an avsr.LM network) or ngram (back-off tables), not both")
+        if word_ngram is not None and (lm is not None or ngram is not None):
+            raise ValueError("ctc_prefix_beam_search takes one language model: word_ngram (word-level tables behind a lexicon) cannot "
+                             "be combined with lm or ngram")
         if lm is not None:
             self._check_lm(lm)
-        if lm is not None or ngram is not None:
+        if lm is not None or ngram is not None or word_ngram is not None:
             lm_weight, length_bonus = self._require_weight("ctc_prefix_beam_search", "lm_weight", float(lm_weight)), float(length_bonus)
             if length_bonus != length_bonus or abs(length_bonus) == float("inf"):
                 raise ValueError("ctc_prefix_beam_search: length_bonus must be finite (got %r)" % (length_bonus,))
@@ -154,6 +165,18 @@ class CtcMixin:
                                  "arcs (got beam width %d, %d symbols, %d labels, %d nodes, %d arcs)"
                                  % (CTC_PREFIX_LM_MAX_W, CTC_PREFIX_MAX_V, CTC_PREFIX_MAX_L, 1 << 24, 1 << 26, W, V, Lm,
                                     ngram["n_nodes"], ngram["n_arcs"]))
+        if word_ngram is not None:
+            g = word_ngram
+            if (g["V"], g["go_id"], g["eos_id"]) != (V, cfg.go_id, cfg.eos_id):
+                raise ValueError("ctc_prefix_beam_search: the word n-gram tables were compiled for V = %d, GO = %d, EOS = %d; the model has "
+                                 "%d, %d, %d" % (g["V"], g["go_id"], g["eos_id"], V, cfg.go_id, cfg.eos_id))
+            if not ops.ctc_prefix_word_ngram_supported(V, W, Lm, g["n_nodes"], g["n_arcs"], g["Vw"], g["n_trie_nodes"], g["n_trie_arcs"]):
+                raise ValueError("ctc_prefix_beam_search: with a word n-gram avsr_ctc_prefix_search_word_ngram covers beam widths of up to "
+                                 "%d (vocabularies of up to %d symbols, label sequences of up to %d) and word automata and lexicon tries "
+                                 "of up to %d nodes and %d arcs each (got beam width %d, %d symbols, %d labels, %d nodes, %d arcs, %d "
+                                 "trie nodes, %d trie arcs)"
+                                 % (CTC_PREFIX_LM_MAX_W, CTC_PREFIX_MAX_V, CTC_PREFIX_MAX_L, 1 << 24, 1 << 26, W, V, Lm, g["n_nodes"],
+                                    g["n_arcs"], g["n_trie_nodes"], g["n_trie_arcs"]))
         if lm is not None:
             lc = lm.cfg
             nl, H, El = len(lc.decoder_units), lc.decoder_units[0], lc.embedding_size
@@ -166,7 +189,9 @@ class CtcMixin:
         E, Cc = self._ctc_head(ws)
         ids, lens, score = self._ctc_nbest_buffers(E, B, W, Lm)
         s_lm = None                                                # (device) with a model: the third column of the n-best
-        if ngram is not None:
+        if word_ngram is not None:
+            s_lm = self._ctc_prefix_word_ngram_launch(E, Cc, B, V, W, Lm, ids, lens, score, word_ngram, lm_weight, length_bonus)
+        elif ngram is not None:
             s_lm = self._ctc_prefix_ngram_launch(E, Cc, B, V, W, Lm, ids, lens, score, ngram, lm_weight, length_bonus)
         elif lm is not None:
             s_lm = self._ctc_prefix_lm_launch(E, Cc, B, V, W, Lm, ids, lens, score, lm, lm_weight, length_bonus)
@@ -234,5 +259,24 @@ class CtcMixin:
             setattr(g, k, ops.fptr(tb[k]))
         g.s_lm, g.lm_steps = ops.fptr(buf["s_lm"]), ops.fptr(buf["steps"])
         ops.ctc_prefix_search_ngram(E["ctc_z"], Cc, E["len"], B, E["T"], V, W, Lm, ids, lens, score, g)
+        self._last_ctc_lm_steps = buf["steps"]
+        return buf["s_lm"]
+
+    WORD_NGRAM_TABLES = ("bow", "backoff", "arc_begin", "sym", "logp", "next", "t_begin", "t_sym", "t_next", "t_word")
+
+    def _ctc_prefix_word_ngram_launch(self, E, Cc, B, V, W, Lm, ids, lens, score, tables, lm_weight, length_bonus):
+        """avsr_ctc_prefix_search_word_ngram over the word automaton and lexicon trie `tables` (ngram.compile_word_tables): the ten
+        arrays go to the device once per model object (_ngram_device_tables); s_lm and lm_steps are cached next to the
+        ("ctc_prefix", W, Lm) buffers.  Returns s_lm [B, W] (device)."""
+        tb = self._ngram_device_tables(tables, self.WORD_NGRAM_TABLES)
+        buf = self._ctc_prefix_model_outputs(E, ("ctc_prefix_word_ngram", W, Lm), B, W)
+        g = CtcPrefixWordNgram()
+        for k in ("n_nodes", "n_arcs", "Vw", "start", "eos_w", "unk_id", "n_trie_nodes", "n_trie_arcs", "space_id", "go_id", "eos_id"):
+            setattr(g, k, int(tables[k]))
+        g.V, g.weight, g.bonus, g.oov = V, lm_weight, length_bonus, float(tables["oov_score"])
+        for k in self.WORD_NGRAM_TABLES:
+            setattr(g, k, ops.fptr(tb[k]))
+        g.s_lm, g.lm_steps = ops.fptr(buf["s_lm"]), ops.fptr(buf["steps"])
+        ops.ctc_prefix_search_word_ngram(E["ctc_z"], Cc, E["len"], B, E["T"], V, W, Lm, ids, lens, score, g)
         self._last_ctc_lm_steps = buf["steps"]
         return buf["s_lm"]

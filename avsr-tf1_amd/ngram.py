@@ -10,7 +10,11 @@ The model of order N over the classes 0 .. V-1 (MASK = 0, the units, EOS = V-2, 
 in float64 where they are used and rounded to float32 once, in `compile_tables`.
 
 Tokens: <s> is GO, </s> is EOS, <space> is the unit ' ', every other token is the unit's own string (multi-character units work).
-Entries that contain <unk> are DROPPED and their probability mass is not given to anything else: the recogniser has no unknown unit."""
+Entries that contain <unk> are DROPPED and their probability mass is not given to anything else: the recogniser has no unknown unit.
+
+The second half of the file is the WORD-level form for models over single-character units (csrc/ctc_prefix_word_ngram.hip): ARPA files
+whose tokens are words (`read_word_arpa`, `write_word_arpa`; <unk> is kept there), `compile_word_tables` -- the same automaton over word
+ids plus a trie over the words' spellings -- and `word_step` / `word_lam`, the kernel's step restated in numpy float32."""
 import math
 
 import numpy as np
@@ -45,10 +49,10 @@ def _tokens(unit_dict):
     return out
 
 
-def read_arpa(path, unit_dict):
-    """Parse an ARPA file into an NGramModel over unit_dict's classes (id -> symbol, io_utils.create_unit_dict).  ValueError for a file
-    without a \\1-grams: section, a malformed line, a count that contradicts the \\data\\ header, or a token that is not a unit."""
-    ids = {t: i for i, t in _tokens(unit_dict).items()}
+def _parse_arpa(path, gram_of):
+    """The ARPA text of `path` as (order, [{gram_of(tokens): (log10 p, log10 bow)} per order]); gram_of(tokens, where) gives an entry's
+    key, None to drop the entry, or raises ValueError for a token it does not know (where = "path:line").  ValueError for a file
+    without a \\1-grams: section, a malformed line or a count that contradicts the \\data\\ header."""
     counts, grams, k, seen = {}, {}, 0, {}
     in_data = False
     with open(path, "r", encoding="utf-8") as f:
@@ -76,7 +80,7 @@ def read_arpa(path, unit_dict):
                     counts[int(a)] = int(b)
                 continue
             if k == 0:
-                continue                                   # (text before \data\)
+                continue                                   # (text before \\data\\)
             f_ = line.split()
             if len(f_) not in (k + 1, k + 2):
                 raise ValueError("%s:%d: a %d-gram line has %d or %d fields: %r" % (path, ln, k, k + 1, k + 2, line))
@@ -85,13 +89,9 @@ def read_arpa(path, unit_dict):
             except ValueError:
                 raise ValueError("%s:%d: not a number in %r" % (path, ln, line))
             seen[k] += 1
-            toks = f_[1:k + 1]
-            if "<unk>" in toks or "<UNK>" in toks:
-                continue                                   # dropped; the lost mass is not renormalised
-            for t in toks:
-                if t not in ids:
-                    raise ValueError("%s:%d: token %r is not a unit of the unit file" % (path, ln, t))
-            grams[k][tuple(ids[t] for t in toks)] = (lp, bow)
+            gram = gram_of(f_[1:k + 1], "%s:%d" % (path, ln))
+            if gram is not None:
+                grams[k][gram] = (lp, bow)
     if 1 not in grams:
         raise ValueError("%s: no \\1-grams: section -- not an ARPA language model" % path)
     order = max(grams)
@@ -100,12 +100,30 @@ def read_arpa(path, unit_dict):
             raise ValueError("%s: no \\%d-grams: section below the \\%d-grams: one" % (path, j, order))
         if j in counts and counts[j] != seen[j]:
             raise ValueError("%s: the header announces %d %d-grams, the section holds %d" % (path, counts[j], j, seen[j]))
-    return NGramModel(order, [grams[j] for j in range(1, order + 1)])
+    return order, [grams[j] for j in range(1, order + 1)]
+
+
+def read_arpa(path, unit_dict):
+    """Parse an ARPA file into an NGramModel over unit_dict's classes (id -> symbol, io_utils.create_unit_dict).  ValueError for a file
+    without a \\1-grams: section, a malformed line, a count that contradicts the \\data\\ header, or a token that is not a unit."""
+    ids = {t: i for i, t in _tokens(unit_dict).items()}
+
+    def gram_of(toks, where):
+        if "<unk>" in toks or "<UNK>" in toks:
+            return None                                    # dropped; the lost mass is not renormalised
+        for t in toks:
+            if t not in ids:
+                raise ValueError("%s: token %r is not a unit of the unit file" % (where, t))
+        return tuple(ids[t] for t in toks)
+    return NGramModel(*_parse_arpa(path, gram_of))
 
 
 def write_arpa(path, model, unit_dict):
     """Write the model with repr()'s digits (read_arpa gives the identical model back); orders below N carry the back-off column."""
-    tok = _tokens(unit_dict)
+    _write_arpa(path, model, _tokens(unit_dict))
+
+
+def _write_arpa(path, model, tok):
     with open(path, "w", encoding="utf-8") as f:
         f.write("\\data\\\n")
         for k, g in enumerate(model.grams, 1):
@@ -260,6 +278,163 @@ def load_tables(path, unit_dict):
     """read_arpa + compile_tables over unit_dict's classes."""
     rev = {s: i for i, s in unit_dict.items()}
     return compile_tables(read_arpa(path, unit_dict), len(unit_dict) - 1, rev["GO"], rev["EOS"])
+
+
+# ---- word-level models behind a lexicon trie (csrc/ctc_prefix_word_ngram.hip; the rule is INTEGRATION.md section 8) ----
+# The search runs over characters; the state of a label sequence is (h, p): h the word automaton's node for the words closed so far,
+# p the trie node of the letters since the last space (0 = the trie's root, WORD_OOV once they have left every spelling).
+
+WORD_BOS, WORD_EOS, WORD_UNK = "<s>", "</s>", ("<unk>", "<UNK>")
+WORD_OOV = -1
+
+
+def read_word_arpa(path):
+    """Parse an ARPA file whose tokens are WORDS into (NGramModel over word ids, vocabulary).  vocabulary[id] is the token: <s> is 0,
+    </s> is 1, every other token of the file follows in sorted order -- <unk> / <UNK>, which is KEPT here, among them.  read_arpa's
+    file errors."""
+    order, grams = _parse_arpa(path, lambda toks, where: tuple(toks))
+    vocabulary = [WORD_BOS, WORD_EOS] + sorted({t for g in grams for gram in g for t in gram} - {WORD_BOS, WORD_EOS})
+    ids = {t: i for i, t in enumerate(vocabulary)}
+    return NGramModel(order, [{tuple(ids[t] for t in gram): v for gram, v in g.items()} for g in grams]), vocabulary
+
+
+def write_word_arpa(path, model, vocabulary):
+    """write_arpa for a model over word ids; read_word_arpa gives the identical (model, vocabulary) back when the vocabulary is in its
+    order (<s>, </s>, the rest sorted) and every word occurs in the model."""
+    _write_arpa(path, model, dict(enumerate(vocabulary)))
+
+
+def word_dict(vocabulary):
+    """The {id: name} dictionary `estimate` takes, for a vocabulary in read_word_arpa's order: <s> as GO, </s> as EOS, every other
+    word a real class (the names are tagged, so that no word reads as one of the dictionary's reserved names)."""
+    if list(vocabulary[:2]) != [WORD_BOS, WORD_EOS]:
+        raise ValueError("a word vocabulary starts with %s, %s (got %r)" % (WORD_BOS, WORD_EOS, list(vocabulary[:2])))
+    d = {i: "w:" + w for i, w in enumerate(vocabulary)}
+    d[0], d[1] = "GO", "EOS"
+    return d
+
+
+def compile_word_tables(model, vocabulary, unit_dict, oov_score=-10.0):
+    """The device tables of include/avsr_hip.h avsr_ctc_prefix_word_ngram as numpy arrays, for a word model (read_word_arpa) decoded
+    over the single-character units of unit_dict:
+        the word automaton   compile_tables(model, Vw, <s>, </s>) unchanged: order, start, n_nodes, n_arcs, bow, backoff, arc_begin, sym,
+                             logp, next, contexts -- with its classes under Vw, go_w, eos_w, and unk_id (-1 without <unk>)
+        the lexicon trie     CSR over the spellings: t_begin i32 [n_trie_nodes + 1], t_sym i32 [n_trie_arcs] (unit ids, sorted per node),
+                             t_next i32 [n_trie_arcs], t_word i32 [n_trie_nodes] (the word a node ends, or -1); node 0 is the root
+        the units            V, go_id, eos_id, space_id; oov_score (natural log, <= 0); n_unspellable
+    A word is spelled by its own characters.  One with a character that is no letter of the unit file (a letter: every unit but ' ')
+    stays in the model as context and is left out of the trie; so are <s>, </s> and <unk>.
+    ValueError: a unit file without ' ' or with a unit longer than one character, no spellable word, oov_score positive or not finite,
+    an order above MAX_ORDER."""
+    oov = float(oov_score)
+    if not oov <= 0.0 or oov == float("-inf"):
+        raise ValueError("the out-of-vocabulary score must be a finite number <= 0 (got %r)" % (oov_score,))
+    rev = {s: i for i, s in unit_dict.items()}
+    if " " not in rev:
+        raise ValueError("a word-level n-gram needs the unit ' ' in the unit file: a space closes a word")
+    letters = {}
+    for i, s in unit_dict.items():
+        if s in ("MASK", "END", "GO", "EOS", " "):
+            continue
+        if len(s) != 1:
+            raise ValueError("a word-level n-gram needs single-character units: words are spelled by their characters (unit %r; phoneme "
+                             "and viseme lists need a pronunciation lexicon, which is not built)" % (s,))
+        letters[s] = i
+    vocabulary = list(vocabulary)
+    idw = {w: i for i, w in enumerate(vocabulary)}
+    if len(idw) != len(vocabulary) or WORD_BOS not in idw or WORD_EOS not in idw:
+        raise ValueError("a word vocabulary holds %s, %s and every word once" % (WORD_BOS, WORD_EOS))
+    t = compile_tables(model, len(vocabulary), idw[WORD_BOS], idw[WORD_EOS])
+    t["Vw"], t["go_w"], t["eos_w"] = t.pop("V"), t.pop("go_id"), t.pop("eos_id")
+    t["unk_id"] = idw.get(WORD_UNK[0], idw.get(WORD_UNK[1], WORD_OOV))
+    children, ends, unspellable = [{}], [-1], 0
+    for wid, w in enumerate(vocabulary):
+        if w in (WORD_BOS, WORD_EOS) + WORD_UNK:
+            continue
+        if not w or any(ch not in letters for ch in w):
+            unspellable += 1
+            continue
+        n = 0
+        for ch in w:
+            if letters[ch] not in children[n]:
+                children[n][letters[ch]] = len(children)
+                children.append({})
+                ends.append(-1)
+            n = children[n][letters[ch]]
+        ends[n] = wid
+    if len(children) == 1:
+        raise ValueError("no word of the model can be spelled with the letters of the unit file (%d words)" % unspellable)
+    t_begin, t_sym, t_next = [0], [], []
+    for ch in children:
+        for c in sorted(ch):
+            t_sym.append(c)
+            t_next.append(ch[c])
+        t_begin.append(len(t_sym))
+    t.update(V=len(unit_dict) - 1, go_id=rev["GO"], eos_id=rev["EOS"], space_id=rev[" "], oov_score=oov, n_unspellable=unspellable,
+             n_trie_nodes=len(children), n_trie_arcs=len(t_sym), t_begin=np.asarray(t_begin, np.int32), t_sym=np.asarray(t_sym, np.int32),
+             t_next=np.asarray(t_next, np.int32), t_word=np.asarray(ends, np.int32))
+    return t
+
+
+def word_start(tables):
+    """The state of the empty label sequence."""
+    return int(tables["start"]), 0
+
+
+def _trie_child(t, p, c):
+    lo, hi = int(t["t_begin"][p]), int(t["t_begin"][p + 1])
+    a = lo + int(np.searchsorted(t["t_sym"][lo:hi], c))
+    return int(t["t_next"][a]) if a < hi and t["t_sym"][a] == c else WORD_OOV
+
+
+def _word_close(t, h, p):
+    """What a space costs at (h, p) and the automaton node it leaves, float32 in the kernel's order."""
+    if p == 0:
+        return np.float32(0.0), h
+    w = int(t["t_word"][p]) if p > 0 else -1
+    prefix = p > 0 and w < 0
+    if w < 0:
+        w = int(t["unk_id"])
+    if w >= 0:
+        v, arc = walk(t, h, w)
+        hc = int(t["next"][arc])
+    else:
+        v, hc = np.float32(0.0), 0
+    return (np.float32(np.float32(t["oov_score"]) + v) if prefix else v), hc
+
+
+def word_step(tables, state, c):
+    """The device step restated: the state of g.c from the state of g."""
+    t, (h, p), c = tables, state, int(c)
+    if c == t["space_id"]:
+        return (_word_close(t, h, p)[1], 0) if p != 0 else (h, p)
+    if c == t["eos_id"]:
+        return int(t["next"][walk(t, _word_close(t, h, p)[1], t["eos_w"])[1]]), 0
+    if c == t["go_id"] or c == 0:
+        return h, p
+    return h, (_trie_child(t, p, c) if p >= 0 else WORD_OOV)
+
+
+def word_lam(tables, state):
+    """The device row restated in numpy float32, additions in the kernel's order: lam(. | g) [V] at the state of g."""
+    t, (h, p) = tables, state
+    oov = np.float32(t["oov_score"])
+    row = np.zeros(t["V"], np.float32)
+    if p >= 0:
+        lo, hi = int(t["t_begin"][p]), int(t["t_begin"][p + 1])
+        row[:] = oov
+        row[t["t_sym"][lo:hi]] = 0.0
+    cl, hc = _word_close(t, h, p)
+    row[t["space_id"]] = cl
+    row[t["eos_id"]] = np.float32(cl + walk(t, hc, t["eos_w"])[0])
+    row[t["go_id"]] = row[0] = np.float32(FLOOR)
+    return row
+
+
+def load_word_tables(path, unit_dict, oov_score=-10.0):
+    """read_word_arpa + compile_word_tables over unit_dict's classes."""
+    model, vocabulary = read_word_arpa(path)
+    return compile_word_tables(model, vocabulary, unit_dict, oov_score)
 
 
 def label_sequences(unit_dict, label_record=None, text_dataset=None):

@@ -430,7 +430,7 @@ def ctc_prefix_search_supported(V, beam_width, L_max):
 
 
 def _ctc_prefix_args(z, ld, in_len, B, T, V, beam_width, L_max, ids, lens, score, trace):
-    """The avsr_ctc_prefix_args of the three searches below."""
+    """The avsr_ctc_prefix_args of the four searches below."""
     from ._lib import CtcPrefixArgs
     a = CtcPrefixArgs()
     a.B, a.T, a.V, a.beam_width, a.L_max, a.ld = int(B), int(T), int(V), int(beam_width), int(L_max), int(ld)
@@ -473,6 +473,19 @@ def ctc_prefix_search_ngram(z, ld, in_len, B, T, V, beam_width, L_max, ids, lens
     and the outputs s_lm [B, W], lm_steps [B] and, optionally, lm_logp [B, W, V] set).  score holds final."""
     a = _ctc_prefix_args(z, ld, in_len, B, T, V, beam_width, L_max, ids, lens, score, trace)
     check(_L().avsr_ctc_prefix_search_ngram(C.byref(a), C.byref(ng), _s()), "avsr_ctc_prefix_search_ngram")
+
+
+def ctc_prefix_word_ngram_supported(V, beam_width, L_max, n_nodes, n_arcs, Vw, n_trie_nodes, n_trie_arcs):
+    """Host-side: does avsr_ctc_prefix_search_word_ngram run this search shape with a word automaton and a trie of these sizes?"""
+    return bool(_L().avsr_ctc_prefix_word_ngram_supported(int(V), int(beam_width), int(L_max), int(n_nodes), int(n_arcs), int(Vw),
+                                                          int(n_trie_nodes), int(n_trie_arcs)))
+
+
+def ctc_prefix_search_word_ngram(z, ld, in_len, B, T, V, beam_width, L_max, ids, lens, score, wg, trace=None):
+    """avsr_ctc_prefix_search_word_ngram: ctc_prefix_search with the term of the word-level n-gram behind a lexicon trie wg (a
+    _lib.CtcPrefixWordNgram with its tables and the outputs s_lm [B, W], lm_steps [B] and, optionally, lm_logp [B, W, V] set)."""
+    a = _ctc_prefix_args(z, ld, in_len, B, T, V, beam_width, L_max, ids, lens, score, trace)
+    check(_L().avsr_ctc_prefix_search_word_ngram(C.byref(a), C.byref(wg), _s()), "avsr_ctc_prefix_search_word_ngram")
 
 
 def ctc_align_supported(V, L):

@@ -677,6 +677,54 @@ int avsr_ctc_prefix_ngram_supported(int32_t V, int32_t beam_width, int32_t L_max
 /* AVSR_ERR_ARG for a NULL / non-positive / inconsistent argument, AVSR_ERR_UNSUPPORTED outside the limits: both before any launch. */
 int avsr_ctc_prefix_search_ngram(const avsr_ctc_prefix_args* a, const avsr_ctc_prefix_ngram* ng, void* stream);
 
+/* The same fused search over CHARACTER units with a WORD-level back-off n-gram behind a lexicon trie (csrc/ctc_prefix_word_ngram.hip;
+ * the rule, with its table of cases, is INTEGRATION.md section 8): every word above about extensions, final, s_lm, lm_steps, lm_logp,
+ * the trace and weight == 0 holds; only lam(. | g) differs.  Units: space_id is the space, class 0 (MASK) and go_id are non-units,
+ * eos_id is EOS, every other class below V is a letter.  Two read-only tables (avsr-tf1_amd/ngram.py compile_word_tables writes them):
+ *   the word automaton   avsr_ctc_prefix_ngram's six tables over WORD ids 0 .. Vw-1 (the root holds Vw arcs), walked by the same
+ *                        csrc/ngram_walk.h; start = the node of (<s>), eos_w = the id of </s>, unk_id = the id of <unk> or -1
+ *   the lexicon trie     CSR over the vocabulary's spellings, node 0 the root: the children of node n are the arcs
+ *                        [t_begin[n], t_begin[n + 1]), t_sym (unit ids) sorted per node, t_next the child; t_word[n] = the word that
+ *                        ends at n, or -1
+ * State of a label sequence, a function of the labels alone: (h, p) = (the automaton node of the words closed so far, the trie node of
+ * the letters since the last space -- the root without any, the sink OOV once they have left every spelling).
+ *   letter c:   0 if p has the child c or p is OOV, else oov (paid once, on leaving the lexicon)
+ *   space:      0 at the root; walk(h, w) where p ends the word w; oov + U(h) at a proper prefix; U(h) at OOV --
+ *               U(h) = walk(h, <unk>), or 0 with h -> node 0 when the model has no <unk>
+ *   EOS:        (what the space costs) + walk(the node after that space, </s>)
+ *   MASK, GO:   the floor -99 ln 10
+ * fp32 additions in exactly this order, so the host restatement (ngram.py word_lam) gives the same bits.  Every node id, word id and
+ * arc range read from a table is clamped into its table; all loops are bounded.
+ * No workspace: the state and three cached scalars per pool row live in LDS.
+ * Limits: avsr_ctc_prefix_search_ngram's, with AVSR_CTC_PREFIX_NGRAM_MAX_NODES / _MAX_ARCS applied to the trie as well (1 <=
+ * n_trie_nodes, 1 <= n_trie_arcs); 2 <= Vw <= n_arcs, 0 <= eos_w < Vw, -1 <= unk_id < Vw; 0 <= space_id < V with space_id, go_id and
+ * eos_id distinct; oov finite and <= 0. */
+typedef struct avsr_ctc_prefix_word_ngram {
+  int32_t n_nodes, n_arcs, Vw, start;
+  int32_t eos_w, unk_id, n_trie_nodes, n_trie_arcs;
+  int32_t V, space_id, go_id, eos_id;
+  float weight, bonus, oov;
+  int32_t pad_;
+  const float* bow;
+  const int32_t* backoff;
+  const int32_t* arc_begin;
+  const int32_t* sym;
+  const float* logp;
+  const int32_t* next;
+  const int32_t* t_begin;
+  const int32_t* t_sym;
+  const int32_t* t_next;
+  const int32_t* t_word;
+  float* s_lm;
+  int32_t* lm_steps;
+  float* lm_logp;
+} avsr_ctc_prefix_word_ngram;
+/* 1 if avsr_ctc_prefix_search_word_ngram runs this shape, else 0 (decided on the host; nothing is dereferenced). */
+int avsr_ctc_prefix_word_ngram_supported(int32_t V, int32_t beam_width, int32_t L_max, int32_t n_nodes, int32_t n_arcs, int32_t Vw,
+                                         int32_t n_trie_nodes, int32_t n_trie_arcs);
+/* AVSR_ERR_ARG for a NULL / non-positive / inconsistent argument, AVSR_ERR_UNSUPPORTED outside the limits: both before any launch. */
+int avsr_ctc_prefix_search_word_ngram(const avsr_ctc_prefix_args* a, const avsr_ctc_prefix_word_ngram* wg, void* stream);
+
 /* Shallow fusion of the same back-off N-GRAM into BEAM SEARCH (csrc/beam_ngram.hip; the rule is this project's own, INTEGRATION.md
  * section 8), the counterpart of avsr_beam_lm with the automaton above as the model:
  *   step_logp[k][v] = log_softmax(logits_am[k])[v] + lm_weight * lam(v | GO, g_k)  (+ the CTC term of avsr_beam_ctc)     (unfinished beam k)

@@ -4,7 +4,13 @@
 
 The label sequences come through the pipelines avsr.LM trains on: a labels TFRecord, or a text file with one sentence per line split
 into characters (symbols that are no unit are left out).  The estimator is ngram.estimate: interpolated Witten-Bell in back-off form.
-Which of the two the second argument is, its first record decides (a TFRecord frame whose length checksum holds)."""
+Which of the two the second argument is, its first record decides (a TFRecord frame whose length checksum holds).
+
+    python tools/train_ngram.py --words TEXT_FILE ORDER OUT.arpa
+
+The word-level form for `AVSR(ctc_word_ngram_lm=...)`: every line of the text file is a sentence, split on spaces into words; the
+same estimator runs over the word vocabulary (<s>, </s>, <unk> -- never seen, so it holds the share Witten-Bell leaves to an unseen
+word -- and every word of the text) and the result is written with ngram.write_word_arpa."""
 import os
 import sys
 
@@ -20,7 +26,26 @@ def _is_tfrecord(path):
         return False
 
 
+def words_main(argv):
+    from avsr_tf1_amd import ngram
+    source, order, out = argv
+    with open(source, "r", encoding="utf-8") as f:
+        sentences = [line.split() for line in f if line.split()]
+    reserved = {ngram.WORD_BOS, ngram.WORD_EOS} | set(ngram.WORD_UNK)
+    vocabulary = [ngram.WORD_BOS, ngram.WORD_EOS] + sorted({w for s in sentences for w in s if w not in reserved} | {ngram.WORD_UNK[0]})
+    ids = {w: i for i, w in enumerate(vocabulary)}
+    unk = ids[ngram.WORD_UNK[0]]
+    model = ngram.estimate([[ids.get(w, unk) for w in s] for s in sentences], int(order), ngram.word_dict(vocabulary))
+    ngram.write_word_arpa(out, model, vocabulary)
+    t = ngram.compile_tables(model, len(vocabulary), 0, 1)
+    print("%d sentences, %d words, order %d: %s n-grams; word automaton of %d nodes, %d arcs -> %s"
+          % (len(sentences), len(vocabulary) - 3, model.order, " + ".join(str(len(g)) for g in model.grams), t["n_nodes"], t["n_arcs"], out))
+    return 0
+
+
 def main(argv):
+    if len(argv) == 4 and argv[0] == "--words":
+        return words_main(argv[1:])
     if len(argv) != 4:
         print(__doc__)
         return 2
