@@ -12,6 +12,7 @@
 #include "beam.h"          // the selection step, the LM / CTC steps ahead of it
 #include "beam_gemm.h"     // the tiled cell / attention-layer steps of mode 3
 #include "dec_persist.h"   // the fused launches tried first
+#include "cell_state.h"    // the layout of `state` / `dstate`
 
 extern "C" int avsr_step_launch_raw(const void* launch, void* stream);                  // step.hip
 extern "C" int avsr_attn_launch_raw(const void* launch, int backward, void* stream);    // attention.hip
@@ -184,24 +185,25 @@ __global__ __launch_bounds__(256) void logits_sample_kernel(const float* x, long
   }
 }
 
-static inline float* hbuf(const avsr_attn_rnn& d, int p) { return d.state + (long)p * d.B * d.H; }
-static inline float* cbuf(const avsr_attn_rnn& d, int p) { return d.state + (long)(2 + p) * d.B * d.H; }
-static inline float* dgroll(const avsr_attn_rnn& d, int p) { return d.dstate + (long)p * d.B * 4 * d.H; }
-static inline float* dcbuf(const avsr_attn_rnn& d, int p) { return d.dstate + (long)(8 + p) * d.B * d.H; }
-static inline float* dhcarry(const avsr_attn_rnn& d, int p) { return d.dstate + (long)(10 + p) * d.B * d.H; }
-// extra decoder layers (MultiRNNCell above the attention-fed cell): same buffer conventions as the block's own cell
-static inline float* xhbuf(const avsr_attn_rnn& d, int j, int p) { return d.extra[j].state + (long)p * d.B * d.H; }
-static inline float* xcbuf(const avsr_attn_rnn& d, int j, int p) { return d.extra[j].state + (long)(2 + p) * d.B * d.H; }
-static inline float* xdgroll(const avsr_attn_rnn& d, int j, int p) { return d.extra[j].dstate + (long)p * d.B * 4 * d.H; }
-static inline float* xdcbuf(const avsr_attn_rnn& d, int j, int p) { return d.extra[j].dstate + (long)(8 + p) * d.B * d.H; }
-static inline float* xdhcarry(const avsr_attn_rnn& d, int j, int p) { return d.extra[j].dstate + (long)(10 + p) * d.B * d.H; }
 // output record of decoder layer j (0 = the attention-fed cell): [B][L+1][H], slot l+1 = step l
-// GRU extra layers: the same dstate layout as the block's own GRU cell (d gates rolling [2][B][2H] | d cand [2][B][H] | carry [2][B][H] | 2 tmp)
-static inline float* xg_dgg(const avsr_attn_rnn& d, int j, int p) { return d.extra[j].dstate + (long)p * d.B * 2 * d.H; }
-static inline float* xg_dpc(const avsr_attn_rnn& d, int j, int p) { return d.extra[j].dstate + (long)(4 + p) * d.B * d.H; }
-static inline float* xg_carry(const avsr_attn_rnn& d, int j, int p) { return d.extra[j].dstate + (long)(6 + p) * d.B * d.H; }
-static inline float* xg_tmp(const avsr_attn_rnn& d, int j, int w) { return d.extra[j].dstate + (long)(8 + w) * d.B * d.H; }
 static inline float* layer_out(const avsr_attn_rnn& d, int j) { return j == 0 ? (d.n_extra > 0 ? d.out0 : d.cell_out) : d.extra[j - 1].out; }
+// One decoder layer as the cell-step builders read it: j = 0 the attention-fed cell (its fields sit in avsr_attn_rnn itself), j > 0
+// extra[j - 1] (MultiRNNCell above it: same buffer conventions).  kw = row length of wt / wt2, roff = where their recurrent columns
+// (the recurrent rows of w / w2) begin: E + A + H and E + A for layer 0, 2H and H above.
+struct DecLayer {
+  const float *wt, *wt2, *w, *w2, *bias, *bias2;
+  float *gates, *cs, *out, *rh_seq, *hs_seq, *xin_seq, *state, *dstate, *dgates, *dgates2;
+  uint32_t cell_id;
+  int kw, roff;
+};
+static inline DecLayer dec_layer(const avsr_attn_rnn& d, int j) {
+  const int H = d.H, EA = d.E + d.n_mech * H;
+  if (j == 0) return {d.wt, d.wt2, d.w, d.w2, d.bias, d.bias2, d.gates, d.cs, layer_out(d, 0), d.rh_seq, d.hs_seq, nullptr, d.state, d.dstate,
+                      d.dgates, d.dgates2, (uint32_t)d.cell_id, EA + H, EA};
+  const avsr_dec_layer& X = d.extra[j - 1];
+  return {X.wt, X.wt2, X.w, X.w2, X.bias, X.bias2, X.gates, X.cs, X.out, X.rh_seq, X.hs_seq, X.xin_seq, X.state, X.dstate,
+          X.dgates, X.dgates2, (uint32_t)X.cell_id, 2 * H, H};
+}
 static inline int nchunk(const avsr_attn_mech& m) { return (m.T + m.chunk - 1) / m.chunk; }
 static inline bool is_bahdanau(const avsr_attn_mech& m) { return m.type >= ATT_BAHDANAU; }
 
@@ -264,6 +266,8 @@ static int bwd_check(const avsr_attn_rnn& d, int* n_bah_out, int* n_luong_out) {
   if (d.n_extra > 0 && (d.dh_final || d.dc_final)) return AVSR_ERR_UNSUPPORTED;     // final-state gradients: single-cell blocks only
   for (int j = 0; j < d.n_extra; ++j)
     if (!d.extra[j].w || !d.extra[j].dgates || !d.extra[j].dstate) return AVSR_ERR_ARG;
+  for (int j = 0; d.cell == 1 && j < d.n_extra; ++j)
+    if (!d.extra[j].w2 || !d.extra[j].dgates2) return AVSR_ERR_ARG;           // GRU layers: candidate kernel and its gradient record
   *n_bah_out = n_bah; *n_luong_out = n_luong;
   return AVSR_OK;
 }
@@ -313,7 +317,7 @@ static int attn_rnn_fwd_impl(const avsr_attn_rnn* dp, const avsr_beam_lm* lm, co
   if (lm && ng) return AVSR_ERR_ARG;                           // one language model per search
   const avsr_attn_rnn& d = *dp;
   hipStream_t s = (hipStream_t)stream;
-  const int B = d.B, H = d.H, L = d.L, E = d.E, A = d.n_mech * H, KW = E + A + H;
+  const int B = d.B, H = d.H, L = d.L, E = d.E, A = d.n_mech * H;
   if (l_begin < 0 || l_end > L || l_begin > l_end) return AVSR_ERR_ARG;
   if ((rc = fwd_check(d))) return rc;
   const bool feed = (d.mode == 1 || d.mode == 3);      // inputs come from the embedding of the previous prediction
@@ -327,10 +331,10 @@ static int attn_rnn_fwd_impl(const avsr_attn_rnn* dp, const avsr_beam_lm* lm, co
     // h0 / c0 or writes zeros: none reads another's result)
     avsr::DevBatch db(s);
     const size_t hrow = sizeof(float) * H, orow = sizeof(float) * (L + 1) * H;
-    if (d.h0) { db.copy(hbuf(d, 0), d.h0, bh); db.copy_2d(layer_out(d, 0), orow, d.h0, hrow, hrow, B); }
-    else { db.zero(hbuf(d, 0), bh); db.zero_2d(layer_out(d, 0), orow, hrow, B); }
-    if (d.c0) db.copy(cbuf(d, 0), d.c0, bh);
-    else db.zero(cbuf(d, 0), bh);
+    if (d.h0) { db.copy(st_h(d.state, B, H, 0), d.h0, bh); db.copy_2d(layer_out(d, 0), orow, d.h0, hrow, hrow, B); }
+    else { db.zero(st_h(d.state, B, H, 0), bh); db.zero_2d(layer_out(d, 0), orow, hrow, B); }
+    if (d.c0) db.copy(st_c(d.state, B, H, 0), d.c0, bh);
+    else db.zero(st_c(d.state, B, H, 0), bh);
     for (int j = 0; j < d.n_extra; ++j) {            // layers above start from the zero state (decoder_unimodal.py:151-157)
       const avsr_dec_layer& X = d.extra[j];
       db.zero(X.state, 4 * bh);
@@ -372,87 +376,57 @@ static int attn_rnn_fwd_impl(const avsr_attn_rnn* dp, const avsr_beam_lm* lm, co
       if (brc == AVSR_OK) cell_done = true;
       else if (brc != AVSR_ERR_UNSUPPORTED) return brc;
     }
-    for (int phase = 0; phase < (gru ? 2 : 1) && !cell_done; ++phase) {
+    // Layer 0 is fed the token (or the caller's xs) and the attention of the previous step; layer j > 0 (MultiRNNCell) consumes the
+    // output layer j-1 emitted a moment ago.  Everything after the input sources is the same cell.  A GRU takes two launches.
+    for (int j = 0; j <= d.n_extra; ++j)
+     for (int phase = 0; phase < (gru ? 2 : 1) && !(j == 0 && cell_done); ++phase) {
+      const DecLayer Y = dec_layer(d, j);
+      const bool cand = gru && phase == 1;                   // the candidate launch, through r*h of the gate launch
       SL.ntask = 1;
       StepTask& tk = SL.task[0];
       tk = StepTask{};
-      const float* wt = (gru && phase == 1) ? d.wt2 : d.wt;
-      if (feed) {
+      const float* wt = cand ? Y.wt2 : Y.wt;
+      if (j > 0) {
         StepSrc& x = tk.src[tk.nsrc++];
-        x.a = d.embedding; x.sb = E; x.K = E; x.w = wt; x.ldw = KW; x.kind = SRC_PLAIN;
+        x.a = (drop ? Y.xin_seq : layer_out(d, j - 1)) + (long)(l + 1) * H; x.sb = (long)(L + 1) * H; x.K = H; x.w = wt; x.ldw = Y.kw;
+        x.kind = SRC_OWNROW;
+      } else if (feed) {
+        StepSrc& x = tk.src[tk.nsrc++];
+        x.a = d.embedding; x.sb = E; x.K = E; x.w = wt; x.ldw = Y.kw; x.kind = SRC_PLAIN;
         tk.gather = d.tok;
-        if (d.mode == 3) tk.gather2 = d.parent_rows;
       } else if (d.mode == 2) {
         StepSrc& x = tk.src[tk.nsrc++];
-        x.a = d.xs + (long)l * E; x.sb = (long)L * E; x.K = E; x.w = wt; x.ldw = KW; x.kind = SRC_PLAIN;
+        x.a = d.xs + (long)l * E; x.sb = (long)L * E; x.K = E; x.w = wt; x.ldw = Y.kw; x.kind = SRC_PLAIN;
       }
-      if (A > 0) {
+      if (j == 0 && A > 0) {
         StepSrc& a = tk.src[tk.nsrc++];
-        a.a = (drop ? d.attd : d.att) + (long)l * A; a.sb = (long)(L + 1) * A; a.K = A; a.w = wt + E; a.ldw = KW; a.kind = SRC_PLAIN;
+        a.a = (drop ? d.attd : d.att) + (long)l * A; a.sb = (long)(L + 1) * A; a.K = A; a.w = wt + E; a.ldw = Y.kw; a.kind = SRC_PLAIN;
       }
       StepSrc& h = tk.src[tk.nsrc++];
-      h.a = (gru && phase == 1) ? hbuf(d, 2) /* r*h */ : hbuf(d, l & 1); h.sb = H; h.K = H; h.w = wt + E + A; h.ldw = KW;
+      h.a = cand ? st_rh(Y.state, B, H) : st_h(Y.state, B, H, l & 1); h.sb = H; h.K = H; h.w = wt + Y.roff; h.ldw = Y.kw;
       // r*h was written by the gate phase of THIS step into this hypothesis' own row: under beam search only the previous state
       // (h, and the attention fed back) lives in the parent's row
-      h.kind = (gru && phase == 1) ? SRC_OWNROW : SRC_PLAIN;
-      tk.B = B; tk.t = l; tk.T = L; tk.reverse = 0; tk.len = d.steplen;
-      tk.s2 = (d.mode == 0) ? 1 : 0;
-      tk.p4 = hbuf(d, l & 1);
-      if (gru && phase == 0) {
-        tk.N = 2 * H; tk.mode = EP_GRU_GATES; tk.bias = d.bias;
-        tk.p0 = d.gates; tk.p1 = hbuf(d, 2); tk.p2 = d.rh_seq;
-      } else {
-        if (gru) { tk.N = H; tk.mode = EP_GRU_CAND; tk.bias = d.bias2; tk.p0 = d.cs; tk.p1 = d.gates; }
-        else { tk.N = 4 * H; tk.mode = EP_LSTM_FWD; tk.bias = d.bias; tk.p0 = d.gates; tk.p1 = d.cs;
-               tk.p3 = cbuf(d, l & 1); tk.p5 = cbuf(d, (l + 1) & 1); }
-        tk.p2 = layer_out(d, 0) + H; tk.s0 = (long)(L + 1) * H; tk.s1 = H;
-        tk.p6 = hbuf(d, (l + 1) & 1);
-        if (drop) {
-          tk.seed = d.seed; tk.k_st = d.keep_state; tk.k_out = d.keep_out; tk.k_in = 1.0f;
-          tk.r_st = cid4 + 1; tk.r_out = cid4 + 2;
-          tk.p9 = d.hs_seq + H; tk.s4 = (long)(L + 1) * H; tk.s5 = H;
-          if (d.n_extra > 0) {   // what layer 1 consumes: this output under layer 1's input mask
-            tk.p11 = d.extra[0].xin_seq + H; tk.k_in = d.keep_in; tk.r_in = (uint32_t)d.extra[0].cell_id * 4; tk.in_W = H; tk.in_coff = 0;
-          }
-        }
-      }
-      if ((rc = avsr_step_launch_raw(&SL, stream))) return rc;
-    }
-    // ---- K1b: the layers above (MultiRNNCell): layer j consumes layer j-1's output of this step -----------------------
-    for (int j = 0; j < d.n_extra; ++j)
-     for (int phase = 0; phase < (gru ? 2 : 1); ++phase) {
-      const avsr_dec_layer& X = d.extra[j];
-      SL.ntask = 1;
-      StepTask& tk = SL.task[0];
-      tk = StepTask{};
-      const float* xwt = (gru && phase == 1) ? X.wt2 : X.wt;
-      StepSrc& x = tk.src[tk.nsrc++];
-      x.a = (drop ? X.xin_seq : layer_out(d, j)) + (long)(l + 1) * H; x.sb = (long)(L + 1) * H; x.K = H; x.w = xwt; x.ldw = 2 * H;
-      x.kind = SRC_OWNROW;
-      StepSrc& h = tk.src[tk.nsrc++];
-      h.a = (gru && phase == 1) ? xhbuf(d, j, 2) /* r*h of this step, own row */ : xhbuf(d, j, l & 1);
-      h.sb = H; h.K = H; h.w = xwt + H; h.ldw = 2 * H; h.kind = (gru && phase == 1) ? SRC_OWNROW : SRC_PLAIN;
+      h.kind = cand ? SRC_OWNROW : SRC_PLAIN;
       if (d.mode == 3) tk.gather2 = d.parent_rows;
       tk.B = B; tk.t = l; tk.T = L; tk.reverse = 0; tk.len = d.steplen;
-      tk.p4 = xhbuf(d, j, l & 1);
-      if (gru && phase == 0) {                       // gates of a GRU layer above the attention-fed one (same epilogues as the block's cell)
-        tk.N = 2 * H; tk.mode = EP_GRU_GATES; tk.bias = X.bias;
-        tk.p0 = X.gates; tk.p1 = xhbuf(d, j, 2); tk.p2 = X.rh_seq;
-        if ((rc = avsr_step_launch_raw(&SL, stream))) return rc;
-        continue;
-      }
-      if (gru) { tk.N = H; tk.mode = EP_GRU_CAND; tk.bias = X.bias2; tk.p0 = X.cs; tk.p1 = X.gates; }
-      else { tk.N = 4 * H; tk.mode = EP_LSTM_FWD; tk.bias = X.bias; tk.p0 = X.gates; tk.p1 = X.cs;
-             tk.p3 = xcbuf(d, j, l & 1); tk.p5 = xcbuf(d, j, (l + 1) & 1); }
-      tk.p6 = xhbuf(d, j, (l + 1) & 1);
-      tk.p2 = X.out + H; tk.s0 = (long)(L + 1) * H; tk.s1 = H;
-      if (drop) {
-        const uint32_t c4 = (uint32_t)X.cell_id * 4;
-        tk.seed = d.seed; tk.k_st = d.keep_state; tk.k_out = d.keep_out; tk.k_in = 1.0f;
-        tk.r_st = c4 + 1; tk.r_out = c4 + 2;
-        tk.p9 = X.hs_seq + H; tk.s4 = (long)(L + 1) * H; tk.s5 = H;
-        if (j + 1 < d.n_extra) {
-          tk.p11 = d.extra[j + 1].xin_seq + H; tk.k_in = d.keep_in; tk.r_in = (uint32_t)d.extra[j + 1].cell_id * 4; tk.in_W = H; tk.in_coff = 0;
+      tk.s2 = (j == 0 && d.mode == 0) ? 1 : 0;               // mode 0: the caller hoisted x . Wx into layer 0's `gates`
+      tk.p4 = st_h(Y.state, B, H, l & 1);
+      if (gru && !cand) {
+        tk.N = 2 * H; tk.mode = EP_GRU_GATES; tk.bias = Y.bias;
+        tk.p0 = Y.gates; tk.p1 = st_rh(Y.state, B, H); tk.p2 = Y.rh_seq;
+      } else {
+        if (gru) { tk.N = H; tk.mode = EP_GRU_CAND; tk.bias = Y.bias2; tk.p0 = Y.cs; tk.p1 = Y.gates; }
+        else { tk.N = 4 * H; tk.mode = EP_LSTM_FWD; tk.bias = Y.bias; tk.p0 = Y.gates; tk.p1 = Y.cs;
+               tk.p3 = st_c(Y.state, B, H, l & 1); tk.p5 = st_c(Y.state, B, H, (l + 1) & 1); }
+        tk.p2 = Y.out + H; tk.s0 = (long)(L + 1) * H; tk.s1 = H;
+        tk.p6 = st_h(Y.state, B, H, (l + 1) & 1);
+        if (drop) {
+          tk.seed = d.seed; tk.k_st = d.keep_state; tk.k_out = d.keep_out; tk.k_in = 1.0f;
+          tk.r_st = Y.cell_id * 4 + 1; tk.r_out = Y.cell_id * 4 + 2;
+          tk.p9 = Y.hs_seq + H; tk.s4 = (long)(L + 1) * H; tk.s5 = H;
+          if (j < d.n_extra) {   // what the layer above consumes: this output under that layer's input mask
+            tk.p11 = d.extra[j].xin_seq + H; tk.k_in = d.keep_in; tk.r_in = (uint32_t)d.extra[j].cell_id * 4; tk.in_W = H; tk.in_coff = 0;
+          }
         }
       }
       if ((rc = avsr_step_launch_raw(&SL, stream))) return rc;
@@ -557,8 +531,8 @@ static int attn_rnn_fwd_impl(const avsr_attn_rnn* dp, const avsr_beam_lm* lm, co
   }
   if (l_end == L) {
     avsr::DevBatch db(s);
-    if (d.h_final) db.copy(d.h_final, hbuf(d, L & 1), bh);
-    if (!gru && d.c_final) db.copy(d.c_final, cbuf(d, L & 1), bh);
+    if (d.h_final) db.copy(d.h_final, st_h(d.state, B, H, L & 1), bh);
+    if (!gru && d.c_final) db.copy(d.c_final, st_c(d.state, B, H, L & 1), bh);
     if (db.flush() != hipSuccess) return AVSR_ERR_HIP;
   }
   return AVSR_OK;
@@ -623,11 +597,6 @@ extern "C" int avsr_attn_rnn_bwd(const avsr_attn_rnn* dp, void* stream) {
   const uint32_t cid4 = (uint32_t)d.cell_id * 4;
   const bool gru = d.cell == 1;
   const int G = gru ? 2 : 4;      // gate pre-activations per unit
-  // GRU dstate: dGg rolling [2][B][2H] | d(cand pre-act) rolling [2][B][H] | carry [2][B][H] | tmp du | tmp dh*u
-  auto g_dgg = [&](int p) { return d.dstate + (long)p * B * 2 * H; };
-  auto g_dpc = [&](int p) { return d.dstate + (long)(4 + p) * B * H; };
-  auto g_carry = [&](int p) { return d.dstate + (long)(6 + p) * B * H; };
-  auto g_tmp = [&](int w) { return d.dstate + (long)(8 + w) * B * H; };
   const bool use_dq = (n_luong > 0) || d.dcell_ext;
   const size_t bh = sizeof(float) * B * H;
   const int NX = d.n_extra;
@@ -637,8 +606,8 @@ extern "C" int avsr_attn_rnn_bwd(const avsr_attn_rnn* dp, void* stream) {
     db.zero(d.dstate, 12 * bh);
     if (db.flush() != hipSuccess) return AVSR_ERR_HIP;
     // ... then the final-state gradients into their slots of it (a second launch: they overwrite part of what the first zeroes)
-    if (!gru && d.dc_final) db.copy(dcbuf(d, L & 1), d.dc_final, bh);
-    if (d.dh_final) db.copy(gru ? g_carry(L & 1) : dhcarry(d, L & 1), d.dh_final, bh);
+    if (!gru && d.dc_final) db.copy(ds_dc(d.dstate, B, H, L & 1), d.dc_final, bh);
+    if (d.dh_final) db.copy(gru ? dg_carry(d.dstate, B, H, L & 1) : ds_dh(d.dstate, B, H, L & 1), d.dh_final, bh);
     if (db.flush() != hipSuccess) return AVSR_ERR_HIP;
   }
 
@@ -660,10 +629,10 @@ extern "C" int avsr_attn_rnn_bwd(const avsr_attn_rnn* dp, void* stream) {
         StepTask& tk = SL.task[0];
         tk = StepTask{};
         StepSrc& x = tk.src[tk.nsrc++];
-        x.a = gru ? g_dgg((l + 1) & 1) : dgroll(d, (l + 1) & 1); x.sb = G * H; x.K = G * H; x.w = d.w + (long)E * G * H; x.ldw = G * H; x.kind = SRC_PLAIN;
+        x.a = gru ? dg_dgg(d.dstate, B, H, (l + 1) & 1) : ds_dg(d.dstate, B, H, (l + 1) & 1); x.sb = G * H; x.K = G * H; x.w = d.w + (long)E * G * H; x.ldw = G * H; x.kind = SRC_PLAIN;
         if (gru) {
           StepSrc& x2 = tk.src[tk.nsrc++];
-          x2.a = g_dpc((l + 1) & 1); x2.sb = H; x2.K = H; x2.w = d.w2 + (long)E * H; x2.ldw = H; x2.kind = SRC_PLAIN;
+          x2.a = dg_dpc(d.dstate, B, H, (l + 1) & 1); x2.sb = H; x2.K = H; x2.w = d.w2 + (long)E * H; x2.ldw = H; x2.kind = SRC_PLAIN;
         }
         tk.B = B; tk.N = A; tk.mode = EP_LINEAR; tk.t = l; tk.T = L;
         if (d.datt_ext) { tk.p1 = const_cast<float*>(d.datt_ext) + (long)l * A; tk.s1 = (long)L * A; }
@@ -722,15 +691,11 @@ extern "C" int avsr_attn_rnn_bwd(const avsr_attn_rnn* dp, void* stream) {
       StepTask& tk = SL.task[0];
       tk = StepTask{};
       const bool top = (j == NX);
-      const uint32_t c4 = j == 0 ? cid4 : (uint32_t)d.extra[j - 1].cell_id * 4;
-      StepSrc& a = tk.src[tk.nsrc++];
-      if (j == 0) {
-        a.a = gru ? g_dgg((l + 1) & 1) : dgroll(d, (l + 1) & 1); a.sb = G * H; a.K = G * H; a.w = d.w + (long)(E + A) * G * H; a.ldw = G * H;
-      } else if (gru) {
-        a.a = xg_dgg(d, j - 1, (l + 1) & 1); a.sb = 2 * H; a.K = 2 * H; a.w = d.extra[j - 1].w + (long)H * 2 * H; a.ldw = 2 * H;
-      } else {
-        a.a = xdgroll(d, j - 1, (l + 1) & 1); a.sb = 4 * H; a.K = 4 * H; a.w = d.extra[j - 1].w + (long)H * 4 * H; a.ldw = 4 * H;
-      }
+      const DecLayer Y = dec_layer(d, j);
+      float* const ds = Y.dstate;
+      const int p = l & 1, q = (l + 1) & 1;
+      StepSrc& a = tk.src[tk.nsrc++];          // the layer's own dG(l+1) through the recurrent rows of its kernel
+      a.a = gru ? dg_dgg(ds, B, H, q) : ds_dg(ds, B, H, q); a.sb = G * H; a.K = G * H; a.w = Y.w + (long)Y.roff * G * H; a.ldw = G * H;
       a.kind = SRC_PLAIN;
       if (top) {
         for (int m = 0; m < d.n_mech; ++m) {
@@ -738,44 +703,32 @@ extern "C" int avsr_attn_rnn_bwd(const avsr_attn_rnn* dp, void* stream) {
           StepSrc& x = tk.src[tk.nsrc++];
           x.a = d.datt + (long)l * A + (long)m * H; x.sb = (long)L * A; x.K = H; x.w = M.watt; x.ldw = H; x.kind = SRC_PLAIN;
           if (is_bahdanau(M)) {
-            StepSrc& q = tk.src[tk.nsrc++];
-            q.a = M.dpq + (long)l * H; q.sb = (long)L * H; q.K = H; q.w = M.wq; q.ldw = H; q.kind = SRC_PLAIN;
+            StepSrc& y = tk.src[tk.nsrc++];
+            y.a = M.dpq + (long)l * H; y.sb = (long)L * H; y.K = H; y.w = M.wq; y.ldw = H; y.kind = SRC_PLAIN;
           }
         }
-      } else if (gru) {   // GRU layer above: through its gate kernel and its candidate kernel (both phases of it ran a moment ago)
+      } else {   // d(output of layer j) = dG_{j+1}(l) . Wx_{j+1}^T: the layer above ran a moment ago (a GRU: its gate and its candidate kernel)
+        const DecLayer U = dec_layer(d, j + 1);
         StepSrc& x = tk.src[tk.nsrc++];
-        x.a = xg_dgg(d, j, l & 1); x.sb = 2 * H; x.K = 2 * H; x.w = d.extra[j].w; x.ldw = 2 * H; x.kind = SRC_PLAIN;
-        StepSrc& x2 = tk.src[tk.nsrc++];
-        x2.a = xg_dpc(d, j, l & 1); x2.sb = H; x2.K = H; x2.w = d.extra[j].w2; x2.ldw = H; x2.kind = SRC_PLAIN;
-      } else {   // d(output of layer j) = dG_{j+1}(l) . Wx_{j+1}^T  (dG of the layer above, computed a moment ago)
-        StepSrc& x = tk.src[tk.nsrc++];
-        x.a = xdgroll(d, j, l & 1); x.sb = 4 * H; x.K = 4 * H; x.w = d.extra[j].w; x.ldw = 4 * H; x.kind = SRC_PLAIN;
+        x.a = gru ? dg_dgg(U.dstate, B, H, p) : ds_dg(U.dstate, B, H, p); x.sb = G * H; x.K = G * H; x.w = U.w; x.ldw = G * H; x.kind = SRC_PLAIN;
+        if (gru) {
+          StepSrc& x2 = tk.src[tk.nsrc++];
+          x2.a = dg_dpc(U.dstate, B, H, p); x2.sb = H; x2.K = H; x2.w = U.w2; x2.ldw = H; x2.kind = SRC_PLAIN;
+        }
       }
       tk.B = B; tk.N = H; tk.t = l; tk.T = L; tk.reverse = 0; tk.len = d.steplen;
-      if (gru && j == 0) {
+      tk.p0 = Y.gates; tk.p1 = Y.cs;
+      float* const hrec = drop ? Y.hs_seq : Y.out;           // slot l = h consumed by step l (GRU)
+      if (gru) {
         tk.mode = EP_GRU_BWD_CAND;
-        tk.p0 = d.gates; tk.p1 = d.cs;
-        tk.p2 = drop ? d.hs_seq : layer_out(d, 0); tk.s2 = (long)(L + 1) * H; tk.s3 = H;     // slot l = h consumed by step l
-        tk.p4 = g_carry((l + 1) & 1); tk.p5 = g_dpc(l & 1); tk.p3 = d.dgates2; tk.p6 = g_tmp(0); tk.p7 = g_tmp(1);
-      } else if (gru) {
-        const avsr_dec_layer& X = d.extra[j - 1];
-        tk.mode = EP_GRU_BWD_CAND;
-        tk.p0 = X.gates; tk.p1 = X.cs;
-        tk.p2 = drop ? X.hs_seq : X.out; tk.s2 = (long)(L + 1) * H; tk.s3 = H;
-        tk.p4 = xg_carry(d, j - 1, (l + 1) & 1); tk.p5 = xg_dpc(d, j - 1, l & 1); tk.p3 = X.dgates2;
-        tk.p6 = xg_tmp(d, j - 1, 0); tk.p7 = xg_tmp(d, j - 1, 1);
-      } else if (j == 0) {
-        tk.mode = EP_LSTM_BWD;
-        tk.bias = d.c0;
-        tk.p0 = d.gates; tk.p1 = d.cs; tk.p2 = d.dgates; tk.p3 = dgroll(d, l & 1);
-        tk.p4 = dcbuf(d, (l + 1) & 1); tk.p5 = dcbuf(d, l & 1);
-        tk.p6 = dhcarry(d, (l + 1) & 1); tk.p7 = dhcarry(d, l & 1);
+        tk.p2 = hrec; tk.s2 = (long)(L + 1) * H; tk.s3 = H;
+        tk.p4 = dg_carry(ds, B, H, q); tk.p5 = dg_dpc(ds, B, H, p); tk.p3 = Y.dgates2; tk.p6 = dg_tmp(ds, B, H, 0); tk.p7 = dg_tmp(ds, B, H, 1);
       } else {
-        const avsr_dec_layer& X = d.extra[j - 1];
-        tk.mode = EP_LSTM_BWD;                       // c_init = 0: bias stays NULL
-        tk.p0 = X.gates; tk.p1 = X.cs; tk.p2 = X.dgates; tk.p3 = xdgroll(d, j - 1, l & 1);
-        tk.p4 = xdcbuf(d, j - 1, (l + 1) & 1); tk.p5 = xdcbuf(d, j - 1, l & 1);
-        tk.p6 = xdhcarry(d, j - 1, (l + 1) & 1); tk.p7 = xdhcarry(d, j - 1, l & 1);
+        tk.mode = EP_LSTM_BWD;
+        if (j == 0) tk.bias = d.c0;                  // c_init; the layers above start from 0: bias stays NULL
+        tk.p2 = Y.dgates; tk.p3 = ds_dg(ds, B, H, p);
+        tk.p4 = ds_dc(ds, B, H, q); tk.p5 = ds_dc(ds, B, H, p);
+        tk.p6 = ds_dh(ds, B, H, q); tk.p7 = ds_dh(ds, B, H, p);
       }
       if (top) {
         if (fold_dq) {
@@ -791,7 +744,7 @@ extern "C" int avsr_attn_rnn_bwd(const avsr_attn_rnn* dp, void* stream) {
       }
       if (drop) {
         tk.seed = d.seed; tk.k_st = d.keep_state; tk.k_out = d.keep_out; tk.k_in = 1.0f;
-        tk.r_st = c4 + 1; tk.r_out = c4 + 2;
+        tk.r_st = Y.cell_id * 4 + 1; tk.r_out = Y.cell_id * 4 + 2;
         if (!top) { tk.k_in = d.keep_in; tk.r_in = (uint32_t)d.extra[j].cell_id * 4; tk.in_W = H; tk.in_coff = 0; }
       }
       if ((rc = avsr_step_launch_raw(&SL, stream))) return rc;
@@ -802,17 +755,9 @@ extern "C" int avsr_attn_rnn_bwd(const avsr_attn_rnn* dp, void* stream) {
         StepSrc& ag = tg.src[tg.nsrc++];
         tg.B = B; tg.N = H; tg.mode = EP_GRU_BWD_GATES; tg.t = l; tg.T = L; tg.reverse = 0; tg.len = d.steplen;
         tg.s2 = (long)(L + 1) * H; tg.s3 = H;
-        if (j == 0) {
-          ag.a = g_dpc(l & 1); ag.sb = H; ag.K = H; ag.w = d.w2 + (long)(E + A) * H; ag.ldw = H; ag.kind = SRC_PLAIN;
-          tg.p0 = d.gates; tg.p2 = drop ? d.hs_seq : layer_out(d, 0);
-          tg.p6 = g_tmp(0); tg.p7 = g_tmp(1); tg.p5 = g_carry(l & 1); tg.p3 = d.dgates; tg.p1 = g_dgg(l & 1);
-        } else {
-          const avsr_dec_layer& X = d.extra[j - 1];
-          if (!X.w2 || !X.dgates2) return AVSR_ERR_ARG;
-          ag.a = xg_dpc(d, j - 1, l & 1); ag.sb = H; ag.K = H; ag.w = X.w2 + (long)H * H; ag.ldw = H; ag.kind = SRC_PLAIN;
-          tg.p0 = X.gates; tg.p2 = drop ? X.hs_seq : X.out;
-          tg.p6 = xg_tmp(d, j - 1, 0); tg.p7 = xg_tmp(d, j - 1, 1); tg.p5 = xg_carry(d, j - 1, l & 1); tg.p3 = X.dgates; tg.p1 = xg_dgg(d, j - 1, l & 1);
-        }
+        ag.a = dg_dpc(ds, B, H, p); ag.sb = H; ag.K = H; ag.w = Y.w2 + (long)Y.roff * H; ag.ldw = H; ag.kind = SRC_PLAIN;
+        tg.p0 = Y.gates; tg.p2 = hrec;
+        tg.p6 = dg_tmp(ds, B, H, 0); tg.p7 = dg_tmp(ds, B, H, 1); tg.p5 = dg_carry(ds, B, H, p); tg.p3 = Y.dgates; tg.p1 = dg_dgg(ds, B, H, p);
         if ((rc = avsr_step_launch_raw(&SL, stream))) return rc;
       }
     }
@@ -823,13 +768,13 @@ extern "C" int avsr_attn_rnn_bwd(const avsr_attn_rnn* dp, void* stream) {
     StepTask& tk = SL.task[0];
     tk = StepTask{};
     StepSrc& a = tk.src[tk.nsrc++];
-    a.a = gru ? g_dgg(0) : dgroll(d, 0); a.sb = G * H; a.K = G * H; a.w = d.w + (long)(E + A) * G * H; a.ldw = G * H; a.kind = SRC_PLAIN;
+    a.a = gru ? dg_dgg(d.dstate, B, H, 0) : ds_dg(d.dstate, B, H, 0); a.sb = G * H; a.K = G * H; a.w = d.w + (long)(E + A) * G * H; a.ldw = G * H; a.kind = SRC_PLAIN;
     tk.B = B; tk.N = H; tk.mode = EP_LINEAR; tk.t = 0; tk.T = L;
-    tk.p1 = gru ? g_carry(0) : dhcarry(d, 0); tk.s1 = H;
+    tk.p1 = gru ? dg_carry(d.dstate, B, H, 0) : ds_dh(d.dstate, B, H, 0); tk.s1 = H;
     tk.p0 = d.dh0; tk.s0 = H;
     if ((rc = avsr_step_launch_raw(&SL, stream))) return rc;
   }
-  if (!gru && d.dc0 && avsr::dev_copy(d.dc0, dcbuf(d, 0), bh, s) != hipSuccess) return AVSR_ERR_HIP;
+  if (!gru && d.dc0 && avsr::dev_copy(d.dc0, ds_dc(d.dstate, B, H, 0), bh, s) != hipSuccess) return AVSR_ERR_HIP;
   return AVSR_OK;
 }
 

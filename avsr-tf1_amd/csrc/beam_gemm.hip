@@ -20,6 +20,7 @@
 #include "attn.h"
 #include "step.h"
 #include "beam_gemm.h"
+#include "cell_state.h"
 
 namespace avsr {
 
@@ -299,11 +300,11 @@ int beam_cell_launch(const avsr_attn_rnn& d, int l, hipStream_t s) {
   x.a = d.embedding; x.sb = E; x.gather = d.tok; x.K = E;
   if (A > 0) { BGSrc& a = P.src[P.nsrc++]; a.a = d.att + (long)l * A; a.sb = (long)(L + 1) * A; a.gather = d.parent_rows; a.K = A; }
   BGSrc& h = P.src[P.nsrc++];
-  h.a = d.state + (long)(l & 1) * B * H; h.sb = H; h.gather = d.parent_rows; h.K = H;
+  h.a = st_h(d.state, B, H, l & 1); h.sb = H; h.gather = d.parent_rows; h.K = H;
   P.R = B; P.N = 4 * H; P.wt = d.wt; P.ldw = KW;
   P.ntx = (P.N + BG_T - 1) / BG_T; P.tile0 = 0;
-  P.bias = d.bias; P.c_in = d.state + (long)(2 + (l & 1)) * B * H; P.parent = d.parent_rows;
-  P.c_out = d.state + (long)(2 + ((l + 1) & 1)) * B * H; P.h_out = d.state + (long)((l + 1) & 1) * B * H;
+  P.bias = d.bias; P.c_in = st_c(d.state, B, H, l & 1); P.parent = d.parent_rows;
+  P.c_out = st_c(d.state, B, H, (l + 1) & 1); P.h_out = st_h(d.state, B, H, (l + 1) & 1);
   P.seq_out = d.cell_out + (long)(l + 1) * H; P.seq_sb = (long)(L + 1) * H;
   G.nprob = 1; G.ntiles = P.ntx * ((B + BG_T - 1) / BG_T);
   ProfScope ps(PROF_STEP_LSTM_FWD, s);

@@ -32,6 +32,7 @@
 // launches): GRU, multi-layer decoder cells, beam search, H or D > 256, V > 64, memories that
 // do not fit the resident budget.
 #include "dec_persist.h"
+#include "cell_state.h"
 
 namespace avsr {
 
@@ -96,7 +97,7 @@ __global__ __launch_bounds__(DP_NT) void dec_persist_kernel(const DPLaunch L) {
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
   const long BH = (long)B * H;
   float* const hbuf = L.state;                  // [2][B][H] ping-pong, then c [2][B][H]
-  float* const cbuf = L.state + 2 * BH;
+  float* const cbuf = L.state + ST_C * BH;      // (slots of cell_state.h)
 
   // ---------------------------------------------------------------------------------------------------------
   // wave-uniform chunk tables (E, A, H, D are multiples of 16: a 16-wide chunk never straddles a source)

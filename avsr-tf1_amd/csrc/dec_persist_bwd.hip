@@ -19,6 +19,7 @@
 // (dstate) are left exactly as the per-step loop leaves them after step 0, so the caller's d h0 / d c0 tail is unchanged.
 // Every wait is bounded (sticky error word of the persistent scratch, as in dec_persist.hip).
 #include "dec_persist.h"
+#include "cell_state.h"
 
 #define DB_KPW 8          // 16-deep K chunks of dG per wave (4H <= 1024)
 #define DB_PART 512       // floats per (workgroup, row) partial: [d cell_out (H <= 256) | d context (D <= 256)]
@@ -98,8 +99,8 @@ __global__ __launch_bounds__(DP_NT) void dec_persist_bwd_kernel(const DBLaunch L
   const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
   const long BH = (long)B * H;
   float* const dgroll = L.dstate;                // [2][B][4H]
-  float* const dcbuf = L.dstate + 8 * BH;        // [2][B][H]
-  float* const dhcarry = L.dstate + 10 * BH;     // [2][B][H]
+  float* const dcbuf = L.dstate + DS_DC * BH;    // [2][B][H]  (slots of cell_state.h)
+  float* const dhcarry = L.dstate + DS_DH * BH;  // [2][B][H]
 
   const int UW = L.UW, uwsh = L.uwsh, unit0 = j * UW;
   const int AW = L.AW, awsh = L.awsh, an0 = j * AW;

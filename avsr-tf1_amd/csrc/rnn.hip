@@ -9,6 +9,7 @@
 #include "step.h"
 #include "avsr_hip.h"
 #include "persist.h"
+#include "cell_state.h"    // the layout of `state` / `dstate`
 
 extern "C" int avsr_step_launch_raw(const void* launch, void* stream);
 int avsr_rnn_fwd_persistent(const avsr_rnn_stack* st, int32_t n, void* stream, int dry);
@@ -50,10 +51,6 @@ namespace avsr {
 
 thread_local RnnPlanRec* g_rnn_plan = nullptr;
 
-static inline float* hbuf(const avsr_rnn_layer& l, int B, int parity) { return l.state + (long)parity * B * l.units; }
-static inline float* cbuf(const avsr_rnn_layer& l, int B, int parity) { return l.state + (long)(2 + parity) * B * l.units; }
-// dropout only: the layer's output as its consumer sees it (output mask x consumer's input mask), ping-pong
-static inline float* xbuf(const avsr_rnn_layer& l, int B, int parity) { return l.state + (long)(4 + parity) * B * l.units; }
 static inline void set_cell_dropout(StepTask& tk, const avsr_rnn_stack& S, int l) {
   if (!S.seed) return;
   const uint32_t cid = (uint32_t)(S.cell_id_base + l);
@@ -66,30 +63,10 @@ static inline void set_cell_dropout(StepTask& tk, const avsr_rnn_stack& S, int l
     tk.k_in = S.consumer_keep; tk.r_in = (uint32_t)S.consumer_stream; tk.in_W = S.consumer_width; tk.in_coff = 0;
   }
 }
-// dstate: dG rolling [2][B][4H] | dc [2][B][H] | dh_carry [2][B][H]
-static inline float* dgroll(const avsr_rnn_layer& l, int B, int parity) { return l.dstate + (long)parity * B * 4 * l.units; }
-static inline float* dcbuf(const avsr_rnn_layer& l, int B, int parity) { return l.dstate + (long)(8 + parity) * B * l.units; }
-static inline float* dhcarry(const avsr_rnn_layer& l, int B, int parity) { return l.dstate + (long)(10 + parity) * B * l.units; }
-// residual layers only: d(emitted output) handed to the layer below, rolling [2][B][H] after the 12*B*H of the rest
-static inline float* dresbuf(const avsr_rnn_layer& l, int B, int parity) { return l.dstate + (long)(12 + parity) * B * l.units; }
-// GRU dstate: d(gate pre-act) rolling [2][B][2H] | d(cand pre-act) rolling [2][B][H] | carry [2][B][H] | tmp du | tmp dh*u
-static inline float* g_dgg(const avsr_rnn_layer& l, int B, int parity) { return l.dstate + (long)parity * B * 2 * l.units; }
-static inline float* g_dpc(const avsr_rnn_layer& l, int B, int parity) { return l.dstate + (long)(4 + parity) * B * l.units; }
-static inline float* g_carry(const avsr_rnn_layer& l, int B, int parity) { return l.dstate + (long)(6 + parity) * B * l.units; }
-static inline float* g_tmp(const avsr_rnn_layer& l, int B, int which) { return l.dstate + (long)(8 + which) * B * l.units; }
 
-}  // namespace avsr
-
-extern "C" int avsr_rnn_fwd(const avsr_rnn_stack* st, int32_t n, void* stream) {
-  using namespace avsr;
-  if (!st || n <= 0 || n > AVSR_MAX_STACKS) return AVSR_ERR_ARG;
-  hipStream_t s = (hipStream_t)stream;
-  {
-    int rc = AVSR_ERR_UNSUPPORTED;                                            // one launch for the whole sequence when it fits:
-    rc = run_persistent(avsr_rnn_fwd_persistent, st, n, stream);             // 8-row groups per XCD / the agent-scope form
-    if (rc != AVSR_ERR_UNSUPPORTED) return rc;
-  }
-  const int nsteps = wavefront_steps(st, n);
+// Every argument check of the per-step forward wavefront: nothing is written before it has passed.
+static int fwd_check(const avsr_rnn_stack* st, int32_t n) {
+  const bool gru = st[0].cell == 1;
   for (int i = 0; i < n; ++i) {
     const avsr_rnn_stack& S = st[i];
     if (S.cell != 0 && S.cell != 1) return AVSR_ERR_UNSUPPORTED;
@@ -100,15 +77,63 @@ extern "C" int avsr_rnn_fwd(const avsr_rnn_stack* st, int32_t n, void* stream) {
       if (Ly.units % 4 || Ly.in_dim % 4 || !Ly.wt || !Ly.gates || !Ly.cs || !Ly.state) return AVSR_ERR_ARG;
       if (Ly.hoisted && l != 0) return AVSR_ERR_ARG;
       if (Ly.residual && (l == 0 || Ly.in_dim != Ly.units || !S.layer[l - 1].out)) return AVSR_ERR_ARG;
-      // zero initial state: h parity 0, c parity 0
-      if (avsr::dev_zero(hbuf(Ly, S.B, 0), sizeof(float) * S.B * Ly.units, s) != hipSuccess) return AVSR_ERR_HIP;
-      if (avsr::dev_zero(cbuf(Ly, S.B, 0), sizeof(float) * S.B * Ly.units, s) != hipSuccess) return AVSR_ERR_HIP;
     }
   }
   if (wavefront_tasks(st, n) > STEP_MAX_TASKS) return AVSR_ERR_UNSUPPORTED;
+  // what the step loop used to find on its way, in the order the wavefront reaches the layers: layer 0 of every stack, then the rest
+  for (int i = 0; i < n; ++i) {
+    const avsr_rnn_layer& Ly = st[i].layer[0];
+    if (gru && (!Ly.wt2 || !Ly.rh_seq)) return AVSR_ERR_ARG;
+    if (!Ly.hoisted) return AVSR_ERR_UNSUPPORTED;             // layer 0 input projection must be hoisted (avsr_gemm)
+  }
+  for (int i = 0; gru && i < n; ++i)
+    for (int l = 1; l < st[i].n_layers; ++l)
+      if (!st[i].layer[l].wt2 || !st[i].layer[l].rh_seq) return AVSR_ERR_ARG;
+  return AVSR_OK;
+}
+
+// Likewise for the backward wavefront.  The GRU checks belong to the per-step path alone (the persistent forms take LSTM stacks
+// only and decline every GRU call), so they can stand ahead of the persistent attempt without refusing a call it would accept.
+static int bwd_check(const avsr_rnn_stack* st, int32_t n) {
+  for (int i = 0; i < n; ++i) {
+    const avsr_rnn_stack& S = st[i];
+    if ((S.cell != 0 && S.cell != 1) || S.cell != st[0].cell) return AVSR_ERR_UNSUPPORTED;
+    if (S.n_layers <= 0 || S.n_layers > AVSR_MAX_LAYERS) return AVSR_ERR_ARG;
+    for (int l = 0; l < S.n_layers; ++l) {
+      const avsr_rnn_layer& Ly = S.layer[l];
+      if (!Ly.w || !Ly.dgates || !Ly.dstate || !Ly.gates || !Ly.cs) return AVSR_ERR_ARG;
+    }
+  }
+  if (wavefront_tasks(st, n) > STEP_MAX_TASKS) return AVSR_ERR_UNSUPPORTED;
+  for (int i = 0; st[0].cell == 1 && i < n; ++i)
+    for (int l = 0; l < st[i].n_layers; ++l) {
+      const avsr_rnn_layer& Ly = st[i].layer[l];
+      if (!Ly.w2 || !Ly.dgates2) return AVSR_ERR_ARG;
+      if ((st[i].seed || Ly.residual) && !Ly.hs_seq) return AVSR_ERR_ARG;   // h(t-1) as the cell consumed it, below
+    }
+  return AVSR_OK;
+}
+
+}  // namespace avsr
+
+extern "C" int avsr_rnn_fwd(const avsr_rnn_stack* st, int32_t n, void* stream) {
+  using namespace avsr;
+  if (!st || n <= 0 || n > AVSR_MAX_STACKS) return AVSR_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  int rc = run_persistent(avsr_rnn_fwd_persistent, st, n, stream);           // one launch for the whole sequence when it fits:
+  if (rc != AVSR_ERR_UNSUPPORTED) return rc;                                 // 8-row groups per XCD / the agent-scope form
+  if ((rc = fwd_check(st, n))) return rc;
+  for (int i = 0; i < n; ++i)
+    for (int l = 0; l < st[i].n_layers; ++l) {       // zero initial state: h parity 0, c parity 0
+      const avsr_rnn_layer& Ly = st[i].layer[l];
+      const size_t bytes = sizeof(float) * st[i].B * Ly.units;
+      if (avsr::dev_zero(st_h(Ly.state, st[i].B, Ly.units, 0), bytes, s) != hipSuccess) return AVSR_ERR_HIP;
+      if (avsr::dev_zero(st_c(Ly.state, st[i].B, Ly.units, 0), bytes, s) != hipSuccess) return AVSR_ERR_HIP;
+    }
 
   static thread_local StepLaunch L;
   const bool gru = st[0].cell == 1;
+  const int nsteps = wavefront_steps(st, n);
   for (int step = 0; step < nsteps; ++step) {
    for (int phase = 0; phase < (gru ? 2 : 1); ++phase) {
     L.ntask = 0;
@@ -120,81 +145,49 @@ extern "C" int avsr_rnn_fwd(const avsr_rnn_stack* st, int32_t n, void* stream) {
         const avsr_rnn_layer& Ly = S.layer[l];
         StepTask& tk = L.task[L.ntask++];
         tk = StepTask{};
-        const int H = Ly.units, in = Ly.in_dim;
-        tk.nsrc = 0;
-        if (gru) {
-          if (!Ly.wt2 || !Ly.rh_seq) return AVSR_ERR_ARG;
-          const float* wt = phase == 0 ? Ly.wt : Ly.wt2;
-          if (!Ly.hoisted) {
-            if (l == 0) return AVSR_ERR_UNSUPPORTED;
-            const avsr_rnn_layer& Lo = S.layer[l - 1];
-            StepSrc& x = tk.src[tk.nsrc++];
-            x.a = (S.seed || Lo.residual) ? xbuf(Lo, S.B, (t + 1) & 1) : hbuf(Lo, S.B, (t + 1) & 1); x.sb = Lo.units; x.K = in; x.w = wt; x.ldw = in + H; x.kind = SRC_PLAIN;
-          }
-          StepSrc& h = tk.src[tk.nsrc++];
-          h.a = phase == 0 ? hbuf(Ly, S.B, t & 1) : hbuf(Ly, S.B, 2) /* r*h */; h.sb = H; h.K = H; h.w = wt + in; h.ldw = in + H; h.kind = SRC_PLAIN;
-          tk.B = S.B; tk.t = t; tk.T = S.T; tk.reverse = S.reverse; tk.len = S.len; tk.s2 = Ly.hoisted ? 1 : 0;
-          tk.p4 = hbuf(Ly, S.B, t & 1);
-          if (phase == 0) {
-            tk.N = 2 * H; tk.mode = EP_GRU_GATES; tk.bias = Ly.bias;
-            tk.p0 = Ly.gates; tk.p1 = hbuf(Ly, S.B, 2); tk.p2 = Ly.rh_seq;
-          } else {
-            tk.N = H; tk.mode = EP_GRU_CAND; tk.bias = Ly.bias2;
-            tk.p0 = Ly.cs; tk.p1 = Ly.gates;
-            tk.p2 = Ly.out ? Ly.out + Ly.ld_out + Ly.out_col : nullptr;
-            tk.s0 = (long)(S.T + 2) * Ly.ld_out; tk.s1 = Ly.ld_out;
-            tk.p6 = hbuf(Ly, S.B, (t + 1) & 1);
-            if (Ly.residual) {   // + raw input = the lower layer's output record (slot 1 = time 0), as for the LSTM below
-              const avsr_rnn_layer& Lo = S.layer[l - 1];
-              tk.p8 = Lo.out + Lo.ld_out + Lo.out_col; tk.pad0 = (int)((long)(S.T + 2) * Lo.ld_out); tk.pad1 = (int)Lo.ld_out;
-            }
-            if (S.seed) {
-              set_cell_dropout(tk, S, l);
-              tk.s4 = (long)(S.T + 2) * H; tk.s5 = H;
-              if (Ly.hs_seq) tk.p9 = Ly.hs_seq + H;
-              if (l + 1 < S.n_layers) tk.p10 = xbuf(Ly, S.B, (t + 1) & 1);
-              if (Ly.xt_seq) tk.p11 = Ly.xt_seq + H;
-            } else if (Ly.residual) {
-              if (l + 1 < S.n_layers) tk.p10 = xbuf(Ly, S.B, (t + 1) & 1);   // no masks: the plain residual sum, for the layer above
-              if (Ly.hs_seq) { tk.p9 = Ly.hs_seq + H; tk.s4 = (long)(S.T + 2) * H; tk.s5 = H; }   // h itself: `out` holds h + x
-            }
-          }
-          continue;
-        }
+        const int B = S.B, H = Ly.units, in = Ly.in_dim, p = t & 1, q = (t + 1) & 1;
+        const bool cand = gru && phase == 1;                   // a GRU's second launch: the candidate, through r*h
+        const float* wt = cand ? Ly.wt2 : Ly.wt;
         if (!Ly.hoisted) {
-          if (l == 0) return AVSR_ERR_UNSUPPORTED;  // layer 0 input projection must be hoisted (avsr_gemm)
           const avsr_rnn_layer& Lo = S.layer[l - 1];
           StepSrc& x = tk.src[tk.nsrc++];
           // the lower layer's EMITTED output: its h state, unless dropout masks or a residual sum make the two differ
-          x.a = (S.seed || Lo.residual) ? xbuf(Lo, S.B, (t + 1) & 1) : hbuf(Lo, S.B, (t + 1) & 1); x.sb = Lo.units; x.K = in; x.w = Ly.wt; x.ldw = in + H; x.kind = SRC_PLAIN;
-          if (Ly.residual) {   // + raw input = the lower layer's output record (slot 1 = time 0)
-            tk.p8 = Lo.out + Lo.ld_out + Lo.out_col; tk.pad0 = (int)((long)(S.T + 2) * Lo.ld_out); tk.pad1 = (int)Lo.ld_out;
-          }
+          x.a = (S.seed || Lo.residual) ? st_x(Lo.state, B, Lo.units, q) : st_h(Lo.state, B, Lo.units, q);
+          x.sb = Lo.units; x.K = in; x.w = wt; x.ldw = in + H; x.kind = SRC_PLAIN;
         }
         StepSrc& h = tk.src[tk.nsrc++];
-        h.a = hbuf(Ly, S.B, t & 1); h.sb = H; h.K = H; h.w = Ly.wt + in; h.ldw = in + H; h.kind = SRC_PLAIN;
-        tk.B = S.B; tk.N = 4 * H; tk.mode = EP_LSTM_FWD;
-        tk.t = t; tk.T = S.T; tk.reverse = S.reverse; tk.len = S.len; tk.bias = Ly.bias;
-        tk.p0 = Ly.gates; tk.p1 = Ly.cs;
+        h.a = cand ? st_rh(Ly.state, B, H) : st_h(Ly.state, B, H, p); h.sb = H; h.K = H; h.w = wt + in; h.ldw = in + H; h.kind = SRC_PLAIN;
+        tk.B = B; tk.t = t; tk.T = S.T; tk.reverse = S.reverse; tk.len = S.len; tk.s2 = Ly.hoisted ? 1 : 0;
+        tk.p4 = st_h(Ly.state, B, H, p);
+        if (gru && !cand) {
+          tk.N = 2 * H; tk.mode = EP_GRU_GATES; tk.bias = Ly.bias;
+          tk.p0 = Ly.gates; tk.p1 = st_rh(Ly.state, B, H); tk.p2 = Ly.rh_seq;
+          continue;
+        }
+        if (gru) { tk.N = H; tk.mode = EP_GRU_CAND; tk.bias = Ly.bias2; tk.p0 = Ly.cs; tk.p1 = Ly.gates; }
+        else { tk.N = 4 * H; tk.mode = EP_LSTM_FWD; tk.bias = Ly.bias; tk.p0 = Ly.gates; tk.p1 = Ly.cs;
+               tk.p3 = st_c(Ly.state, B, H, p); tk.p5 = st_c(Ly.state, B, H, q); }
         tk.p2 = Ly.out ? Ly.out + Ly.ld_out /* slot 1 = time 0 */ + Ly.out_col : nullptr;
-        tk.s0 = (long)(S.T + 2) * Ly.ld_out; tk.s1 = Ly.ld_out; tk.s2 = Ly.hoisted ? 1 : 0;
-        tk.p3 = cbuf(Ly, S.B, t & 1); tk.p4 = hbuf(Ly, S.B, t & 1);
-        tk.p5 = cbuf(Ly, S.B, (t + 1) & 1); tk.p6 = hbuf(Ly, S.B, (t + 1) & 1);
+        tk.s0 = (long)(S.T + 2) * Ly.ld_out; tk.s1 = Ly.ld_out;
+        tk.p6 = st_h(Ly.state, B, H, q);
+        if (Ly.residual) {   // + raw input = the lower layer's output record (slot 1 = time 0)
+          const avsr_rnn_layer& Lo = S.layer[l - 1];
+          tk.p8 = Lo.out + Lo.ld_out + Lo.out_col; tk.pad0 = (int)((long)(S.T + 2) * Lo.ld_out); tk.pad1 = (int)Lo.ld_out;
+        }
         if (S.seed) {
           set_cell_dropout(tk, S, l);
           tk.s4 = (long)(S.T + 2) * H; tk.s5 = H;
           if (Ly.hs_seq) tk.p9 = Ly.hs_seq + H;                       // slot 1 = time 0
-          if (l + 1 < S.n_layers) tk.p10 = xbuf(Ly, S.B, (t + 1) & 1);
+          if (l + 1 < S.n_layers) tk.p10 = st_x(Ly.state, B, H, q);
           if (Ly.xt_seq) tk.p11 = Ly.xt_seq + H;
         } else if (Ly.residual) {
-          if (l + 1 < S.n_layers) tk.p10 = xbuf(Ly, S.B, (t + 1) & 1);   // no masks: the plain residual sum, for the layer above
+          if (l + 1 < S.n_layers) tk.p10 = st_x(Ly.state, B, H, q);   // no masks: the plain residual sum, for the layer above
           if (Ly.hs_seq) { tk.p9 = Ly.hs_seq + H; tk.s4 = (long)(S.T + 2) * H; tk.s5 = H; }   // h itself (dWh operand): `out` holds h + x
         }
       }
     }
     if (L.ntask == 0) continue;
-    int rc = avsr_step_launch_raw(&L, stream);
-    if (rc) return rc;
+    if ((rc = avsr_step_launch_raw(&L, stream))) return rc;
    }
   }
   for (int i = 0; i < n; ++i) {
@@ -202,9 +195,9 @@ extern "C" int avsr_rnn_fwd(const avsr_rnn_stack* st, int32_t n, void* stream) {
     for (int l = 0; l < S.n_layers; ++l) {
       const avsr_rnn_layer& Ly = S.layer[l];
       const size_t bytes = sizeof(float) * S.B * Ly.units;
-      if (Ly.h_final && avsr::dev_copy(Ly.h_final, hbuf(Ly, S.B, S.T & 1), bytes, s) != hipSuccess)
+      if (Ly.h_final && avsr::dev_copy(Ly.h_final, st_h(Ly.state, S.B, Ly.units, S.T & 1), bytes, s) != hipSuccess)
         return AVSR_ERR_HIP;
-      if (!gru && Ly.c_final && avsr::dev_copy(Ly.c_final, cbuf(Ly, S.B, S.T & 1), bytes, s) != hipSuccess)
+      if (!gru && Ly.c_final && avsr::dev_copy(Ly.c_final, st_c(Ly.state, S.B, Ly.units, S.T & 1), bytes, s) != hipSuccess)
         return AVSR_ERR_HIP;
     }
   }
@@ -215,39 +208,28 @@ extern "C" int avsr_rnn_bwd(const avsr_rnn_stack* st, int32_t n, void* stream) {
   using namespace avsr;
   if (!st || n <= 0 || n > AVSR_MAX_STACKS) return AVSR_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
-  const int nsteps = wavefront_steps(st, n);
+  int rc = bwd_check(st, n);
+  if (rc) return rc;
+  const bool gru = st[0].cell == 1;
   for (int i = 0; i < n; ++i) {
     const avsr_rnn_stack& S = st[i];
-    if ((S.cell != 0 && S.cell != 1) || S.cell != st[0].cell) return AVSR_ERR_UNSUPPORTED;
-    if (S.n_layers <= 0 || S.n_layers > AVSR_MAX_LAYERS) return AVSR_ERR_ARG;
     for (int l = 0; l < S.n_layers; ++l) {
       const avsr_rnn_layer& Ly = S.layer[l];
-      if (!Ly.w || !Ly.dgates || !Ly.dstate || !Ly.gates || !Ly.cs) return AVSR_ERR_ARG;
-      const size_t bh = sizeof(float) * S.B * Ly.units;
+      const int B = S.B, H = Ly.units, pT = S.T & 1;
+      const size_t bh = sizeof(float) * B * H;
       // rolling dG (both parities), dc / dh_carry at parity T&1 = gradient of the final state
       if (avsr::dev_zero(Ly.dstate, (Ly.residual ? 14 : 12) * bh, s) != hipSuccess) return AVSR_ERR_HIP;
-      if (l == S.n_layers - 1) {
-        if (S.cell == 1) {
-          if (S.dh_final && avsr::dev_copy(g_carry(Ly, S.B, S.T & 1), S.dh_final, bh, s) != hipSuccess)
-            return AVSR_ERR_HIP;
-        } else {
-          if (S.dc_final && avsr::dev_copy(dcbuf(Ly, S.B, S.T & 1), S.dc_final, bh, s) != hipSuccess)
-            return AVSR_ERR_HIP;
-          if (S.dh_final && avsr::dev_copy(dhcarry(Ly, S.B, S.T & 1), S.dh_final, bh, s) != hipSuccess)
-            return AVSR_ERR_HIP;
-        }
-      }
+      if (l != S.n_layers - 1) continue;
+      if (!gru && S.dc_final && avsr::dev_copy(ds_dc(Ly.dstate, B, H, pT), S.dc_final, bh, s) != hipSuccess) return AVSR_ERR_HIP;
+      if (S.dh_final && avsr::dev_copy(gru ? dg_carry(Ly.dstate, B, H, pT) : ds_dh(Ly.dstate, B, H, pT), S.dh_final, bh, s) != hipSuccess)
+        return AVSR_ERR_HIP;
     }
   }
-  if (wavefront_tasks(st, n) > STEP_MAX_TASKS) return AVSR_ERR_UNSUPPORTED;
-  {
-    int rc = AVSR_ERR_UNSUPPORTED;                                            // one launch for the whole BPTT when it fits:
-    rc = run_persistent(avsr_rnn_bwd_persistent, st, n, stream);
-    if (rc != AVSR_ERR_UNSUPPORTED) return rc;
-  }
+  rc = run_persistent(avsr_rnn_bwd_persistent, st, n, stream);              // one launch for the whole BPTT when it fits
+  if (rc != AVSR_ERR_UNSUPPORTED) return rc;
 
   static thread_local StepLaunch L;
-  const bool gru = st[0].cell == 1;
+  const int nsteps = wavefront_steps(st, n);
   for (int step = 0; step < nsteps; ++step) {
    for (int phase = 0; phase < (gru ? 2 : 1); ++phase) {
     L.ntask = 0;
@@ -260,71 +242,56 @@ extern "C" int avsr_rnn_bwd(const avsr_rnn_stack* st, int32_t n, void* stream) {
         const avsr_rnn_layer& Ly = S.layer[l];
         StepTask& tk = L.task[L.ntask++];
         tk = StepTask{};
-        const int H = Ly.units, in = Ly.in_dim;
+        const int B = S.B, H = Ly.units, in = Ly.in_dim, p = t & 1, q = (t + 1) & 1;
+        const int G = gru ? 2 : 4;                         // gate pre-activations per unit
+        float* const ds = Ly.dstate;
+        tk.B = B; tk.N = H; tk.t = t; tk.T = S.T; tk.reverse = S.reverse; tk.len = S.len;
+        tk.p0 = Ly.gates;
         if (gru) {
-          if (!Ly.w2 || !Ly.dgates2) return AVSR_ERR_ARG;
           // h(t-1) as the cell consumed it: the state-dropped sequence under dropout, else the output sequence
           const bool own_h = S.seed || Ly.residual;        // (a residual layer's output record holds h + x)
-          if (own_h && !Ly.hs_seq) return AVSR_ERR_ARG;
           const float* hseq = own_h ? Ly.hs_seq : Ly.out + Ly.out_col;
           const long hld = own_h ? H : Ly.ld_out;
-          tk.B = S.B; tk.N = H; tk.t = t; tk.T = S.T; tk.reverse = S.reverse; tk.len = S.len;
-          tk.p0 = Ly.gates;
           tk.p2 = const_cast<float*>(hseq) + (S.reverse ? 2 * hld : 0); tk.s2 = (long)(S.T + 2) * hld; tk.s3 = hld;
-          tk.p6 = g_tmp(Ly, S.B, 0); tk.p7 = g_tmp(Ly, S.B, 1);
-          if (phase == 0) {
-            tk.mode = EP_GRU_BWD_CAND;
-            StepSrc& a = tk.src[tk.nsrc++];
-            a.a = g_dgg(Ly, S.B, (t + 1) & 1); a.sb = 2 * H; a.K = 2 * H; a.w = Ly.w + (long)in * 2 * H; a.ldw = 2 * H; a.kind = SRC_PLAIN;
-            if (l + 1 < nl) {
-              const avsr_rnn_layer& Up = S.layer[l + 1];
-              StepSrc& u1 = tk.src[tk.nsrc++];
-              u1.a = g_dgg(Up, S.B, t & 1); u1.sb = 2 * Up.units; u1.K = 2 * Up.units; u1.w = Up.w; u1.ldw = 2 * Up.units; u1.kind = SRC_PLAIN;
-              StepSrc& u2 = tk.src[tk.nsrc++];
-              u2.a = g_dpc(Up, S.B, t & 1); u2.sb = Up.units; u2.K = Up.units; u2.w = Up.w2; u2.ldw = Up.units; u2.kind = SRC_PLAIN;
-            }
-            tk.p1 = Ly.cs; tk.p4 = g_carry(Ly, S.B, (t + 1) & 1);
-            tk.p5 = g_dpc(Ly, S.B, t & 1); tk.p3 = Ly.dgates2;
-            if (Ly.dout) {
-              tk.p8 = const_cast<float*>(Ly.dout) + Ly.ld_dout + Ly.dout_col;
-              tk.s0 = (long)(S.T + 2) * Ly.ld_dout; tk.s1 = Ly.ld_dout;
-            } else if (l + 1 < nl && S.layer[l + 1].residual) {
-              tk.p8 = dresbuf(S.layer[l + 1], S.B, t & 1); tk.s0 = H; tk.s1 = 0;   // d(output) through the upper layer's residual sum
-            }
-            if (Ly.residual) tk.p10 = dresbuf(Ly, S.B, t & 1);
-            if (S.seed) {
-              set_cell_dropout(tk, S, l);
-              if (l + 1 >= nl) tk.k_in = 1.0f;
-            }
-          } else {
+          tk.p6 = dg_tmp(ds, B, H, 0); tk.p7 = dg_tmp(ds, B, H, 1);
+          if (phase == 1) {
             tk.mode = EP_GRU_BWD_GATES;
             StepSrc& a = tk.src[tk.nsrc++];
-            a.a = g_dpc(Ly, S.B, t & 1); a.sb = H; a.K = H; a.w = Ly.w2 + (long)in * H; a.ldw = H; a.kind = SRC_PLAIN;
-            tk.p5 = g_carry(Ly, S.B, t & 1); tk.p3 = Ly.dgates; tk.p1 = g_dgg(Ly, S.B, t & 1);
+            a.a = dg_dpc(ds, B, H, p); a.sb = H; a.K = H; a.w = Ly.w2 + (long)in * H; a.ldw = H; a.kind = SRC_PLAIN;
+            tk.p5 = dg_carry(ds, B, H, p); tk.p3 = Ly.dgates; tk.p1 = dg_dgg(ds, B, H, p);
+            continue;
           }
-          continue;
         }
-        // dh[b,u] = dG_{t+1}(own) . Wh[u,:]  +  dG_t(upper layer) . Wx_upper[u,:]
-        StepSrc& a = tk.src[0];
-        a.a = dgroll(Ly, S.B, (t + 1) & 1); a.sb = 4 * H; a.K = 4 * H; a.w = Ly.w + (long)in * 4 * H; a.ldw = 4 * H; a.kind = SRC_PLAIN;
-        tk.nsrc = 1;
+        // dh[b,u] = dG_{t+1}(own) . Wh[u,:]  +  dG_t(upper layer) . Wx_upper[u,:]  (a GRU above: its gate and its candidate kernel)
+        StepSrc& a = tk.src[tk.nsrc++];
+        a.a = gru ? dg_dgg(ds, B, H, q) : ds_dg(ds, B, H, q); a.sb = G * H; a.K = G * H; a.w = Ly.w + (long)in * G * H; a.ldw = G * H; a.kind = SRC_PLAIN;
         if (l + 1 < nl) {
           const avsr_rnn_layer& Up = S.layer[l + 1];
+          const int HU = Up.units;
           StepSrc& u = tk.src[tk.nsrc++];
-          u.a = dgroll(Up, S.B, t & 1); u.sb = 4 * Up.units; u.K = 4 * Up.units; u.w = Up.w; u.ldw = 4 * Up.units; u.kind = SRC_PLAIN;
+          u.a = gru ? dg_dgg(Up.dstate, B, HU, p) : ds_dg(Up.dstate, B, HU, p); u.sb = G * HU; u.K = G * HU; u.w = Up.w; u.ldw = G * HU; u.kind = SRC_PLAIN;
+          if (gru) {
+            StepSrc& u2 = tk.src[tk.nsrc++];
+            u2.a = dg_dpc(Up.dstate, B, HU, p); u2.sb = HU; u2.K = HU; u2.w = Up.w2; u2.ldw = HU; u2.kind = SRC_PLAIN;
+          }
         }
-        tk.B = S.B; tk.N = H; tk.mode = EP_LSTM_BWD;
-        tk.t = t; tk.T = S.T; tk.reverse = S.reverse; tk.len = S.len; tk.bias = nullptr;
-        tk.p0 = Ly.gates; tk.p1 = Ly.cs; tk.p2 = Ly.dgates; tk.p3 = dgroll(Ly, S.B, t & 1);
-        tk.p4 = dcbuf(Ly, S.B, (t + 1) & 1); tk.p5 = dcbuf(Ly, S.B, t & 1);
-        tk.p6 = dhcarry(Ly, S.B, (t + 1) & 1); tk.p7 = dhcarry(Ly, S.B, t & 1);
+        tk.p1 = Ly.cs;
+        if (gru) {
+          tk.mode = EP_GRU_BWD_CAND;
+          tk.p4 = dg_carry(ds, B, H, q); tk.p5 = dg_dpc(ds, B, H, p); tk.p3 = Ly.dgates2;
+        } else {
+          tk.mode = EP_LSTM_BWD;
+          tk.p2 = Ly.dgates; tk.p3 = ds_dg(ds, B, H, p);
+          tk.p4 = ds_dc(ds, B, H, q); tk.p5 = ds_dc(ds, B, H, p);
+          tk.p6 = ds_dh(ds, B, H, q); tk.p7 = ds_dh(ds, B, H, p);
+        }
         if (Ly.dout) {
           tk.p8 = const_cast<float*>(Ly.dout) + Ly.ld_dout + Ly.dout_col;  // slot 1 = time 0
           tk.s0 = (long)(S.T + 2) * Ly.ld_dout; tk.s1 = Ly.ld_dout;
         } else if (l + 1 < nl && S.layer[l + 1].residual) {
-          tk.p8 = dresbuf(S.layer[l + 1], S.B, t & 1); tk.s0 = H; tk.s1 = 0;   // d(output) through the upper layer's residual sum
+          tk.p8 = ds_dres(S.layer[l + 1].dstate, B, S.layer[l + 1].units, p); tk.s0 = H; tk.s1 = 0;   // d(output) through the upper layer's residual sum
         }
-        if (Ly.residual) tk.p10 = dresbuf(Ly, S.B, t & 1);
+        if (Ly.residual) tk.p10 = ds_dres(ds, B, H, p);
         if (S.seed) {
           set_cell_dropout(tk, S, l);
           if (l + 1 >= nl) tk.k_in = 1.0f;   // no upper layer inside the stack: external d out is already wrt the output
@@ -332,8 +299,7 @@ extern "C" int avsr_rnn_bwd(const avsr_rnn_stack* st, int32_t n, void* stream) {
       }
     }
     if (L.ntask == 0) continue;
-    int rc = avsr_step_launch_raw(&L, stream);
-    if (rc) return rc;
+    if ((rc = avsr_step_launch_raw(&L, stream))) return rc;
    }
   }
   return AVSR_OK;

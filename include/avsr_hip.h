@@ -106,7 +106,7 @@ int avsr_gemm_batch(const avsr_gemm_desc* descs, int32_t n, void* stream);
  *                        on entry (bias is added by the kernel).
  *   cs     [B][T][H]     cell states (post clip)
  *   out    [B][T+2][ld_out] (+out_col)  slot s = time s-1; caller keeps slot 0 and slots > len zero.
- *   state  scratch 4*B*H floats (h and c ping-pong)
+ *   state  scratch 4*B*H floats (h and c ping-pong; the layout of state / dstate: csrc/cell_state.h)
  *   dgates [B][T][H][4]  backward: d(pre-activation)
  *   dstate scratch (2*4 + 2 + 2)*B*H floats
  *   dout   gradient wrt out (same slot layout/stride as out), top layer only (others NULL)
@@ -138,7 +138,9 @@ typedef struct avsr_rnn_layer {
   /* GRU (stack.cell == 1; rnn_cell_impl.GRUCell, avsr/cells.py:25-29).  wt/w/bias = gate kernel [in+H][2H] with unit-
    * interleaved columns (2*unit + {0:r,1:u}) and its transpose; wt2/w2/bias2 = candidate kernel [in+H][H].
    * `gates` holds [B][T][H][2] (hoisted x.Wg_x on entry), `cs` the candidate record [B][T][H] (hoisted x.Wc_x on entry),
-   * rh_seq [B][T][H] = r*h (dWc operand); backward: dgates [B][T][H][2], dgates2 [B][T][H]. */
+   * rh_seq [B][T][H] = r*h (dWc operand); backward: dgates [B][T][H][2], dgates2 [B][T][H].
+   * wt2 and rh_seq (forward), w2 and dgates2 (backward) are required of every GRU layer, here, in avsr_dec_layer and in
+   * avsr_attn_rnn: a call without one returns AVSR_ERR_ARG and writes nothing.  bias2, like bias, may be NULL: a zero bias. */
   const float* wt2;
   const float* w2;
   const float* bias2;
@@ -243,7 +245,7 @@ int avsr_rnn_plan(const avsr_rnn_stack* stacks, int32_t n_stacks, int32_t bwd, i
  * Buffers (A = n_mech * H):
  *   gates [B][L][H][4], cs [B][L][H], cell_out [B][L+1][H] (slot l+1 = step l; slot 0 = h0, written
  *   by the op), att [B][L+1][A] (slot l+1 = attention after step l; slot 0 zero, written by the op),
- *   state scratch 4*B*H.
+ *   state scratch 4*B*H (its layout, and dstate's: csrc/cell_state.h).
  *   per mechanism: scores [B][L][T] raw scores (Luong: un-scaled), ctx [B][L][D], pq [B][L][H]
  *   (Bahdanau), pstat [L][2][nchunk][B], pctx scratch [nchunk][B][D], with nchunk = ceil(T / chunk).
  * Backward adds: dgates [B][L][H][4], dstate scratch 12*B*H, datt [B][L][A], dq scratch [B][L][H]
@@ -284,7 +286,7 @@ typedef struct avsr_attn_mech {
  * what `cell_out` records, so the top layer's `out` must be the block's cell_out.  State starts at zero
  * (decoder_unimodal.py:151-157).  Buffers: wt [4H][2H] / w [2H][4H] (rows: input part, then recurrent part), bias [H][4],
  * gates [B][L][H][4], cs [B][L][H], out [B][L+1][H] (slot l+1 = step l, slot 0 = 0), state 4*B*H, dgates [B][L][H][4],
- * dstate 12*B*H; dropout only: hs_seq [B][L+1][H] state-dropped h, xin_seq [B][L+1][H] = the input as this layer consumed it
+ * dstate 12*B*H (layout: csrc/cell_state.h); dropout only: hs_seq [B][L+1][H] state-dropped h, xin_seq [B][L+1][H] = the input as this layer consumed it
  * (slot l+1 = step l: lower layer's output mask x this layer's input mask).
  * GRU layers (round 6): wt [2H][2H] / w [2H][2H] = the gate kernel (columns unit-interleaved r, u), bias [H][2], gates [B][L][H][2],
  * cs = the candidate record [B][L][H], dgates [B][L][H][2]; plus the candidate kernel wt2 [H][2H] / w2 [2H][H] (rows: input part, then

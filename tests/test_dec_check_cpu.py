@@ -359,3 +359,34 @@ def test_library_plan_declines_as_the_calls_do():
         assert ops.attn_rnn_plan(d)["form"] == "per_step" and ops.attn_rnn_plan(d, bwd=True)["form"] == "per_step"
     finally:
         ops._L().avsr_rnn_set_persistent(None, 0)
+
+
+def _gru_two_layer_descriptor():
+    """A GRU block with one layer above the attention-fed cell and no mechanism, by hand: every pointer either call needs is a fake
+    non-NULL address (avsr_attn_rnn_plan only tests pointers for NULL)."""
+    from avsr_tf1_amd._lib import AttnRnn
+    d = AttnRnn()
+    d.B, d.L, d.H, d.E, d.n_mech, d.mode, d.cell, d.n_extra = 2, 3, 4, 4, 0, 0, 1, 1
+    for f in ("steplen", "wt", "w", "bias", "gates", "cs", "cell_out", "state", "dgates", "dstate", "wt2", "w2", "bias2", "rh_seq", "dgates2", "out0"):
+        setattr(d, f, 64)
+    X = d.extra[0]
+    for f in ("wt", "w", "bias", "gates", "cs", "out", "state", "dgates", "dstate", "wt2", "w2", "bias2", "rh_seq", "dgates2"):
+        setattr(X, f, 64)
+    X.cell_id = 1
+    return d
+
+
+def test_library_plan_checks_the_gru_layers_of_both_passes():
+    """What a GRU layer needs is asked before anything is queued, so the plan answers it too: the candidate kernel and the r*h record of
+    the forward pass, the transposed candidate kernel and d(candidate) of the BPTT, for the block's own cell and for a layer above it."""
+    from avsr_tf1_amd import ops
+    from avsr_tf1_amd._lib import AvsrError
+    ops._L().avsr_rnn_set_persistent(None, 0)
+    d = _gru_two_layer_descriptor()
+    assert ops.attn_rnn_plan(d)["form"] == "per_step" and ops.attn_rnn_plan(d, bwd=True)["form"] == "per_step"
+    for where, field, bwd in (("extra", "w2", True), ("extra", "dgates2", True), ("block", "w2", True), ("block", "dgates2", True),
+                              ("extra", "wt2", False), ("extra", "rh_seq", False)):
+        d = _gru_two_layer_descriptor()
+        setattr(d.extra[0] if where == "extra" else d, field, None)
+        with pytest.raises(AvsrError, match="code -1"):                     # AVSR_ERR_ARG
+            ops.attn_rnn_plan(d, bwd=bwd)

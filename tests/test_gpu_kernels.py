@@ -266,3 +266,27 @@ def test_adam_step_with_cosine_restarts(start):
     assert int(step.item()) == t
     assert np.abs(dp.cpu().numpy() - want).max() < 2e-6 * max(1.0, lr_t / 1e-3)
     assert np.abs((dp.cpu().numpy() - p) - (want - p)).max() < 1e-3 * np.abs(want - p).max() + 1e-9
+
+
+def test_rnn_per_step_refuses_before_it_writes():
+    """A descriptor the per-step wavefront refuses is refused before anything is queued: the two-layer GRU row of tests/ref_rnn.py's
+    table, every buffer inside its NaN band, once without layer 1's candidate kernel (forward) and once without layer 0's d(candidate)
+    record (BPTT).  Both return AVSR_ERR_ARG and every buffer of both layers comes back bit for bit (no NULL reaches a kernel)."""
+    import ref_rnn as R
+    from test_gpu_rnn_conformance import _addr, _upload
+    from avsr_tf1_amd import ops
+    from avsr_tf1_amd._lib import AvsrError
+    case = {c.name: c for c in R.CASES}["gru/fw"]
+    assert len(case.stacks) == 1 and len(case.stacks[0].units) == 2 and case.stacks[0].cell == "gru"
+    inp, ref, _ = R.fixture(case)
+    before = R.initial_buffers(case, inp, ref)
+    dev_ = _upload(case, inp, before)
+    ops.rnn_set_persistent(False)
+    for call, layer, field in ((ops.rnn_fwd, 1, "wt2"), (ops.rnn_bwd, 0, "dgates2")):
+        stacks = R.descriptors(case, _addr(dev_, before))
+        setattr(stacks[0].layer[layer], field, None)
+        with pytest.raises(AvsrError, match="code -1"):
+            call(stacks)
+        torch.cuda.synchronize()
+        for key in before:          # gates, cs, rh, out, state, dgates, dgates2, dstate of both layers among them
+            assert (dev_[key].cpu().numpy().view(np.uint32) == before[key].view(np.uint32)).all(), (call.__name__, key)
