@@ -234,6 +234,16 @@ class BeamNgram(C.Structure):
                [(n, C.c_void_p) for n in ("bow", "backoff", "arc_begin", "sym", "logp", "next", "node", "lm_logp")]
 
 
+class BeamWordNgram(C.Structure):
+    """avsr_beam_word_ngram: the word automaton and lexicon trie of CtcPrefixWordNgram as beam search's fused model
+    (csrc/beam_word_ngram.hip)."""
+    _fields_ = [(n, C.c_int32) for n in ("n_nodes", "n_arcs", "Vw", "start", "eos_w", "unk_id", "n_trie_nodes", "n_trie_arcs", "V", "space_id",
+                                         "go_id", "eos_id", "n_rows")] + \
+               [("lm_weight", C.c_float), ("oov", C.c_float), ("pad_", C.c_int32)] + \
+               [(n, C.c_void_p) for n in ("bow", "backoff", "arc_begin", "sym", "logp", "next", "t_begin", "t_sym", "t_next", "t_word", "state",
+                                          "lm_logp")]
+
+
 CTC_ALIGN_MAX_L = 512                  # AVSR_CTC_ALIGN_MAX_L of include/avsr_hip.h
 
 
@@ -257,7 +267,7 @@ _STRUCTS = {"avsr_dec_layer": DecLayer, "avsr_mat": Mat, "avsr_gemm_desc": GemmD
             "avsr_attn_rnn_launch": AttnRnnLaunch,
             "avsr_colsum_job": ColsumJob, "avsr_beam_lm": BeamLm, "avsr_beam_ctc": BeamCtc, "avsr_ctc_prefix_args": CtcPrefixArgs,
             "avsr_ctc_prefix_lm": CtcPrefixLm, "avsr_ctc_prefix_ngram": CtcPrefixNgram, "avsr_ctc_prefix_word_ngram": CtcPrefixWordNgram,
-            "avsr_beam_ngram": BeamNgram,
+            "avsr_beam_ngram": BeamNgram, "avsr_beam_word_ngram": BeamWordNgram,
             "avsr_ctc_align_args": CtcAlignArgs}
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -333,6 +343,9 @@ _SIGS = {
     "avsr_beam_ngram_supported": [C.POINTER(BeamNgram)],
     "avsr_beam_ngram_step": [C.POINTER(BeamNgram), _vp, _vp, _i32, _i32, _vp],
     "avsr_attn_rnn_fwd_ngram": [C.POINTER(AttnRnn), C.POINTER(BeamNgram), C.POINTER(BeamCtc), _i32, _i32, _vp],
+    "avsr_beam_word_ngram_supported": [C.POINTER(BeamWordNgram)],
+    "avsr_beam_word_ngram_step": [C.POINTER(BeamWordNgram), _vp, _vp, _i32, _i32, _vp],
+    "avsr_attn_rnn_fwd_word_ngram": [C.POINTER(AttnRnn), C.POINTER(BeamWordNgram), C.POINTER(BeamCtc), _i32, _i32, _vp],
     "avsr_beam_ctc_supported": [C.POINTER(BeamCtc)],
     "avsr_beam_ctc_begin": [C.POINTER(BeamCtc), _vp],
     "avsr_beam_ctc_step": [C.POINTER(BeamCtc), _vp, _vp, _vp, _i32, _vp],

@@ -28,6 +28,12 @@ unfinished beam's continuation with log p_model + lm_weight * log p_lm (INTEGRAT
 with the same `lm_weight`: log p_model + lm_weight * lam(v | GO, labels), one table-walk launch per step and no model to train
 (ngram.py, csrc/beam_ngram.hip).  It is refused together with `lm_checkpoint` and under any other `decoding_algorithm`; it works together
 with `ctc_decode_weight`.
+`word_ngram_lm` (the path of an ARPA file over WORDS, read as `ctc_word_ngram_lm` below is) fuses a word-level back-off n-gram into beam
+search of a model over single-character units through a lexicon trie, again with `lm_weight`: letters inside the lexicon are free, the
+letter that leaves it pays `word_oov_score` (-10.0, natural log: a conventional value, not a tuned one) once, and a space or EOS that
+closes a word pays the word model (ngram.py compile_word_tables, csrc/beam_word_ngram.hip; the rule is INTEGRATION.md section 8).  No CTC
+head is needed.  Refused together with `lm_checkpoint` or `ngram_lm`, under any other `decoding_algorithm`, and for unit files without
+' ' or with multi-character units; it works together with `ctc_decode_weight`.  Nothing was trained with it: no error rate is claimed.
 Hybrid CTC / attention training (not in the reference, which only reserves `use_ctc` in its hyper-parameters): `use_ctc` (False),
 `ctc_weight` (0.3: a conventional value, not a tuned one) arrive through **kwargs; a CTC head on the audio (else video) encoder adds
 ctc_weight * CTC loss per label token to the step's loss, and `evaluate` also reports that head's best-path error rate under the key
@@ -231,6 +237,30 @@ class AVSR(object):
                 raise ValueError("ngram_lm: avsr_beam_ngram_supported covers automata of up to %d nodes and %d arcs (got %d, %d)"
                                  % (CTC_PREFIX_NGRAM_MAX_NODES, CTC_PREFIX_NGRAM_MAX_ARCS, self._ngram["n_nodes"], self._ngram["n_arcs"]))
 
+        # word-level n-gram behind a lexicon trie, fused into beam search (csrc/beam_word_ngram.hip): parsed, compiled and refused on the
+        # host, here, before any engine is built; without the keyword nothing is read
+        self._word_ngram = None
+        word_ngram_lm = kwargs.get('word_ngram_lm')
+        if word_ngram_lm is not None:
+            from . import ngram as _ngram
+            from ._lib import CTC_PREFIX_NGRAM_MAX_ARCS, CTC_PREFIX_NGRAM_MAX_NODES
+            if decoding_algorithm != 'beam_search':
+                raise ValueError("word_ngram_lm needs decoding_algorithm='beam_search': this keyword fuses the word model into the "
+                                 "attention decoder's beam ('ctc_prefix_beam_search' takes ctc_word_ngram_lm; 'greedy' and "
+                                 "'attention_rescoring' take no language model)")
+            if lm_checkpoint is not None or ngram_lm is not None:
+                raise ValueError("word_ngram_lm and %s are two language models for one search: give one of them"
+                                 % ("lm_checkpoint" if lm_checkpoint is not None else "ngram_lm"))
+            if not self._lm_weight >= 0.0 or self._lm_weight == float('inf'):
+                raise ValueError("lm_weight must be a finite number >= 0 (got %r)" % (kwargs.get('lm_weight'),))
+            # ValueError: not an ARPA file, units that cannot spell (no ' ', multi-character units), no spellable word, a bad oov score
+            g = self._word_ngram = _ngram.load_word_tables(word_ngram_lm, self._unit_dict, kwargs.get('word_oov_score', -10.0))
+            if max(g["n_nodes"], g["n_trie_nodes"]) > CTC_PREFIX_NGRAM_MAX_NODES or max(g["n_arcs"], g["n_trie_arcs"]) > CTC_PREFIX_NGRAM_MAX_ARCS:
+                raise ValueError("word_ngram_lm: avsr_beam_word_ngram_supported covers word automata and lexicon tries of up to %d nodes "
+                                 "and %d arcs each (got %d, %d and %d, %d)"
+                                 % (CTC_PREFIX_NGRAM_MAX_NODES, CTC_PREFIX_NGRAM_MAX_ARCS, g["n_nodes"], g["n_arcs"], g["n_trie_nodes"],
+                                    g["n_trie_arcs"]))
+
         # language model fused into the CTC prefix search (csrc/ctc_prefix_lm.hip): its own keywords, refused on the host like lm_checkpoint
         self._ctc_lm = None
         self._ctc_lm_weight, self._ctc_lm_bonus = float(kwargs.get('ctc_lm_weight', 0.3)), float(kwargs.get('ctc_lm_length_bonus', 0.0))
@@ -283,7 +313,8 @@ class AVSR(object):
             from ._lib import CTC_PREFIX_LM_MAX_W, CTC_PREFIX_NGRAM_MAX_ARCS, CTC_PREFIX_NGRAM_MAX_NODES
             if decoding_algorithm != 'ctc_prefix_beam_search':
                 raise ValueError("ctc_word_ngram_lm needs decoding_algorithm='ctc_prefix_beam_search': the word model is fused into the "
-                                 "CTC head's own search (no other decoding algorithm takes a word-level model)")
+                                 "CTC head's own search ('beam_search' takes word_ngram_lm; 'greedy' and 'attention_rescoring' take no word-level "
+                                 "model)")
             if ctc_lm_checkpoint is not None or ctc_ngram_lm is not None:
                 raise ValueError("ctc_word_ngram_lm and %s are two language models for one search: give one of them"
                                  % ("ctc_lm_checkpoint" if ctc_lm_checkpoint is not None else "ctc_ngram_lm"))
@@ -611,9 +642,11 @@ class AVSR(object):
     def _decode(self, batch):
         """The predictions of one batch under `decoding_algorithm`: rows of ids (a numpy array or a list of id lists)."""
         if self._decoding_algorithm == 'beam_search':     # avsr.py:58-59 default: width 10, first beam returned
+            fused = self._lm is not None or self._ngram is not None or self._word_ngram is not None
             ids = self._model.beam_search_decode(batch, beam_width=self._beam_width, max_steps=self._cfg.max_label_length,
                                                  lm=self._lm, ngram=self._ngram,
-                                                 lm_weight=self._lm_weight if self._lm is not None or self._ngram is not None else 0.0,
+                                                 lm_weight=self._lm_weight if fused else 0.0,
+                                                 **({} if self._word_ngram is None else dict(word_ngram=self._word_ngram)),
                                                  ctc_weight=self._ctc_decode_weight)
         elif self._decoding_algorithm == 'attention_rescoring':        # two passes: the head's n-best, then teacher-forced scoring
             ids = self._model.attention_rescoring(batch, beam_width=self._beam_width, max_steps=self._cfg.max_label_length,

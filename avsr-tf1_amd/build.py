@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(CSRC, "libavsr_hip.so")
-SOURCES = ["capi.hip", "gemm.hip", "step.hip", "rnn.hip", "rnn_persist.hip", "rnn_persist_bwd.hip", "attention.hip", "attn_rnn.hip", "beam.hip", "beam_gemm.hip", "beam_lm.hip", "beam_ngram.hip", "beam_ctc.hip", "dec_persist.hip", "dec_persist_bwd.hip", "elementwise.hip", "reduce.hip", "batchnorm.hip", "conv.hip", "conv_direct.hip", "conv_mfma.hip", "conv_wgrad.hip", "conv3d.hip", "audio_frontend.hip", "specaugment.hip", "video_augment.hip", "ctc.hip", "ctc_prefix.hip", "ctc_prefix_lm.hip", "ctc_prefix_ngram.hip", "ctc_prefix_word_ngram.hip", "ctc_align.hip", "rescore.hip"]
+SOURCES = ["capi.hip", "gemm.hip", "step.hip", "rnn.hip", "rnn_persist.hip", "rnn_persist_bwd.hip", "attention.hip", "attn_rnn.hip", "beam.hip", "beam_gemm.hip", "beam_lm.hip", "beam_ngram.hip", "beam_word_ngram.hip", "beam_ctc.hip", "dec_persist.hip", "dec_persist_bwd.hip", "elementwise.hip", "reduce.hip", "batchnorm.hip", "conv.hip", "conv_direct.hip", "conv_mfma.hip", "conv_wgrad.hip", "conv3d.hip", "audio_frontend.hip", "specaugment.hip", "video_augment.hip", "ctc.hip", "ctc_prefix.hip", "ctc_prefix_lm.hip", "ctc_prefix_ngram.hip", "ctc_prefix_word_ngram.hip", "ctc_align.hip", "rescore.hip"]
 
 
 def _hipcc():

@@ -307,14 +307,18 @@ static void fill_attn_launch(const avsr_attn_rnn& d, int l, AttnLaunch& AL) {
 
 // lm != NULL (mode 3 only, checked by the caller): the language-model step runs ahead of every step's selection.
 // ng != NULL (likewise; never together with lm): the back-off n-gram's step takes that place (beam_ngram.hip).
+// wn != NULL (likewise; never together with lm or ng): the word-level n-gram's step behind a lexicon trie (beam_word_ngram.hip).
 // ctc != NULL (mode 3, weight > 0): the CTC prefix-score step runs after it, and the selection reads ctc->extra -- the two terms
 // combined by that step -- as its one additive term with weight 1 (beam_ctc.hip).
-static int attn_rnn_fwd_impl(const avsr_attn_rnn* dp, const avsr_beam_lm* lm, const avsr_beam_ngram* ng, const avsr_beam_ctc* ctc,
-                             int32_t l_begin, int32_t l_end, void* stream) {
+static int attn_rnn_fwd_impl(const avsr_attn_rnn* dp, const avsr_beam_lm* lm, const avsr_beam_ngram* ng,
+                             const avsr_beam_word_ngram* wn, const avsr_beam_ctc* ctc, int32_t l_begin, int32_t l_end, void* stream) {
   using namespace avsr;
   int rc = validate(dp);
   if (rc) return rc;
-  if (lm && ng) return AVSR_ERR_ARG;                           // one language model per search
+  if ((lm != nullptr) + (ng != nullptr) + (wn != nullptr) > 1) return AVSR_ERR_ARG;   // one language model per search
+  // the fused model's [R][V] term and its weight, whichever model it is: what the selection reads when no CTC step pre-combines it
+  const float* const fused_logp = lm ? lm->lm_logp : ng ? ng->lm_logp : wn ? wn->lm_logp : nullptr;
+  const float fused_weight = lm ? lm->lm_weight : ng ? ng->lm_weight : wn ? wn->lm_weight : 0.f;
   const avsr_attn_rnn& d = *dp;
   hipStream_t s = (hipStream_t)stream;
   const int B = d.B, H = d.H, L = d.L, E = d.E, A = d.n_mech * H;
@@ -368,6 +372,7 @@ static int attn_rnn_fwd_impl(const avsr_attn_rnn* dp, const avsr_beam_lm* lm, co
     // ---- K0: language-model step on the symbols and parents the previous selection left (independent of the decoder's chain) ----
     if (lm && (rc = beam_lm_step_launch(*lm, d.tok, d.parent_rows, l, s))) return rc;
     if (ng && (rc = beam_ngram_step_launch(*ng, d.tok, d.parent_rows, l, s))) return rc;
+    if (wn && (rc = beam_word_ngram_step_launch(*wn, d.tok, d.parent_rows, l, s))) return rc;
     if (ctc && (rc = beam_ctc_step_launch(*ctc, d.tok, d.parent_rows, d.beam_fin + (long)(l & 1) * B, l, s))) return rc;
     // ---- K1: LSTM step -------------------------------------------------------------------
     bool cell_done = false;
@@ -503,7 +508,7 @@ static int attn_rnn_fwd_impl(const avsr_attn_rnn* dp, const avsr_beam_lm* lm, co
         bs = BeamStep{d.logits + (long)l * d.V, (long)L * d.V, B / d.beam_width, d.beam_width, d.V, l, d.eos_id, d.length_penalty,
                       d.beam_logp + pin, d.beam_fin + pin, d.beam_len + pin, d.beam_logp + pout, d.beam_fin + pout, d.beam_len + pout,
                       d.tok, d.parent_rows, d.step_ids, d.parent_ids, d.n_unfinished, xa, xsb, O, d.wout_t, d.bout,
-                      ctc ? ctc->extra : lm ? lm->lm_logp : ng ? ng->lm_logp : nullptr, ctc ? 1.f : lm ? lm->lm_weight : ng ? ng->lm_weight : 0.f};
+                      ctc ? ctc->extra : fused_logp, ctc ? 1.f : fused_weight};
         bs_inside = beam_dense && beam_step_nct(bs) != 0;
       }
       if (!bs_inside) {
@@ -539,7 +544,7 @@ static int attn_rnn_fwd_impl(const avsr_attn_rnn* dp, const avsr_beam_lm* lm, co
 }
 
 extern "C" int avsr_attn_rnn_fwd(const avsr_attn_rnn* dp, int32_t l_begin, int32_t l_end, void* stream) {
-  return attn_rnn_fwd_impl(dp, nullptr, nullptr, nullptr, l_begin, l_end, stream);
+  return attn_rnn_fwd_impl(dp, nullptr, nullptr, nullptr, nullptr, l_begin, l_end, stream);
 }
 
 extern "C" int avsr_attn_rnn_fwd_lm(const avsr_attn_rnn* dp, const avsr_beam_lm* lm, int32_t l_begin, int32_t l_end, void* stream) {
@@ -548,7 +553,7 @@ extern "C" int avsr_attn_rnn_fwd_lm(const avsr_attn_rnn* dp, const avsr_beam_lm*
   const int rc = avsr::beam_lm_check(lm);
   if (rc) return rc;
   if (lm->V != dp->V || lm->n_rows != dp->B) return AVSR_ERR_ARG;
-  return attn_rnn_fwd_impl(dp, lm, nullptr, nullptr, l_begin, l_end, stream);
+  return attn_rnn_fwd_impl(dp, lm, nullptr, nullptr, nullptr, l_begin, l_end, stream);
 }
 
 extern "C" int avsr_attn_rnn_fwd_ctc(const avsr_attn_rnn* dp, const avsr_beam_lm* lm, const avsr_beam_ctc* ctc, int32_t l_begin,
@@ -565,7 +570,7 @@ extern "C" int avsr_attn_rnn_fwd_ctc(const avsr_attn_rnn* dp, const avsr_beam_lm
   } else if (ctc->lm_logp) {
     return AVSR_ERR_ARG;
   }
-  return attn_rnn_fwd_impl(dp, lm, nullptr, ctc->weight == 0.f ? nullptr : ctc, l_begin, l_end, stream);
+  return attn_rnn_fwd_impl(dp, lm, nullptr, nullptr, ctc->weight == 0.f ? nullptr : ctc, l_begin, l_end, stream);
 }
 
 extern "C" int avsr_attn_rnn_fwd_ngram(const avsr_attn_rnn* dp, const avsr_beam_ngram* ng, const avsr_beam_ctc* ctc, int32_t l_begin,
@@ -581,7 +586,23 @@ extern "C" int avsr_attn_rnn_fwd_ngram(const avsr_attn_rnn* dp, const avsr_beam_
         ctc->lm_logp != ng->lm_logp)
       return AVSR_ERR_ARG;
   }
-  return attn_rnn_fwd_impl(dp, nullptr, ng, ctc && ctc->weight != 0.f ? ctc : nullptr, l_begin, l_end, stream);
+  return attn_rnn_fwd_impl(dp, nullptr, ng, nullptr, ctc && ctc->weight != 0.f ? ctc : nullptr, l_begin, l_end, stream);
+}
+
+extern "C" int avsr_attn_rnn_fwd_word_ngram(const avsr_attn_rnn* dp, const avsr_beam_word_ngram* wn, const avsr_beam_ctc* ctc,
+                                            int32_t l_begin, int32_t l_end, void* stream) {
+  if (!dp || !wn) return AVSR_ERR_ARG;
+  if (dp->mode != 3) return AVSR_ERR_ARG;                      // fusion is defined on the beam
+  int rc = avsr::beam_word_ngram_check(wn);
+  if (rc) return rc;
+  if (wn->V != dp->V || wn->n_rows != dp->B) return AVSR_ERR_ARG;
+  if (ctc) {
+    if ((rc = avsr::beam_ctc_check(ctc))) return rc;
+    if (ctc->V != dp->V || (long)ctc->n_utt * ctc->beam_width != dp->B || ctc->beam_width != dp->beam_width || ctc->eos_id != dp->eos_id ||
+        ctc->lm_logp != wn->lm_logp)
+      return AVSR_ERR_ARG;
+  }
+  return attn_rnn_fwd_impl(dp, nullptr, nullptr, wn, ctc && ctc->weight != 0.f ? ctc : nullptr, l_begin, l_end, stream);
 }
 
 extern "C" int avsr_attn_rnn_bwd(const avsr_attn_rnn* dp, void* stream) {

@@ -1,4 +1,4 @@
-// The beam-search selection step (csrc/beam.hip) and the per-step terms queued ahead of it (beam_lm.hip, beam_ngram.hip, beam_ctc.hip): what the
+// The beam-search selection step (csrc/beam.hip) and the per-step terms queued ahead of it (beam_lm.hip, beam_ngram.hip, beam_word_ngram.hip, beam_ctc.hip): what the
 // decoder's scheduler (attn_rnn.hip) and the C entries call.
 #pragma once
 #include "common.h"
@@ -37,6 +37,8 @@ int beam_lm_check(const avsr_beam_lm* m);                                       
 int beam_lm_step_launch(const avsr_beam_lm& m, const int32_t* tok, const int32_t* parent_rows, int step, hipStream_t s);
 int beam_ngram_check(const avsr_beam_ngram* g);                                     // beam_ngram.hip: the back-off n-gram step
 int beam_ngram_step_launch(const avsr_beam_ngram& g, const int32_t* tok, const int32_t* parent_rows, int step, hipStream_t s);
+int beam_word_ngram_check(const avsr_beam_word_ngram* g);                           // beam_word_ngram.hip: the word-level n-gram step
+int beam_word_ngram_step_launch(const avsr_beam_word_ngram& g, const int32_t* tok, const int32_t* parent_rows, int step, hipStream_t s);
 int beam_ctc_check(const avsr_beam_ctc* c);                                         // beam_ctc.hip: the CTC prefix-score step
 int beam_ctc_begin_launch(const avsr_beam_ctc& c, hipStream_t s);
 int beam_ctc_step_launch(const avsr_beam_ctc& c, const int32_t* tok, const int32_t* parent_rows, const int32_t* fin, int step, hipStream_t s);

@@ -9,7 +9,7 @@ extern "C" int64_t avsr_sizeof(const char* name) {
 #define SZ(T) if (!strcmp(name, #T)) return (int64_t)sizeof(T);
   SZ(avsr_mat) SZ(avsr_gemm_desc) SZ(avsr_conv_desc) SZ(avsr_conv_launch) SZ(avsr_bn_plan) SZ(avsr_conv3d_desc) SZ(avsr_logmel_args) SZ(avsr_spec_augment_args) SZ(avsr_video_augment_args) SZ(avsr_ctc_args) SZ(avsr_rnn_layer) SZ(avsr_rnn_stack) SZ(avsr_rnn_launch) SZ(avsr_colsum_job)
 #ifdef AVSR_HAVE_ATTN
-  SZ(avsr_attn_mech) SZ(avsr_attn_rnn) SZ(avsr_attn_rnn_launch) SZ(avsr_transpose_job) SZ(avsr_dec_layer) SZ(avsr_beam_lm) SZ(avsr_beam_ctc) SZ(avsr_ctc_prefix_args) SZ(avsr_ctc_prefix_lm) SZ(avsr_ctc_prefix_ngram) SZ(avsr_ctc_prefix_word_ngram) SZ(avsr_beam_ngram) SZ(avsr_ctc_align_args)
+  SZ(avsr_attn_mech) SZ(avsr_attn_rnn) SZ(avsr_attn_rnn_launch) SZ(avsr_transpose_job) SZ(avsr_dec_layer) SZ(avsr_beam_lm) SZ(avsr_beam_ctc) SZ(avsr_ctc_prefix_args) SZ(avsr_ctc_prefix_lm) SZ(avsr_ctc_prefix_ngram) SZ(avsr_ctc_prefix_word_ngram) SZ(avsr_beam_ngram) SZ(avsr_beam_word_ngram) SZ(avsr_ctc_align_args)
 #endif
 #undef SZ
   return -1;

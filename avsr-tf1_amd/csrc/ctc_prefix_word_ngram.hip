@@ -2,7 +2,9 @@
 // (avsr_ctc_prefix_search_word_ngram, include/avsr_hip.h; the rule is INTEGRATION.md section 8): the search of csrc/ctc_prefix_search.h
 // (cp_search: ONE launch per batch, one 256-thread workgroup per utterance, the beam in LDS, fp32, no atomics, two launches
 // bit-identical) with lam(. | g) formed from two device-resident read-only tables -- the word automaton, walked by csrc/ngram_walk.h as
-// it is (word ids in the place of unit ids), and the trie over the vocabulary's spellings.  This file is the model's side only.
+// it is (word ids in the place of unit ids), and the trie over the vocabulary's spellings.  The model's side -- the trie search, the
+// transition, close / hc / eos and the per-class value -- is csrc/word_ngram_walk.h, one copy shared with beam search's word step
+// (csrc/beam_word_ngram.hip); this file places its state in the search's LDS.
 //
 // State placement.  Per label sequence the model holds FIVE words in LDS behind the search's own, [2 W rows] each, addressed by the
 // same per-slot row index as the lam rows (a stay inherits its parent's row, an extension takes a row no old slot references, so no
@@ -22,40 +24,13 @@
 // Nothing here can run away on tables it was not meant for: the walk is bounded and clamped (ngram_walk.h), the trie search is the same
 // clamped binary search, and every node and word id read from a table is clamped into its table before it is used as an index.
 #include "ctc_prefix_search.h"
-#include "ngram_walk.h"
+#include "word_ngram_walk.h"
 
 namespace avsr {
 
-#define CPW_FLOOR (-227.95592420641054f)                                    // -99 ln 10 (ngram.FLOOR), rounded to fp32 once
-#define CPW_OOV (-1)
-
-// the lexicon trie: CSR over nodes, children sorted by unit id
-struct trie_view {
-  int n_nodes, n_arcs;
-  const int32_t* begin; const int32_t* sym; const int32_t* next; const int32_t* word;
-};
-
-// the child of trie node p (0 <= p < n_nodes) under unit c, or CPW_OOV
-__device__ __forceinline__ int trie_child(const trie_view& T, int p, int c) {
-  int lo = T.begin[p], end = T.begin[p + 1];
-  lo = lo < 0 ? 0 : lo;
-  end = end > T.n_arcs ? T.n_arcs : end;
-  int hi = end;
-  while (lo < hi) {                                                        // the first child with sym >= c
-    const int mid = (lo + hi) >> 1;
-    if (T.sym[mid] < c) lo = mid + 1; else hi = mid;
-  }
-  if (!(lo < end && T.sym[lo] == c)) return CPW_OOV;
-  const int n = T.next[lo];
-  return (unsigned)n < (unsigned)T.n_nodes ? n : CPW_OOV;
-}
-
-// the word model behind the trie as cp_search's Step: five words per pool row in LDS
+// the word model (word_ngram_walk.h) as cp_search's Step: five words per pool row in LDS
 struct cpw_step {
-  const ngram_view G;
-  const trie_view T;
-  const int V, Vw, start, eos_w, unk_id, space_id, go_id, eos_id;
-  const float oov;
+  const word_model M;
   int* sH; int* sP; float* sClose; int* sHc; float* sEos;                  // [2 W] each
   static size_t extra(int W) { return 10 * (size_t)W; }
   __device__ __forceinline__ void init(int, int W, uint32_t* words) {
@@ -63,52 +38,25 @@ struct cpw_step {
     sHc = reinterpret_cast<int*>(sClose + 2 * W); sEos = reinterpret_cast<float*>(sHc + 2 * W);
   }
   __device__ __forceinline__ void prologue(int) {}
-  __device__ __forceinline__ int word_id(int w) const { return (unsigned)w < (unsigned)Vw ? w : -1; }
-  // what a space costs at (h, p != root) and the node it leaves: the word p ends, else <unk> (oov first for a proper prefix)
-  __device__ __forceinline__ float close(int h, int p, int& hc) const {
-    int w = p > 0 ? word_id(T.word[p]) : -1;
-    const bool prefix = p > 0 && w < 0;
-    if (w < 0) w = word_id(unk_id);
-    float v = 0.f;
-    hc = 0;
-    if (w >= 0) {
-      int arc;
-      v = ngram_walk(G, h, w, arc);
-      hc = ngram_node(G, G.next[arc]);
-    }
-    return prefix ? oov + v : v;
-  }
-  __device__ __forceinline__ void step(int M, const int* sTok, const int* sPar, const int* sNew, float* sLam, bool first) {
-    const int tid = threadIdx.x;
-    if (tid < M) {
-      int h = ngram_node(G, start), p = 0;
+  __device__ __forceinline__ void step(int M_, const int* sTok, const int* sPar, const int* sNew, float* sLam, bool first) {
+    const int tid = threadIdx.x, V = M.V;
+    if (tid < M_) {
+      int h = ngram_node(M.G, M.start), p = 0;
       if (!first) {
-        const int par = sPar[tid], c = sTok[tid];
+        const int par = sPar[tid];
         h = sH[par]; p = sP[par];
-        if (c == space_id) { h = sHc[par]; p = 0; }                        // (at the root hc = h)
-        else if (c == eos_id) {
-          int arc;
-          ngram_walk(G, sHc[par], eos_w, arc);
-          h = ngram_node(G, G.next[arc]); p = 0;
-        } else if (c != go_id && c != 0) {
-          if (p >= 0) p = trie_child(T, p, c);
-        }
+        M.advance(h, p, sHc[par], sTok[tid]);
       }
-      float cl = 0.f;
-      int hc = h, arc;
-      if (p != 0) cl = close(h, p, hc);
+      float cl, eos;
+      int hc;
+      M.scalars(h, p, cl, hc, eos);
       const int nw = sNew[tid];
-      sH[nw] = h; sP[nw] = p; sClose[nw] = cl; sHc[nw] = hc; sEos[nw] = cl + ngram_walk(G, hc, eos_w, arc);
+      sH[nw] = h; sP[nw] = p; sClose[nw] = cl; sHc[nw] = hc; sEos[nw] = eos;
     }
     lds_barrier();
-    for (int e = tid; e < M * V; e += 256) {
-      const int m = e / V, c = e - m * V, nw = sNew[m], p = sP[nw];
-      float v;
-      if (c == space_id) v = sClose[nw];
-      else if (c == eos_id) v = sEos[nw];
-      else if (c == go_id || c == 0) v = CPW_FLOOR;
-      else v = (p < 0 || trie_child(T, p, c) >= 0) ? 0.f : oov;
-      sLam[nw * V + c] = v;
+    for (int e = tid; e < M_ * V; e += 256) {
+      const int m = e / V, c = e - m * V, nw = sNew[m];
+      sLam[nw * V + c] = M.value(sP[nw], c, sClose[nw], sEos[nw]);
     }
     lds_barrier();
   }
@@ -117,8 +65,7 @@ struct cpw_step {
 // dynamic LDS: cp_lds_words(V, W, L_max, true, 10 W) words
 __global__ __launch_bounds__(256) void ctc_prefix_word_ngram_kernel(const avsr_ctc_prefix_args A, const avsr_ctc_prefix_word_ngram G) {
   extern __shared__ __attribute__((aligned(16))) uint32_t cpw_smem[];
-  cpw_step step{ngram_view_of(G), trie_view{G.n_trie_nodes, G.n_trie_arcs, G.t_begin, G.t_sym, G.t_next, G.t_word},
-                G.V, G.Vw, G.start, G.eos_w, G.unk_id, G.space_id, G.go_id, G.eos_id, G.oov, nullptr, nullptr, nullptr, nullptr, nullptr};
+  cpw_step step{word_model_of(G), nullptr, nullptr, nullptr, nullptr, nullptr};
   const cp_terms terms{G.weight, G.bonus, G.go_id, G.eos_id, G.s_lm, G.lm_steps, G.lm_logp};
   cp_search(A, terms, step, cpw_smem);
 }

@@ -102,6 +102,9 @@ class LM(object):
         if kwargs.get('ngram_lm') is not None:
             raise ValueError("ngram_lm: an n-gram is fused into the recogniser's beam search (AVSR(ngram_lm=...)); the language model "
                              "trains and scores alone")
+        if kwargs.get('word_ngram_lm') is not None:
+            raise ValueError("word_ngram_lm: a word-level n-gram is fused into the recogniser's beam search (AVSR(word_ngram_lm=...)); "
+                             "the language model trains and scores alone")
         reverse = {v: k for k, v in self._unit_dict.items()}
         common = dict(architecture='lm', video_units=None, audio_units=None, cell_type=cell_type,
                       decoder_units=tuple(decoder_units_per_layer), embedding_size=embedding_size,

@@ -10,7 +10,7 @@ import os
 import numpy as np
 import torch
 from . import ops, params as PR
-from ._lib import AttnRnn, BEAM_CTC_MAX_T, BEAM_CTC_MAX_V, BeamCtc, BeamLm, BeamNgram, MAX_LM_LAYERS, RnnStack
+from ._lib import AttnRnn, BEAM_CTC_MAX_T, BEAM_CTC_MAX_V, BeamCtc, BeamLm, BeamNgram, BeamWordNgram, MAX_LM_LAYERS, RnnStack
 from .config import ATT_CODE, BAHDANAU_TYPES, CELL_ID_DECODER, LUONG_TYPES, ModelConfig, encoder_cell_id
 from .model_base import Batch, Ref, SeqBuf, _FlagReader, _PtrView, _splitk, desc_steplen  # noqa: F401
 
@@ -427,23 +427,25 @@ class DecoderMixin:
     def beam_search_decode(self, *args, **kw):
         """See _beam_search_decode.  If a persistent kernel's bounded wait expired during the pass (workgroups not co-resident) the
         results are invalid: check_persistent() has then switched the one-launch paths off and the pass is redone with one launch
-        per step (the ids written to .mlf files and error rates never come from a flagged pass); the redo carries `lm`, `ngram` and
-        `ctc_weight` along."""
+        per step (the ids written to .mlf files and error rates never come from a flagged pass); the redo carries `lm`, `ngram`,
+        `word_ngram` and `ctc_weight` along."""
         return self._redo_if_flagged(self._beam_search_decode, *args, **kw)
 
-    def greedy_decode(self, *args, lm=None, ctc_weight=0.0, ngram=None, **kw):
+    def greedy_decode(self, *args, lm=None, ctc_weight=0.0, ngram=None, word_ngram=None, **kw):
         """See _greedy_decode; redone through the per-step launches if a persistent kernel flagged its pass (as above)."""
         if lm is not None:
             raise ValueError("greedy_decode: language-model fusion is defined on the beam (beam_search_decode(lm=...))")
         if ngram is not None:
             raise ValueError("greedy_decode: n-gram fusion is defined on the beam (beam_search_decode(ngram=...))")
+        if word_ngram is not None:
+            raise ValueError("greedy_decode: word n-gram fusion is defined on the beam (beam_search_decode(word_ngram=...))")
         if ctc_weight != 0.0:
             raise ValueError("greedy_decode: joint CTC / attention scoring is defined on the beam (beam_search_decode(ctc_weight=...))")
         return self._redo_if_flagged(self._greedy_decode, *args, **kw)
 
     def _beam_search_decode(self, batch: Batch, beam_width: int = 10, length_penalty_weight: Optional[float] = None,
                             max_steps: Optional[int] = None, check_every: int = 8, return_all: bool = False, lm=None,
-                            lm_weight: float = 0.0, ctc_weight: float = 0.0, ngram=None):
+                            lm_weight: float = 0.0, ctc_weight: float = 0.0, ngram=None, word_ngram=None):
         """Eval graph with BeamSearchDecoder (decoder_unimodal.py:222-271, decoder_bimodal.py:328-381): ids of beam 0,
         int32 [B, T_out]; positions after the first EOS hold EOS (gather_tree).  length_penalty_weight defaults to the
         reference's 0.6 (unimodal / av_align) or 0.5 (bimodal).
@@ -454,8 +456,16 @@ class DecoderMixin:
         ngram: instead of lm, the tables of a back-off n-gram (ngram.compile_tables / ngram.load_tables) -- the same rule with
         lam(v | GO, labels) read from the automaton: lm_weight * lam on every symbol of an unfinished beam, EOS included, one table-walk
         launch per step (avsr_beam_ngram; csrc/beam_ngram.hip).  The tables are uploaded once per model object; lm and ngram together
-        are refused.  It works together with ctc_weight."""
+        are refused.  It works together with ctc_weight.
+        word_ngram: instead of either, the tables of a WORD-level back-off n-gram behind a lexicon trie (ngram.compile_word_tables /
+        ngram.load_word_tables) for a model over single-character units -- lam(v | labels) is the word rule of INTEGRATION.md section 8:
+        letters inside the lexicon are free, the letter that leaves it pays the oov score once, a space or EOS that closes a word pays
+        the word model (avsr_beam_word_ngram; csrc/beam_word_ngram.hip).  The ten arrays are uploaded once per model object and shared
+        with ctc_prefix_beam_search(word_ngram=...); refused together with lm or ngram.  It works together with ctc_weight."""
         cfg, K = self.cfg, int(beam_width)
+        if word_ngram is not None and (lm is not None or ngram is not None):
+            raise ValueError("beam search takes one language model: word_ngram (word-level tables behind a lexicon) cannot be combined "
+                             "with lm or ngram")
         if lm is not None and ngram is not None:
             raise ValueError("beam search takes one language model: lm (an avsr.LM network) or ngram (back-off tables), not both")
         if ngram is not None:
@@ -463,6 +473,15 @@ class DecoderMixin:
             if (ngram["V"], ngram["go_id"], ngram["eos_id"]) != (cfg.vocab_size, cfg.go_id, cfg.eos_id):
                 raise ValueError("beam search: the n-gram tables were compiled for V = %d, GO = %d, EOS = %d; the model has %d, %d, %d"
                                  % (ngram["V"], ngram["go_id"], ngram["eos_id"], cfg.vocab_size, cfg.go_id, cfg.eos_id))
+        if word_ngram is not None:
+            g = word_ngram
+            lm_weight = self._require_weight("beam search", "lm_weight", lm_weight)
+            if (g["V"], g["go_id"], g["eos_id"]) != (cfg.vocab_size, cfg.go_id, cfg.eos_id):
+                raise ValueError("beam search: the word n-gram tables were compiled for V = %d, GO = %d, EOS = %d; the model has %d, %d, %d"
+                                 % (g["V"], g["go_id"], g["eos_id"], cfg.vocab_size, cfg.go_id, cfg.eos_id))
+            if not 0 < g["space_id"] < cfg.vocab_size or g["space_id"] in (cfg.go_id, cfg.eos_id):
+                raise ValueError("beam search: the word n-gram tables hold the space as class %d, which is no unit of the model (V = %d, "
+                                 "GO = %d, EOS = %d)" % (g["space_id"], cfg.vocab_size, cfg.go_id, cfg.eos_id))
         ctc_weight = self._require_weight("beam search", "ctc_weight", float(ctc_weight))
         if ctc_weight != 0.0 and not cfg.use_ctc:
             raise ValueError("beam search: ctc_weight needs a model built with use_ctc=True")
@@ -520,7 +539,9 @@ class DecoderMixin:
         ops.zero_multi([fin, ln])
         lmd = self._beam_lm_desc(lm, lm_weight, X, R) if lm is not None else None
         ngd = self._beam_ngram_desc(ngram, lm_weight, X, R) if ngram is not None else None
-        cd = self._beam_ctc_desc(ws, ctc_weight, X, B, K, lmd if ngd is None else ngd) if ctc_weight != 0.0 else None
+        wnd = self._beam_word_ngram_desc(word_ngram, lm_weight, X, R) if word_ngram is not None else None
+        fused = lmd if lmd is not None else ngd if ngd is not None else wnd
+        cd = self._beam_ctc_desc(ws, ctc_weight, X, B, K, fused) if ctc_weight != 0.0 else None
         self._decoder_init_state(wsb)
         self._block_prepare(wsb, D)
         d = self._block_desc(wsb, D, D["steplen"], 3, D["h0"], D["c0"], with_bwd=False)
@@ -533,6 +554,8 @@ class DecoderMixin:
         def launch(l, l1):
             if ngd is not None:
                 ops.attn_rnn_fwd_ngram(d, ngd, cd, l, l1)
+            elif wnd is not None:
+                ops.attn_rnn_fwd_word_ngram(d, wnd, cd, l, l1)
             elif cd is not None:
                 ops.attn_rnn_fwd_ctc(d, lmd, cd, l, l1)
             elif lmd is None:
@@ -598,10 +621,34 @@ class DecoderMixin:
                              "avsr_beam_ngram_supported" % (g.n_nodes, g.n_arcs, g.start, V))
         return g
 
+    def _beam_word_ngram_desc(self, tables, lm_weight, X, R):
+        """avsr_beam_word_ngram over the word automaton and lexicon trie `tables` (their ten arrays on the device once per model object,
+        shared with the CTC prefix search: _ngram_device_tables); the (h, p, hc) ping-pong and the log-probability scratch live in the
+        cached beam workspace X."""
+        fresh = id(tables) not in self.__dict__.get("_ngram_tables", {})
+        tb, V = self._ngram_device_tables(tables, self.WORD_NGRAM_TABLES), self.cfg.vocab_size
+        if "word_ngram" not in X:
+            X["word_ngram"] = dict(state=torch.zeros(2, 3, R, dtype=torch.int32, device=self.dev), logp=torch.zeros(R, V, device=self.dev))
+        buf = X["word_ngram"]
+        g = BeamWordNgram()
+        for k in ("n_nodes", "n_arcs", "Vw", "start", "eos_w", "unk_id", "n_trie_nodes", "n_trie_arcs", "space_id", "go_id", "eos_id"):
+            setattr(g, k, int(tables[k]))
+        g.V, g.n_rows, g.lm_weight, g.oov = V, R, float(lm_weight), float(tables["oov_score"])
+        for k in self.WORD_NGRAM_TABLES:
+            setattr(g, k, ops.fptr(tb[k]))
+        g.state, g.lm_logp = ops.fptr(buf["state"]), ops.fptr(buf["logp"])
+        if not ops.beam_word_ngram_supported(g):
+            if fresh:
+                self._ngram_tables.pop(id(tables), None)                   # refused tables are not kept on the device
+            raise ValueError("beam search: the word n-gram tables (%d nodes, %d arcs over %d words; %d trie nodes, %d trie arcs; oov %r) "
+                             "are outside avsr_beam_word_ngram_supported: word automata and lexicon tries of up to %d nodes and %d arcs "
+                             "each" % (g.n_nodes, g.n_arcs, g.Vw, g.n_trie_nodes, g.n_trie_arcs, g.oov, 1 << 24, 1 << 26))
+        return g
+
     def _beam_ctc_desc(self, ws, weight, X, B, K, lmd):
         """avsr_beam_ctc over the head's logits of this batch (_ctc_head, encoders in evaluation mode); log-probabilities, the state
         ping-pong, term and the pre-combined buffer live in the cached beam workspace X.  Queues avsr_beam_ctc_begin.  lmd: the fused
-        model's descriptor (a BeamLm or a BeamNgram: both carry lm_logp and lm_weight), or None."""
+        model's descriptor (a BeamLm, a BeamNgram or a BeamWordNgram: all carry lm_logp and lm_weight), or None."""
         cfg, dev = self.cfg, self.dev
         E, Cc = self._ctc_head(ws)
         T, V, R = E["T"], cfg.vocab_size, B * K

@@ -227,6 +227,23 @@ def attn_rnn_fwd_ngram(desc, ng_desc, ctc_desc, l_begin, l_end):
                                        int(l_end), _s()), "avsr_attn_rnn_fwd_ngram")
 
 
+def beam_word_ngram_supported(desc):
+    """Host-side: does avsr_beam_word_ngram_step run this descriptor (a _lib.BeamWordNgram)?"""
+    return bool(_L().avsr_beam_word_ngram_supported(C.byref(desc)))
+
+
+def beam_word_ngram_step(desc, tok, parent_rows, n_rows, step):
+    """One word-level n-gram step over the hypothesis rows (include/avsr_hip.h avsr_beam_word_ngram): writes desc.lm_logp and the other
+    half of desc.state."""
+    check(_L().avsr_beam_word_ngram_step(C.byref(desc), fptr(tok), fptr(parent_rows), int(n_rows), int(step), _s()),
+          "avsr_beam_word_ngram_step")
+
+
+def attn_rnn_fwd_word_ngram(desc, wn_desc, ctc_desc, l_begin, l_end):
+    check(_L().avsr_attn_rnn_fwd_word_ngram(C.byref(desc), C.byref(wn_desc), C.byref(ctc_desc) if ctc_desc is not None else None,
+                                            int(l_begin), int(l_end), _s()), "avsr_attn_rnn_fwd_word_ngram")
+
+
 def beam_ctc_supported(desc):
     return bool(_L().avsr_beam_ctc_supported(C.byref(desc)))
 

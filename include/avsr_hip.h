@@ -767,6 +767,57 @@ int avsr_beam_ngram_step(const avsr_beam_ngram* ng, const int32_t* tok, const in
 int avsr_attn_rnn_fwd_ngram(const avsr_attn_rnn* d, const avsr_beam_ngram* ng, const avsr_beam_ctc* ctc, int32_t l_begin, int32_t l_end,
                             void* stream);
 
+/* Shallow fusion of the WORD-level back-off n-gram behind a lexicon trie into BEAM SEARCH over character units
+ * (csrc/beam_word_ngram.hip), the counterpart of avsr_beam_ngram with avsr_ctc_prefix_word_ngram's model:
+ *   step_logp[k][v] = log_softmax(logits_am[k])[v] + lm_weight * lam(v | g_k)  (+ the CTC term of avsr_beam_ctc)         (unfinished beam k)
+ * lam is exactly the value of avsr_ctc_prefix_word_ngram (the table of cases above: letters, space, EOS, MASK / GO), formed by the one
+ * copy of the model's side both kernels include (csrc/word_ngram_walk.h): fp32 additions in its fixed order, so ngram.py word_lam gives
+ * the same bits; always finite.  EOS gets its term like any other symbol; a finished beam continues with EOS at 0 and no term;
+ * lm_weight == 0 reproduces the search without a model bit for bit.  No length bonus.  The ten tables and the scalars are
+ * avsr_ctc_prefix_word_ngram's (ngram.py compile_word_tables).
+ * State: (h, p, hc) per hypothesis row -- the automaton node of the closed words, the trie node of the open word (0 = root, -1 = OOV)
+ * and the node a space would leave (h at the root) -- as int32 state [2][3][n_rows]: step s reads half s & 1 at parent_rows[r] and
+ * writes half (s + 1) & 1 at r; step 0 puts every row at (start, 0, start) and reads neither tok nor the other half.  A row whose tok
+ * is EOS transitions like any other; its values are never read.  tok / parent_rows outside [0, V) / [0, n_rows) are clamped to 0, a
+ * stale h or hc outside [0, n_nodes) to 0, a stale p outside [-1, n_trie_nodes) to the root: nothing outside the buffers is addressed.
+ * Limits: avsr_beam_ngram's on the automaton (over Vw word ids: 2 <= Vw <= n_arcs), n_rows and lm_weight, and
+ * avsr_ctc_prefix_word_ngram's on the trie and scalars: 1 <= n_trie_nodes <= AVSR_CTC_PREFIX_NGRAM_MAX_NODES, 1 <= n_trie_arcs <=
+ * AVSR_CTC_PREFIX_NGRAM_MAX_ARCS, 0 <= eos_w < Vw, -1 <= unk_id < Vw, space_id, go_id and eos_id distinct classes below V, oov finite
+ * and <= 0.  No beam-width limit of its own: beam search's hold (K <= 64, K * V <= 1024). */
+typedef struct avsr_beam_word_ngram {
+  int32_t n_nodes, n_arcs, Vw, start;
+  int32_t eos_w, unk_id, n_trie_nodes, n_trie_arcs;
+  int32_t V, space_id, go_id, eos_id;
+  int32_t n_rows;
+  float lm_weight, oov;
+  int32_t pad_;
+  const float* bow;
+  const int32_t* backoff;
+  const int32_t* arc_begin;
+  const int32_t* sym;
+  const float* logp;
+  const int32_t* next;
+  const int32_t* t_begin;
+  const int32_t* t_sym;
+  const int32_t* t_next;
+  const int32_t* t_word;
+  int32_t* state;      /* [2][3][n_rows]: h, p, hc */
+  float* lm_logp;      /* [n_rows][V] */
+} avsr_beam_word_ngram;
+/* 1 if avsr_beam_word_ngram_step runs this descriptor, else 0 (decided on the host; nothing is dereferenced). */
+int avsr_beam_word_ngram_supported(const avsr_beam_word_ngram* wn);
+/* One word-model step over n_rows (== wn->n_rows) hypothesis rows: the transition into the other half of state, then lm_logp[r][c] =
+ * lam(c | row r's labels) for every c < V.  One launch, plain loads and vector stores, no atomics: two launches are bit-identical.
+ * AVSR_ERR_ARG for a NULL / non-positive / inconsistent argument, AVSR_ERR_UNSUPPORTED outside the limits: both before any launch. */
+int avsr_beam_word_ngram_step(const avsr_beam_word_ngram* wn, const int32_t* tok, const int32_t* parent_rows, int32_t n_rows, int32_t step,
+                              void* stream);
+/* avsr_attn_rnn_fwd in mode 3 with avsr_beam_word_ngram_step ahead of every selection (wn->n_rows == d->B, wn->V == d->V), under every
+ * avsr_attn_rnn_set_beam_kernel setting; ctc as in avsr_attn_rnn_fwd_ngram (ctc->lm_logp must be wn->lm_logp; ctc->weight == 0: no CTC
+ * launch).  A step queued after the search has ended advances the states harmlessly and its output is not read.  Two fused models in
+ * one search are not built. */
+int avsr_attn_rnn_fwd_word_ngram(const avsr_attn_rnn* d, const avsr_beam_word_ngram* wn, const avsr_beam_ctc* ctc, int32_t l_begin,
+                                 int32_t l_end, void* stream);
+
 /* CTC forced alignment (csrc/ctc_align.hip; the rule is this project's own): the single most probable
  * alignment (Viterbi path) of a GIVEN label row to the frames of the head.  z [B * T][ld] are the head's logits over V + 1 real classes,
  * the blank is class V; in_len [B], T_b = clamp(in_len, 0, T); labels [B][L], target_len [B], U = clamp(target_len, 0, L) -- a plain
